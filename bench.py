@@ -34,6 +34,9 @@ sys.path.insert(0, REPO)
 HBM_PEAK_GBPS = 8000.0      # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 N_PRIME = 3                 # untimed frames after the index build (first tables, first blend models), volume cleared after them
 MIN_STAT_FRAMES = 40        # frame_stats percentiles are taken over at least this many consecutive frames of the sweep
+DUMP_LIMIT_BYTES = 64 * 10 ** 6     # --dump-outputs: the files' total
+DUMP_VOXELS = 1 << 22               # --dump-outputs: voxel indices drawn for the volume sample
+DUMP_SEED = 20261015
 
 
 def parse(argv=None):
@@ -97,7 +100,42 @@ def parse(argv=None):
     ap.add_argument("--no-pipeline", action="store_true", help="(the default; kept for A/B command lines)")
     ap.add_argument("--no-prefetch", action="store_true",
                     help="A/B switch: DF_WARP_NO_PREFETCH on every warped integrate (no look-ahead table / model builds on the handle's side stream)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed frames, write what the last one computed to DIR as .npy (float32): the ray-cast's points, normals and hit mask, "
+                         "and the tsdf and weight of a fixed, seeded sample of the volume's voxels (at most %d MB in all).  The inputs are the same "
+                         "from run to run, so two builds can be compared file by file" % (DUMP_LIMIT_BYTES // 10 ** 6))
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
+    return args
+
+
+def dump_outputs(out_dir, pts, nrm, vol_data):
+    """What the timed path hands its caller after the last timed frame: the ray-cast's points and normals (rows x cols x 4; the
+    caller gets NaN where a ray missed, the files zeros, with hit_mask = 1 where it hit) and the volume (lo16 = half tsdf, hi16 = weight per voxel), the volume as a sample at DUMP_SEED-drawn voxel indices
+    (sorted, duplicates dropped; every voxel if the volume is smaller), which depend on the volume's size only."""
+    os.makedirs(out_dir, exist_ok=True)
+    p, n = pts.cpu().numpy().astype(np.float32), nrm.cpu().numpy().astype(np.float32)
+    hit = np.isfinite(p).all(-1) & np.isfinite(n).all(-1)
+    p[~hit] = 0.0; n[~hit] = 0.0                 # (every file finite: a missed ray's NaN point and normal become zeros, hit_mask says which)
+    img = {"points": p, "normals": n, "hit_mask": hit.astype(np.float32)}
+    flat = vol_data.reshape(-1)
+    n_vox = flat.numel()
+    n_img = sum(a.nbytes for a in img.values())
+    n_max = min(DUMP_VOXELS, (DUMP_LIMIT_BYTES - n_img - (1 << 16)) // 8)     # two float32 per voxel; (1 << 16): the .npy headers
+    if n_vox <= n_max:
+        idx = np.arange(n_vox, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n_vox, size=n_max, dtype=np.int64))
+    vox = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy().view(np.uint32)
+    img["tsdf_sample"] = (vox & 0xFFFF).astype(np.uint16).view(np.float16).astype(np.float32)
+    img["weight_sample"] = (vox >> 16).astype(np.float32)
+    for name, a in img.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": {k: list(a.shape) for k, a in img.items()}, "voxels_in_volume": int(n_vox), "sample_seed": DUMP_SEED,
+            "bytes": int(sum(a.nbytes for a in img.values()))}
 
 
 def config_of(args):
@@ -446,6 +484,9 @@ def main():
     if os.environ.get("DFUSION_BENCH_TEST_FAIL_RANK") == str(rank):          # test hook: the launcher must report a failing rank
         raise RuntimeError("DFUSION_BENCH_TEST_FAIL_RANK: rank %d fails on purpose" % rank)
     n_dev = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    if args.dump_outputs is not None and (n_dev == 0 or world > 1 or force_dist):
+        raise SystemExit("bench.py: --dump-outputs needs one unsharded rank on a GPU (%s)"
+                         % ("no GPU visible" if n_dev == 0 else "WORLD_SIZE=%d, DFUSION_BENCH_FORCE_DIST=%d" % (world, force_dist)))
     if n_dev == 0:
         return dry_run(args, rank, world)
     # DFUSION_BENCH_FORCE_DIST=1: take the N > 1 code path (RCCL process group, slab volume, broadcast, the merge collectives) with
@@ -750,6 +791,7 @@ def main():
         elapsed = float(t.item())
     vol_end = vol.data().clone() if verify else None
     timed_frames = [(i0 + i) % F for i in range(args.steps)]
+    dumped = dump_outputs(args.dump_outputs, pts, nrm, vol.data()) if args.dump_outputs is not None else None
 
     # ---- the sweep goes on (untimed by the wall clock, HIP events per frame) until the percentiles have MIN_STAT_FRAMES samples; these
     # frames also carry the per-stage events (sharded.StageTimer: every collective and kernel stage of the frame, per rank) -- not the
@@ -1139,6 +1181,8 @@ def main():
                                  "also streams its per-voxel k-NN + weight cache (48 B/voxel at k=8), see DESIGN.md"},
         }
         out.update(extra)
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if verify_cull is not None:
             out["verify_cull"] = verify_cull
         if rebalance is not None:

@@ -1,22 +1,22 @@
 """TEST INFRASTRUCTURE: builds the REFERENCE'S OWN apps/demo.cpp, unmodified, against this repository's kfusion mirror.
 
     /root/reference/apps/demo.cpp  +  dynamicfusion_amd/host (mirror, compiled with -DKFUSION_USE_OPENCV)  +  tests/opencv_stub
-    ->  tests/_demo_ref/libkfusion_hip_cv.so, tests/_demo_ref/demo_ref
+    ->  oracle/_ref/demo_ref/libkfusion_hip_cv.so, oracle/_ref/demo_ref/demo_ref
 
 OpenCV is not installed in this image; tests/opencv_stub supplies the OpenCV names demo.cpp uses (windows become files).  The source
-is read where it lies under /root/reference -- nothing is copied -- and the outputs are git-ignored but travel to the GPU box with the
-gpurun snapshot, where tests/test_demo_ref.py runs the binary (/root/reference does not exist there).
+is read where it lies under /root/reference -- nothing is copied.  The outputs go under oracle/_ref/ with the other reference-built
+checkers: git-ignored, and carried to a GPU machine with the built tree, where tests/test_demo_ref.py runs the binary without the reference.
 """
 import os
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
-OUT = os.path.join(HERE, "_demo_ref")
+OUT = os.path.join(HERE, "_ref", "demo_ref")
 DEMO_SRC = "/root/reference/apps/demo.cpp"
 LIB = os.path.join(OUT, "libkfusion_hip_cv.so")
 APP = os.path.join(OUT, "demo_ref")
-STUB = os.path.join(HERE, "opencv_stub")
+STUB = os.path.join(REPO, "tests", "opencv_stub")
 HOST = os.path.join(REPO, "dynamicfusion_amd", "host")
 
 
@@ -38,7 +38,7 @@ def syntax_check():
 
 
 def build(force=False):
-    """Returns the path of the demo binary (built here when the reference is present, else whatever travelled with the snapshot)."""
+    """Returns the path of the demo binary (built here when the reference is present, else the one built with the tree, if any)."""
     if not have_reference():
         return APP if os.path.exists(APP) else None
     from dynamicfusion_amd import build as B
@@ -51,7 +51,7 @@ def build(force=False):
     os.makedirs(OUT, exist_ok=True)
     common, rocm = flags()
     link = ["-L", os.path.join(REPO, "dynamicfusion_amd"), "-ldfusion_hip", "-L", os.path.join(rocm, "lib"), "-lamdhip64"]
-    rpath = ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/../../dynamicfusion_amd"]
+    rpath = ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/../../../dynamicfusion_amd"]
     subprocess.check_call(common + ["-fPIC", "-shared", src, stub_cpp, "-o", LIB] + link + rpath)
     subprocess.check_call(common + [DEMO_SRC, "-o", APP, "-L", OUT, "-lkfusion_hip_cv"] + link + rpath)
     return APP

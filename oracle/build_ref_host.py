@@ -2,19 +2,20 @@
 
     /root/reference/kfusion/src/{tsdf_volume.cpp, imgproc.cpp, precomp.cpp, device_memory.cpp}      (unmodified, read where they lie)
   + tests/ref_host_bridge/hip_bridge.cpp     (kfusion::device::*  ->  the C-ABI of libdfusion_hip.so: what a maintainer adds)
-    ->  tests/ref_host_bridge/_build/libkfusion_refhost.so
-  + tests/ref_host_bridge/ref_host_frame.cpp (driver)  ->  tests/ref_host_bridge/_build/ref_host_frame
+    ->  oracle/_ref/ref_host/libkfusion_refhost.so
+  + tests/ref_host_bridge/ref_host_frame.cpp (driver)  ->  oracle/_ref/ref_host/ref_host_frame
 
 with g++ against the reference's own headers, tests/opencv_stub (OpenCV is not installed in this image) and tests/ref_host_bridge/shim
 (a dozen cudaX -> hipX names for the reference's safe_call.hpp / device_memory.cpp; a two-line stand-in for the absent third-party
-Opt solver header that kfusion/kinfu.hpp pulls in).  Nothing is copied out of /root/reference; the outputs are git-ignored but travel to the
-GPU box with the gpurun snapshot, where tests/test_gpu_ref_host_bridge.py runs the binary (/root/reference does not exist there)."""
+Opt solver header that kfusion/kinfu.hpp pulls in).  Nothing is copied out of /root/reference.  The outputs go under oracle/_ref/ with the
+other reference-built checkers: git-ignored, and carried to a GPU machine with the built tree, where tests/test_gpu_ref_host_bridge.py runs the
+binary without the reference."""
 import os
 import subprocess
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+HERE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "ref_host_bridge")    # the bridge's sources
 REPO = os.path.dirname(os.path.dirname(HERE))
-OUT = os.path.join(HERE, "_build")
+OUT = os.path.join(REPO, "oracle", "_ref", "ref_host")
 REF = "/root/reference/kfusion"
 LIB = os.path.join(OUT, "libkfusion_refhost.so")
 APP = os.path.join(OUT, "ref_host_frame")
@@ -33,7 +34,7 @@ def flags():
 
 
 def build(force=False):
-    """Returns the driver's path (built here when the reference is present, else whatever travelled with the snapshot)."""
+    """Returns the driver's path (built here when the reference is present, else the one built with the tree, if any)."""
     if not have_reference():
         return APP if os.path.exists(APP) else None
     import sys

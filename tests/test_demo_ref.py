@@ -3,18 +3,20 @@
 OpenCV is absent from this image, so the file is compiled against tests/opencv_stub (the OpenCV names it uses; windows are files) and
 the mirror built with -DKFUSION_USE_OPENCV, where getNodesAsMat() / get_cloud_host() return cv::Mat and KinFu::Ptr is cv::Ptr<KinFu>
 exactly as in the reference's headers (kfusion/include/kfusion/kinfu.hpp:52, warp_field.hpp:78, cuda/tsdf_volume.hpp:24-28).
-  * CPU (where /root/reference exists): the file compiles UNMODIFIED and links into tests/_demo_ref/demo_ref;
-  * GPU: the binary -- built in the container, travelled with the snapshot -- runs its own frame loop on a synthetic sequence; every
+  * CPU (where /root/reference exists): the file compiles UNMODIFIED and links into oracle/_ref/demo_ref/demo_ref (oracle/build_demo_ref.py);
+  * GPU: the binary -- built with the tree where the reference exists, carried with oracle/_ref -- runs its own frame loop on a synthetic sequence; every
     "Scene" window it shows and the "warp_field" cloud equal, byte for byte, what host/apps/demo_calls.cpp (the look-alike of round 2,
     same calls through the non-OpenCV build of the mirror) produces on the same frames."""
 import os
 import struct
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-import build_demo_ref as D
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+import build_demo_ref as D          # noqa: E402  (oracle/build_demo_ref.py)
 from dynamicfusion_amd import build, synth
 
 F32 = np.float32
@@ -47,7 +49,7 @@ def write_raw(path, arr, cv_type):
 def test_reference_demo_binary_runs_and_matches_demo_calls(tmp_path):
     app = D.build()
     if not app:
-        pytest.skip("tests/_demo_ref/demo_ref was not built (needs /root/reference in the build container)")
+        pytest.skip("oracle/_ref/demo_ref/demo_ref was not built (needs /root/reference where the tree was built)")
     # demo.cpp takes its parameters from default_params_dynamicfusion(): 640 x 480, 256^3 / 1 m, fx = fy = 570.342 (kinfu.cpp:15-50)
     cfg = synth.Config(256, 1.0, cols=640, rows=480, nodes=0, k=8)
     frames = 4

@@ -1,12 +1,12 @@
 """INTEGRATION.md section A, for real: the REFERENCE'S OWN host class drives the HIP kernels.
 
-tests/ref_host_bridge/build_ref_host.py compiles kfusion/src/{tsdf_volume, imgproc, precomp, device_memory}.cpp UNMODIFIED -- where they lie under
+oracle/build_ref_host.py compiles kfusion/src/{tsdf_volume, imgproc, precomp, device_memory}.cpp UNMODIFIED -- where they lie under
 /root/reference, against the reference's own headers -- plus ONE added translation unit, tests/ref_host_bridge/hip_bridge.cpp, which
 defines the kfusion::device::* functions of the reference's private header (kfusion/src/internal.hpp:104-143) by forwarding them to the
 C-ABI of libdfusion_hip.so.  That is the patch a maintainer of the reference would make (delete the .cu files, add the bridge).
   * CPU (where /root/reference exists): the build succeeds, leaves no kfusion::device::* symbol undefined, and the library takes its
     TsdfVolume from the REFERENCE's tsdf_volume.cpp, not from this repository's mirror;
-  * GPU: the binary (built in the container, travelled with the snapshot) runs kfusion::cuda::TsdfVolume::{clear, integrate, raycast x2,
+  * GPU: the binary (built with the tree where the reference exists, carried with oracle/_ref) runs kfusion::cuda::TsdfVolume::{clear, integrate, raycast x2,
     compute_points, compute_normals} and cuda::computeDists of the reference on the MI355X, and every output equals the oracle's bit for
     bit (kfusion/src/tsdf_volume.cpp:89-174,184-220,312-324; kinfu.cpp:226,248,297,398-399);
   * round 6: ALL 20 forwards of the bridge run -- the front-end through the reference's own imgproc.cpp wrappers
@@ -26,8 +26,8 @@ from dynamicfusion_amd import synth
 from scene import Scene, compare_volumes
 from test_gpu_cxx_host import cxx_inv, cxx_mul
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_host_bridge"))
-import build_ref_host as RB          # noqa: E402  (tests/ref_host_bridge/build_ref_host.py)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+import build_ref_host as RB          # noqa: E402  (oracle/build_ref_host.py)
 
 F32 = np.float32
 
@@ -54,7 +54,7 @@ def test_reference_host_layer_builds_unmodified_over_the_bridge():
 def test_reference_tsdf_volume_class_on_the_gpu_matches_oracle(tmp_path):
     app = RB.build()
     if not app:
-        pytest.skip("tests/ref_host_bridge/_build/ref_host_frame was not built (needs /root/reference in the build container)")
+        pytest.skip("oracle/_ref/ref_host/ref_host_frame was not built (needs /root/reference where the tree was built)")
     cfg = synth.Config(64, 1.0, cols=160, rows=120, nodes=0, k=8)
     frames = 3
     sc = Scene(cfg, n_frames=frames)

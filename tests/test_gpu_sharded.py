@@ -202,6 +202,27 @@ def test_bench_force_dist_self_launch_is_one_real_rccl_rank():
     assert d["verify_cull"]["cull_bit_identical"] and d["value"] > 0
 
 
+def test_bench_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs: what the last of --steps timed frames computed, written after the timed region; two runs with the same arguments
+    dump the same bytes (the inputs are seeded), and the images are a ray-cast that hit the scene."""
+    import numpy as np
+    common = ["--config", "256", "--steps", "4", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--long-frames", "0", "--no-verify-cull"]
+    runs = []
+    for tag in ("a", "b"):
+        d = _bench(common + ["--dump-outputs", str(tmp_path / tag)])
+        assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["dump_outputs"]["dir"] == str(tmp_path / tag)
+        runs.append({p.stem: np.load(p) for p in (tmp_path / tag).glob("*.npy")})
+    a, b = runs
+    assert set(a) == {"points", "normals", "hit_mask", "tsdf_sample", "weight_sample"} and all(v.dtype == np.float32 for v in a.values())
+    assert a["points"].shape == a["normals"].shape == (480, 640, 4) and a["hit_mask"].shape == (480, 640)
+    assert a["tsdf_sample"].shape == a["weight_sample"].shape and all(np.isfinite(v).all() for v in a.values())
+    for k in a:
+        assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
+    miss = a["hit_mask"] == 0
+    assert set(np.unique(a["hit_mask"])) == {0.0, 1.0} and not a["points"][miss].any() and not a["normals"][miss].any()
+    assert (a["weight_sample"] > 0).any()
+
+
 def test_alive_block_profile_of_slabs_adds_up_to_the_unsharded_one():
     """dfusion_warp_alive_blocks (the measured re-balance's input): per 8-plane layer, the blocks a sweep's verdict pass kept.  With the
     ball test alone (no block models: a verdict then depends on the block and the frame only) the profiles of two slabs, each counting
