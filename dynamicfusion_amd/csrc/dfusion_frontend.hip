@@ -55,6 +55,7 @@ extern "C" int dfusion_bilateral_filter(const uint16_t* src, size_t src_pitch, u
                                         int kernel_size, float sigma_spatial, float sigma_depth, dfStream stream)
 {
     if (!src || !dst || src == dst || cols <= 0 || rows <= 0 || kernel_size <= 0 || !(sigma_spatial > 0.f) || !(sigma_depth > 0.f)) return DF_E_INVALID;
+    if (!df_pitch_ok(src_pitch, cols, 2) || !df_pitch_ok(dst_pitch, cols, 2)) return DF_E_INVALID;
     sigma_depth *= 1000;                                                                 // :50 metres -> mm
     hipLaunchKernelGGL(df_bilateral_kernel, FE_GRID(cols, rows), dim3(256), 0, (hipStream_t)stream, src, src_pitch, dst, dst_pitch, cols,
                        rows, kernel_size, 0.5f / (sigma_spatial * sigma_spatial), 0.5f / (sigma_depth * sigma_depth));   // :56
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(256) void df_truncate_kernel(uint16_t* depth, size_
 
 extern "C" int dfusion_truncate_depth(uint16_t* depth, size_t pitch, int cols, int rows, float max_dist, dfStream stream)
 {
-    if (!depth || cols <= 0 || rows <= 0 || !(max_dist >= 0.f) || !(max_dist * 1000.f < 65536.f)) return DF_E_INVALID;
+    if (!depth || cols <= 0 || rows <= 0 || !(max_dist >= 0.f) || !(max_dist * 1000.f < 65536.f) || !df_pitch_ok(pitch, cols, 2)) return DF_E_INVALID;
     hipLaunchKernelGGL(df_truncate_kernel, FE_GRID(cols, rows), dim3(256), 0, (hipStream_t)stream, depth, pitch, cols, rows,
                        (uint16_t)(max_dist * 1000.f));                                   // :83
     DF_LAUNCH_CHECK();
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(256) void df_cloud_to_depth_kernel(const float* __r
 }
 extern "C" int dfusion_cloud_to_depth(const float* cloud, size_t cloud_pitch, uint16_t* depth, size_t depth_pitch, int cols, int rows, dfStream stream)
 {
-    if (!cloud || !depth || cols <= 0 || rows <= 0) return DF_E_INVALID;
+    if (!cloud || !depth || cols <= 0 || rows <= 0 || !df_pitch_ok(cloud_pitch, cols, 16) || !df_pitch_ok(depth_pitch, cols, 2)) return DF_E_INVALID;
     hipLaunchKernelGGL(df_cloud_to_depth_kernel, FE_GRID(cols, rows), dim3(256), 0, (hipStream_t)stream, cloud, cloud_pitch, depth, depth_pitch, cols, rows);
     DF_LAUNCH_CHECK();
     return DF_OK;
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(256) void df_pyramid_kernel(const uint16_t* __restr
 extern "C" int dfusion_depth_pyramid(const uint16_t* src, size_t src_pitch, int src_cols, int src_rows, uint16_t* dst, size_t dst_pitch,
                                      float sigma_depth, dfStream stream)
 {
-    if (!src || !dst || src_cols < 2 || src_rows < 2) return DF_E_INVALID;
+    if (!src || !dst || src_cols < 2 || src_rows < 2 || !df_pitch_ok(src_pitch, src_cols, 2) || !df_pitch_ok(dst_pitch, src_cols / 2, 2)) return DF_E_INVALID;
     sigma_depth *= 1000;                                                                 // :130
     const int dc = src_cols / 2, dr = src_rows / 2;                                      // imgproc.cpp:36
     hipLaunchKernelGGL(df_pyramid_kernel, FE_GRID(dc, dr), dim3(256), 0, (hipStream_t)stream, src, src_pitch, src_cols, src_rows, dst,
@@ -169,6 +170,7 @@ extern "C" int dfusion_compute_normals_mask_depth(uint16_t* depth, size_t depth_
                                                   int rows, const float intr[4], dfStream stream)
 {
     if (!depth || !normals || !intr || cols <= 0 || rows <= 0) return DF_E_INVALID;
+    if (!df_pitch_ok(depth_pitch, cols, 2) || !df_pitch_ok(normals_pitch, cols, 16)) return DF_E_INVALID;
     hipLaunchKernelGGL(df_normals_kernel, FE_GRID(cols, rows), dim3(256), 0, (hipStream_t)stream, depth, depth_pitch, normals, normals_pitch,
                        cols, rows, fe_intr(intr));
     DF_LAUNCH_CHECK();
@@ -199,6 +201,7 @@ extern "C" int dfusion_compute_point_normals(const uint16_t* depth, size_t depth
                                              size_t normals_pitch, int cols, int rows, const float intr[4], dfStream stream)
 {
     if (!depth || !points || !normals || !intr || cols <= 0 || rows <= 0) return DF_E_INVALID;
+    if (!df_pitch_ok(depth_pitch, cols, 2) || !df_pitch_ok(points_pitch, cols, 16) || !df_pitch_ok(normals_pitch, cols, 16)) return DF_E_INVALID;
     hipLaunchKernelGGL(df_point_normals_kernel, FE_GRID(cols, rows), dim3(256), 0, (hipStream_t)stream, depth, depth_pitch, points,
                        points_pitch, normals, normals_pitch, cols, rows, fe_intr(intr));
     DF_LAUNCH_CHECK();
@@ -236,6 +239,8 @@ extern "C" int dfusion_resize_depth_normals(const uint16_t* depth, size_t depth_
                                             size_t normals_out_pitch, dfStream stream)
 {
     if (!depth || !normals || !depth_out || !normals_out || src_cols < 2 || src_rows < 2) return DF_E_INVALID;
+    if (!df_pitch_ok(depth_pitch, src_cols, 2) || !df_pitch_ok(normals_pitch, src_cols, 16) || !df_pitch_ok(depth_out_pitch, src_cols / 2, 2) ||
+        !df_pitch_ok(normals_out_pitch, src_cols / 2, 16)) return DF_E_INVALID;
     const int dc = src_cols / 2, dr = src_rows / 2;
     hipLaunchKernelGGL(df_resize_depth_normals_kernel, FE_GRID(dc, dr), dim3(256), 0, (hipStream_t)stream, depth, depth_pitch, normals,
                        normals_pitch, depth_out, depth_out_pitch, normals_out, normals_out_pitch, dc, dr);
@@ -270,6 +275,8 @@ extern "C" int dfusion_resize_points_normals(const float* points, size_t points_
                                              size_t normals_out_pitch, dfStream stream)
 {
     if (!points || !normals || !points_out || !normals_out || src_cols < 2 || src_rows < 2) return DF_E_INVALID;
+    if (!df_pitch_ok(points_pitch, src_cols, 16) || !df_pitch_ok(normals_pitch, src_cols, 16) || !df_pitch_ok(points_out_pitch, src_cols / 2, 16) ||
+        !df_pitch_ok(normals_out_pitch, src_cols / 2, 16)) return DF_E_INVALID;
     const int dc = src_cols / 2, dr = src_rows / 2;
     hipLaunchKernelGGL(df_resize_points_normals_kernel, FE_GRID(dc, dr), dim3(256), 0, (hipStream_t)stream, points, points_pitch, normals,
                        normals_pitch, points_out, points_out_pitch, normals_out, normals_out_pitch, dc, dr);
@@ -338,6 +345,7 @@ extern "C" int dfusion_render_image_points(const float* points, size_t points_pi
                                            int rows, const float light_pose[3], unsigned char* image, size_t image_pitch, dfStream stream)
 {
     if (!points || !normals || !light_pose || !image || cols <= 0 || rows <= 0) return DF_E_INVALID;
+    if (!df_pitch_ok(points_pitch, cols, 16) || !df_pitch_ok(normals_pitch, cols, 16) || !df_pitch_ok(image_pitch, cols, 4)) return DF_E_INVALID;
     FeIntr I; I.fx = I.fy = 1.f; I.cx = I.cy = 0.f; I.finvx = I.finvy = 1.f;
     hipLaunchKernelGGL((df_render_kernel<false>), FE_GRID(cols, rows), dim3(256), 0, (hipStream_t)stream, (const void*)points, points_pitch, normals,
                        normals_pitch, cols, rows, I, mk3h(light_pose), (uint32_t*)image, image_pitch);
@@ -349,6 +357,7 @@ extern "C" int dfusion_render_image_depth(const uint16_t* depth, size_t depth_pi
                                           dfStream stream)
 {
     if (!depth || !normals || !intr || !light_pose || !image || cols <= 0 || rows <= 0) return DF_E_INVALID;
+    if (!df_pitch_ok(depth_pitch, cols, 2) || !df_pitch_ok(normals_pitch, cols, 16) || !df_pitch_ok(image_pitch, cols, 4)) return DF_E_INVALID;
     hipLaunchKernelGGL((df_render_kernel<true>), FE_GRID(cols, rows), dim3(256), 0, (hipStream_t)stream, (const void*)depth, depth_pitch, normals,
                        normals_pitch, cols, rows, fe_intr(intr), mk3h(light_pose), (uint32_t*)image, image_pitch);
     DF_LAUNCH_CHECK();
@@ -357,7 +366,7 @@ extern "C" int dfusion_render_image_depth(const uint16_t* depth, size_t depth_pi
 extern "C" int dfusion_render_tangent_colors(const float* normals, size_t normals_pitch, int cols, int rows, unsigned char* image,
                                              size_t image_pitch, dfStream stream)
 {
-    if (!normals || !image || cols <= 0 || rows <= 0) return DF_E_INVALID;
+    if (!normals || !image || cols <= 0 || rows <= 0 || !df_pitch_ok(normals_pitch, cols, 16) || !df_pitch_ok(image_pitch, cols, 4)) return DF_E_INVALID;
     hipLaunchKernelGGL(df_tangent_colors_kernel, FE_GRID(cols, rows), dim3(256), 0, (hipStream_t)stream, normals, normals_pitch, cols, rows,
                        (uint32_t*)image, image_pitch);
     DF_LAUNCH_CHECK();
@@ -391,6 +400,7 @@ extern "C" int dfusion_transform_points(const float* in, size_t in_pitch, int in
                                         int cols, int rows, const float aff[12], dfStream stream)
 {
     if (!in || !out || in == out || cols <= 0 || rows <= 0 || in_stride < 3 || out_stride < 3 || out_stride > 4) return DF_E_INVALID;
+    if (!df_pitch_ok(in_pitch, cols, 4 * (size_t)in_stride) || !df_pitch_ok(out_pitch, cols, 4 * (size_t)out_stride)) return DF_E_INVALID;
     DfAff A;
     memset(&A, 0, sizeof(A));
     if (aff) A = df_aff(aff);
@@ -552,6 +562,9 @@ static int df_icp_launch(DfIcpArgs& A, bool depth, const float aff[12], const fl
                          float* workspace, float* sums, int* accepted, hipStream_t st)
 {
     if (!aff || !intr || !workspace || !sums || A.cols <= 0 || A.rows <= 0) return DF_E_INVALID;
+    const size_t esz = depth ? 2 : 16;
+    if (!df_pitch_ok(depth ? A.dcpitch : A.vcpitch, A.cols, esz) || !df_pitch_ok(depth ? A.dppitch : A.vppitch, A.cols, esz) ||
+        !df_pitch_ok(A.ncpitch, A.cols, 16) || !df_pitch_ok(A.nppitch, A.cols, 16)) return DF_E_INVALID;
     A.aff = df_aff(aff); A.I = fe_intr(intr); A.min_cosine = min_cosine; A.dist2_thres = dist2_thres;
     const dim3 grid((A.cols + 31) / 32, (A.rows + 7) / 8);                              // :406-407
     A.partial = workspace; A.partials = (int)(grid.x * grid.y); A.accepted = accepted;
@@ -686,6 +699,12 @@ extern "C" int dfusion_icp_estimate(const DfIcpLevel* levels, int n_levels, int 
                                     float min_cosine, float* workspace, float* state, dfStream stream)
 {
     if (!levels || n_levels <= 0 || n_levels > 8 || !intr || !workspace || !state) return DF_E_INVALID;
+    const size_t esz = depth_variant ? 2 : 16;
+    for (int level = 0; level < n_levels; ++level) {                                     // every level's pitches, before anything is enqueued
+        const DfIcpLevel& L = levels[level];
+        if (L.iters > 0 && (!df_pitch_ok(L.curr_pitch, L.cols, esz) || !df_pitch_ok(L.prev_pitch, L.cols, esz) ||
+                            !df_pitch_ok(L.ncurr_pitch, L.cols, 16) || !df_pitch_ok(L.nprev_pitch, L.cols, 16))) return DF_E_INVALID;
+    }
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(df_icp_state_init_kernel, dim3(1), dim3(64), 0, st, state);
     DF_LAUNCH_CHECK();

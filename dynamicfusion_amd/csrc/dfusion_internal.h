@@ -34,6 +34,8 @@ static inline bool df_volume_valid(const DfVolume& v)
            v.voxel_size[0] > 0 && v.voxel_size[1] > 0 && v.voxel_size[2] > 0 && v.trunc_dist > 0;
 }
 static inline DfAff df_aff(const float a[12]) { DfAff r; memcpy(r.R, a, 36); memcpy(r.t, a + 9, 12); return r; }
+// an image row of `cols` pixels of `bpp` bytes fits its byte pitch (include/dfusion.h Conventions); cols <= 0 never fits
+static inline bool df_pitch_ok(size_t pitch, int cols, size_t bpp) { return cols > 0 && pitch >= (size_t)cols * bpp; }
 
 // Device-side view of the warp field + brick index (passed to kernels by value).
 struct DfWarpView {

@@ -395,7 +395,7 @@ extern "C" int dfusion_raycast_points(DfVolume v, const DfSlab* slab, const floa
                                       const float reproj[4], float* points, size_t ppitch, float* normals, size_t npitch,
                                       int cols, int rows, float step_factor, float delta_factor, uint32_t* keys, dfStream stream)
 {
-    if (!points || !normals) return DF_E_INVALID;
+    if (!points || !normals || !df_pitch_ok(ppitch, cols, 16) || !df_pitch_ok(npitch, cols, 16)) return DF_E_INVALID;
     DfRayArgs a;
     int rc = df_raycast_setup(a, v, slab, cam2vol, Rinv, reproj, cols, rows, step_factor, delta_factor);
     if (rc) return rc;
@@ -419,7 +419,7 @@ extern "C" int dfusion_raycast_depth(DfVolume v, const DfSlab* slab, const float
                                      const float reproj[4], uint16_t* depth, size_t dpitch, float* normals, size_t npitch,
                                      int cols, int rows, float step_factor, float delta_factor, dfStream stream)
 {
-    if (!depth || !normals) return DF_E_INVALID;
+    if (!depth || !normals || !df_pitch_ok(dpitch, cols, 2) || !df_pitch_ok(npitch, cols, 16)) return DF_E_INVALID;
     DfRayArgs a;
     int rc = df_raycast_setup(a, v, slab, cam2vol, Rinv, reproj, cols, rows, step_factor, delta_factor);
     if (rc) return rc;
@@ -457,6 +457,7 @@ extern "C" int dfusion_raycast_shade(DfVolume v, const DfSlab* slab, const float
                                      dfStream stream)
 {
     if (!merged_keys || !normals) return DF_E_INVALID;                  // points nullable: see dfusion_raycast_points_of_keys
+    if (!df_pitch_ok(npitch, cols, 16) || (points && !df_pitch_ok(ppitch, cols, 16))) return DF_E_INVALID;
     DfRayArgs a;
     int rc = df_raycast_setup(a, v, slab, cam2vol, Rinv, reproj, cols, rows, 0.75f, delta_factor);
     if (rc) return rc;
@@ -478,7 +479,7 @@ extern "C" int dfusion_raycast_points_of_keys_rows(const float cam2vol[12], cons
                                                    size_t ppitch, int cols, int image_rows, int row0, int rows, dfStream stream)
 {
     if (!cam2vol || !Rinv || !reproj || !merged_keys || !normals || !points || cols <= 0 || image_rows <= 0) return DF_E_INVALID;
-    if (row0 < 0 || rows < 0 || row0 + rows > image_rows) return DF_E_INVALID;
+    if (row0 < 0 || rows < 0 || row0 + rows > image_rows || !df_pitch_ok(npitch, cols, 16) || !df_pitch_ok(ppitch, cols, 16)) return DF_E_INVALID;
     if (rows == 0) return DF_OK;
     DfRayArgs a;
     memset(&a, 0, sizeof(a));

@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256) void df_compute_dists_kernel(const uint16_t* _
 extern "C" int dfusion_compute_dists(const uint16_t* depth, size_t depth_pitch, uint16_t* dists, size_t dists_pitch,
                                      int cols, int rows, const float intr[4], dfStream stream)
 {
-    if (!depth || !dists || !intr || cols <= 0 || rows <= 0) return DF_E_INVALID;
+    if (!depth || !dists || !intr || cols <= 0 || rows <= 0 || !df_pitch_ok(depth_pitch, cols, 2) || !df_pitch_ok(dists_pitch, cols, 2)) return DF_E_INVALID;
     dim3 grid((cols + 63) / 64, (rows + 3) / 4);
     hipLaunchKernelGGL(df_compute_dists_kernel, grid, dim3(256), 0, (hipStream_t)stream, depth, depth_pitch, dists,
                        dists_pitch, cols, rows, 1.f / intr[0], 1.f / intr[1], intr[2], intr[3]);   // imgproc.cu:292
@@ -185,7 +185,7 @@ extern "C" int dfusion_project_and_remove(const uint16_t* dists_in, size_t in_pi
                                           float* ro, unsigned long long* n_inside, dfStream stream)
 {
     if (!dists_in || !points || !proj || cols <= 0 || rows <= 0) return DF_E_INVALID;
-    if (dists_out == dists_in) return DF_E_INVALID;
+    if (dists_out == dists_in || !df_pitch_ok(in_pitch, cols, 2) || (dists_out && !df_pitch_ok(out_pitch, cols, 2))) return DF_E_INVALID;
     if (n == 0) return DF_OK;
     const float P = proj[0] * proj[1];
     const float dinv = 1.f / P;
@@ -805,7 +805,7 @@ extern "C" int dfusion_integrate_ex(const uint16_t* dists, size_t pitch, int col
 {
     const bool no_depth_cull = (flags & DF_RIGID_NO_DEPTH_CULL) != 0, no_fast_forms = (flags & DF_RIGID_NO_SHORT_FORMS) != 0;
     const bool keep_all = (flags & DF_RIGID_KEEP_ALL) != 0, no_sat = (flags & DF_RIGID_NO_SAT) != 0;
-    if (!dists || !vol2cam || !proj || cols <= 0 || rows <= 0 || !df_volume_valid(v)) return DF_E_INVALID;
+    if (!dists || !vol2cam || !proj || cols <= 0 || rows <= 0 || !df_pitch_ok(pitch, cols, 2) || !df_volume_valid(v)) return DF_E_INVALID;
     DfSlab s = df_slab_or_full(v, slab);
     if (!df_slab_valid(v, s)) return DF_E_INVALID;
     if (s.z_own_n == 0) return DF_OK;

@@ -2601,7 +2601,7 @@ static int df_integrate_warped_impl(const uint16_t* dists, size_t pitch, int col
                                     const float vol2world[12], const float world2cam[12], const float proj[4],
                                     DfWarpField* wf, int k, unsigned flags, unsigned long long* n_updated, dfStream stream, int mode)
 {
-    if (!dists || !vol2world || !world2cam || !proj || !wf || cols <= 0 || rows <= 0 || !df_volume_valid(v)) return DF_E_INVALID;
+    if (!dists || !vol2world || !world2cam || !proj || !wf || cols <= 0 || rows <= 0 || !df_pitch_ok(pitch, cols, 2) || !df_volume_valid(v)) return DF_E_INVALID;
     if (k < 1 || k > 8 || wf->M < k) return DF_E_INVALID;
     DfSlab s = df_slab_or_full(v, slab);
     if (!df_slab_valid(v, s)) return DF_E_INVALID;

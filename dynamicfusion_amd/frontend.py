@@ -11,7 +11,7 @@ import torch
 
 from . import capi
 from .synth import aff12
-from .tsdf_volume import F32, Intr, _ptr, _stream
+from .tsdf_volume import BGRA, F4, F32, U16, Intr, _image, _stream
 
 
 def intr_level(intr, level):
@@ -28,74 +28,94 @@ def _new_image4(rows, cols, device):
     return torch.empty((rows, cols, 4), dtype=torch.float32, device=device)
 
 
+def _sized(t, kind, rows, cols):
+    """(ptr, pitch) of an output / second input image that must be rows x cols."""
+    p, pitch, r, c = _image(t, kind)
+    if (r, c) != (rows, cols):
+        raise ValueError("image is %dx%d, expected %dx%d" % (r, c, rows, cols))
+    return p, pitch
+
+
 def depthBilateralFilter(depth, kernel_size, sigma_spatial, sigma_depth, out=None):
-    rows, cols = depth.shape
+    sp, spitch, rows, cols = _image(depth, U16)
     if out is None:
         out = _new_depth(rows, cols, depth.device)
-    capi.check(capi.lib().dfusion_bilateral_filter(_ptr(depth), cols * 2, _ptr(out), cols * 2, cols, rows, int(kernel_size),
+    dp, dpitch = _sized(out, U16, rows, cols)
+    capi.check(capi.lib().dfusion_bilateral_filter(sp, spitch, dp, dpitch, cols, rows, int(kernel_size),
                                                    float(sigma_spatial), float(sigma_depth), _stream()), "dfusion_bilateral_filter")
     return out
 
 
 def depthTruncation(depth, threshold):
-    rows, cols = depth.shape
-    capi.check(capi.lib().dfusion_truncate_depth(_ptr(depth), cols * 2, cols, rows, float(threshold), _stream()), "dfusion_truncate_depth")
+    dp, pitch, rows, cols = _image(depth, U16)
+    capi.check(capi.lib().dfusion_truncate_depth(dp, pitch, cols, rows, float(threshold), _stream()), "dfusion_truncate_depth")
     return depth
 
 
 def cloudToDepth(cloud, out=None):
     """cuda::cloudToDepth (imgproc.cpp:98-103): depth mm = points.z * 1000 (a NaN point -- a ray-cast miss -- gives 0)."""
-    rows, cols = cloud.shape[:2]
+    cp, cpitch, rows, cols = _image(cloud, F4)
     if out is None:
         out = torch.empty((rows, cols), dtype=torch.int16, device=cloud.device)
-    capi.check(capi.lib().dfusion_cloud_to_depth(_ptr(cloud), cols * 16, _ptr(out), cols * 2, cols, rows, _stream()), "dfusion_cloud_to_depth")
+    dp, dpitch = _sized(out, U16, rows, cols)
+    capi.check(capi.lib().dfusion_cloud_to_depth(cp, cpitch, dp, dpitch, cols, rows, _stream()), "dfusion_cloud_to_depth")
     return out
 
 
 def depthBuildPyramid(depth, sigma_depth, out=None):
-    rows, cols = depth.shape
+    sp, spitch, rows, cols = _image(depth, U16)
     if out is None:
         out = _new_depth(rows // 2, cols // 2, depth.device)
-    capi.check(capi.lib().dfusion_depth_pyramid(_ptr(depth), cols * 2, cols, rows, _ptr(out), (cols // 2) * 2, float(sigma_depth),
+    dp, dpitch = _sized(out, U16, rows // 2, cols // 2)
+    capi.check(capi.lib().dfusion_depth_pyramid(sp, spitch, cols, rows, dp, dpitch, float(sigma_depth),
                                                 _stream()), "dfusion_depth_pyramid")
     return out
 
 
 def computeNormalsAndMaskDepth(intr, depth, normals=None):
-    rows, cols = depth.shape
+    dp, dpitch, rows, cols = _image(depth, U16)
     if normals is None:
         normals = _new_image4(rows, cols, depth.device)
-    capi.check(capi.lib().dfusion_compute_normals_mask_depth(_ptr(depth), cols * 2, _ptr(normals), cols * 16, cols, rows, intr.as_proj(),
+    np_, npitch = _sized(normals, F4, rows, cols)
+    capi.check(capi.lib().dfusion_compute_normals_mask_depth(dp, dpitch, np_, npitch, cols, rows, intr.as_proj(),
                                                              _stream()), "dfusion_compute_normals_mask_depth")
     return normals
 
 
 def computePointNormals(intr, depth, points=None, normals=None):
-    rows, cols = depth.shape
+    dp, dpitch, rows, cols = _image(depth, U16)
     if points is None:
         points = _new_image4(rows, cols, depth.device)
     if normals is None:
         normals = _new_image4(rows, cols, depth.device)
-    capi.check(capi.lib().dfusion_compute_point_normals(_ptr(depth), cols * 2, _ptr(points), cols * 16, _ptr(normals), cols * 16, cols,
+    pp, ppitch = _sized(points, F4, rows, cols)
+    np_, npitch = _sized(normals, F4, rows, cols)
+    capi.check(capi.lib().dfusion_compute_point_normals(dp, dpitch, pp, ppitch, np_, npitch, cols,
                                                         rows, intr.as_proj(), _stream()), "dfusion_compute_point_normals")
     return points, normals
 
 
-def resizeDepthNormals(depth, normals):
-    rows, cols = depth.shape
-    d = _new_depth(rows // 2, cols // 2, depth.device)
-    n = _new_image4(rows // 2, cols // 2, depth.device)
-    capi.check(capi.lib().dfusion_resize_depth_normals(_ptr(depth), cols * 2, _ptr(normals), cols * 16, cols, rows, _ptr(d),
-                                                       (cols // 2) * 2, _ptr(n), (cols // 2) * 16, _stream()), "dfusion_resize_depth_normals")
+def resizeDepthNormals(depth, normals, d=None, n=None):
+    dp, dpitch, rows, cols = _image(depth, U16)
+    np_, npitch = _sized(normals, F4, rows, cols)
+    d = _new_depth(rows // 2, cols // 2, depth.device) if d is None else d
+    n = _new_image4(rows // 2, cols // 2, depth.device) if n is None else n
+    odp, odpitch = _sized(d, U16, rows // 2, cols // 2)
+    onp, onpitch = _sized(n, F4, rows // 2, cols // 2)
+    capi.check(capi.lib().dfusion_resize_depth_normals(dp, dpitch, np_, npitch, cols, rows, odp,
+                                                       odpitch, onp, onpitch, _stream()), "dfusion_resize_depth_normals")
     return d, n
 
 
-def resizePointsNormals(points, normals):
-    rows, cols = points.shape[:2]
-    p = _new_image4(rows // 2, cols // 2, points.device)
-    n = _new_image4(rows // 2, cols // 2, points.device)
-    capi.check(capi.lib().dfusion_resize_points_normals(_ptr(points), cols * 16, _ptr(normals), cols * 16, cols, rows, _ptr(p),
-                                                        (cols // 2) * 16, _ptr(n), (cols // 2) * 16, _stream()),
+def resizePointsNormals(points, normals, p=None, n=None):
+    pp, ppitch, rows, cols = _image(points, F4)
+    np_, npitch = _sized(normals, F4, rows, cols)
+    p = _new_image4(rows // 2, cols // 2, points.device) if p is None else p
+    n = _new_image4(rows // 2, cols // 2, points.device) if n is None else n
+    opp, oppitch = _sized(p, F4, rows // 2, cols // 2)
+    onp, onpitch = _sized(n, F4, rows // 2, cols // 2)
+    capi.check(capi.lib().dfusion_resize_points_normals(pp, ppitch, np_, npitch, cols, rows, opp,
+                                                        oppitch, onp, onpitch, _stream()),
                "dfusion_resize_points_normals")
     return p, n
 
@@ -103,25 +123,29 @@ def resizePointsNormals(points, normals):
 def renderImage(src, normals, intr, light_pose, image=None):
     """kfusion::cuda::renderImage (imgproc.cpp:152-186): Phong view of a points image (float32 [rows, cols, 4]) or a depth image
     (int16 [rows, cols]) with its normals; image: uint8 [rows, cols, 4] BGRA (device)."""
-    rows, cols = normals.shape[:2]
+    np_, npitch, rows, cols = _image(normals, F4)
     if image is None:
         image = torch.empty((rows, cols, 4), dtype=torch.uint8, device=normals.device)
+    ip, ipitch = _sized(image, BGRA, rows, cols)
     light = capi.floats(light_pose)
     if src.dtype == torch.float32:
-        capi.check(capi.lib().dfusion_render_image_points(_ptr(src), cols * 16, _ptr(normals), cols * 16, cols, rows, light, _ptr(image),
-                                                          image.stride(0), _stream()), "dfusion_render_image_points")
+        sp, spitch = _sized(src, F4, rows, cols)
+        capi.check(capi.lib().dfusion_render_image_points(sp, spitch, np_, npitch, cols, rows, light, ip,
+                                                          ipitch, _stream()), "dfusion_render_image_points")
     else:
-        capi.check(capi.lib().dfusion_render_image_depth(_ptr(src), cols * 2, _ptr(normals), cols * 16, cols, rows, intr.as_proj(), light,
-                                                         _ptr(image), image.stride(0), _stream()), "dfusion_render_image_depth")
+        sp, spitch = _sized(src, U16, rows, cols)
+        capi.check(capi.lib().dfusion_render_image_depth(sp, spitch, np_, npitch, cols, rows, intr.as_proj(), light,
+                                                         ip, ipitch, _stream()), "dfusion_render_image_depth")
     return image
 
 
 def renderTangentColors(normals, image=None):
     """kfusion::cuda::renderTangentColors (imgproc.cpp:193-201)."""
-    rows, cols = normals.shape[:2]
+    np_, npitch, rows, cols = _image(normals, F4)
     if image is None:
         image = torch.empty((rows, cols, 4), dtype=torch.uint8, device=normals.device)
-    capi.check(capi.lib().dfusion_render_tangent_colors(_ptr(normals), cols * 16, cols, rows, _ptr(image), image.stride(0), _stream()),
+    ip, ipitch = _sized(image, BGRA, rows, cols)
+    capi.check(capi.lib().dfusion_render_tangent_colors(np_, npitch, cols, rows, ip, ipitch, _stream()),
                "dfusion_render_tangent_colors")
     return image
 
@@ -196,7 +220,11 @@ class ProjectiveICP:
 
     def sums(self, level_intr, curr, ncurr, prev, nprev, affine, depth_variant=False):
         """One ComputeIcpHelper::operator() call: returns the 27 sums (numpy f32)."""
-        rows, cols = nprev.shape[:2]
+        kind = U16 if depth_variant else F4
+        np_, nppitch, rows, cols = _image(nprev, F4)
+        cp, cpitch = _sized(curr, kind, rows, cols)
+        ncp, ncpitch = _sized(ncurr, F4, rows, cols)
+        pp, ppitch = _sized(prev, kind, rows, cols)
         need = capi.lib().dfusion_icp_workspace_floats(cols, rows)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 27 * 1200 + 27), dtype=torch.float32, device=nprev.device)
@@ -205,14 +233,10 @@ class ProjectiveICP:
         acc = torch.zeros(1, dtype=torch.int32, device=nprev.device)
         d2, mc = self.thresholds()
         L = capi.lib()
-        if depth_variant:
-            capi.check(L.dfusion_icp_sums_depth(_ptr(curr), cols * 2, _ptr(ncurr), cols * 16, _ptr(prev), cols * 2, _ptr(nprev), cols * 16,
-                                                cols, rows, capi.floats(aff12(affine)), level_intr.as_proj(), d2, mc, _ptr(self._ws),
-                                                _ptr(self._sums), _ptr(acc), _stream()), "dfusion_icp_sums_depth")
-        else:
-            capi.check(L.dfusion_icp_sums_points(_ptr(curr), cols * 16, _ptr(ncurr), cols * 16, _ptr(prev), cols * 16, _ptr(nprev),
-                                                 cols * 16, cols, rows, capi.floats(aff12(affine)), level_intr.as_proj(), d2, mc,
-                                                 _ptr(self._ws), _ptr(self._sums), _ptr(acc), _stream()), "dfusion_icp_sums_points")
+        fn = L.dfusion_icp_sums_depth if depth_variant else L.dfusion_icp_sums_points
+        capi.check(fn(cp, cpitch, ncp, ncpitch, pp, ppitch, np_, nppitch, cols, rows, capi.floats(aff12(affine)), level_intr.as_proj(), d2, mc,
+                      self._ws.data_ptr(), self._sums.data_ptr(), acc.data_ptr(), _stream()),
+                   "dfusion_icp_sums_depth" if depth_variant else "dfusion_icp_sums_points")
         out = self._sums.cpu().numpy().copy()                      # cudaStreamSynchronize + pinned copy in the reference (:45)
         self.last_accepted = int(acc.item())
         return out
@@ -222,11 +246,13 @@ class ProjectiveICP:
         end.  Returns (ok, affine 4x4 f32 curr -> prev)."""
         n = self.getUsedLevelsNum()
         levels = (capi.DfIcpLevel * n)()
-        esz = 2 if depth_variant else 16
+        kind = U16 if depth_variant else F4
         for l in range(n):
-            rows, cols = nprev_pyr[l].shape[:2]
-            levels[l] = capi.DfIcpLevel(curr_pyr[l].data_ptr(), cols * esz, ncurr_pyr[l].data_ptr(), cols * 16, prev_pyr[l].data_ptr(), cols * esz,
-                                        nprev_pyr[l].data_ptr(), cols * 16, cols, rows, self.iters_[l])
+            np_, nppitch, rows, cols = _image(nprev_pyr[l], F4)
+            cp, cpitch = _sized(curr_pyr[l], kind, rows, cols)
+            ncp, ncpitch = _sized(ncurr_pyr[l], F4, rows, cols)
+            pp, ppitch = _sized(prev_pyr[l], kind, rows, cols)
+            levels[l] = capi.DfIcpLevel(cp.value, cpitch, ncp.value, ncpitch, pp.value, ppitch, np_.value, nppitch, cols, rows, self.iters_[l])
         rows0, cols0 = nprev_pyr[0].shape[:2]
         need = capi.lib().dfusion_icp_workspace_floats(cols0, rows0) + 27
         dev = nprev_pyr[0].device
@@ -234,7 +260,7 @@ class ProjectiveICP:
             self._ws = torch.empty(max(need, 27 * 1200 + 27), dtype=torch.float32, device=dev)
         state = torch.empty(13, dtype=torch.float32, device=dev)
         d2, mc = self.thresholds()
-        capi.check(capi.lib().dfusion_icp_estimate(levels, n, 1 if depth_variant else 0, intr.as_proj(), d2, mc, _ptr(self._ws), _ptr(state),
+        capi.check(capi.lib().dfusion_icp_estimate(levels, n, 1 if depth_variant else 0, intr.as_proj(), d2, mc, self._ws.data_ptr(), state.data_ptr(),
                                                    _stream()), "dfusion_icp_estimate")
         st = state.cpu().numpy()
         affine = np.eye(4, dtype=F32)

@@ -26,6 +26,43 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+# pixel layouts of the C-ABI's images (include/dfusion.h): (dtype, channels, element bytes, alignment of base and pitch)
+U16 = (torch.int16, None, 2, 2)     # depth / dists: u16 bits [rows, cols]
+F4 = (torch.float32, 4, 4, 16)      # points / normals: float4 [rows, cols, 4]
+BGRA = (torch.uint8, 4, 1, 4)       # rendered images [rows, cols, 4] (stored as 32-bit words)
+
+
+def _image(t, kind, check_device=True):
+    """A pitched C-ABI image from a tensor -> (ptr, pitch_bytes, rows, cols).  Rows may be strided (row bands, column windows of a wider
+    image): the pitch is stride(0) * element size.  Raises ValueError for what the ABI cannot express -- wrong dtype / shape, a
+    non-dense pixel row, a negative or overlapping row stride, a float4 image not 16-byte aligned (BGRA: 4-byte), a host tensor.
+    Reads strides and the pointer only: nothing synchronises (and it is cheap: it runs for every image of every frame)."""
+    dtype, ch, esz, align = kind
+    shape, st = t.shape, t.stride()
+    if t.dtype != dtype or len(shape) != (2 if ch is None else 3) or (ch is not None and shape[2] != ch):
+        raise ValueError("image %s %s, expected %s [rows, cols%s]" % (t.dtype, tuple(shape), dtype, "" if ch is None else ", %d" % ch))
+    if check_device and not t.is_cuda:
+        raise ValueError("image is not on a CUDA device")
+    rows, cols = shape[0], shape[1]
+    row = cols * (ch or 1)                                          # elements per row
+    if st[-1] != 1 or (ch is not None and cols > 1 and st[1] != ch):
+        raise ValueError("image pixels are not dense within a row (strides %s)" % (st,))
+    if rows > 1 and st[0] < row:
+        raise ValueError("image row stride %d is negative or shorter than a row (%d elements)" % (st[0], row))
+    pitch = (st[0] if rows > 1 else row) * esz
+    ptr = t.data_ptr()
+    if ptr % align or pitch % align:
+        raise ValueError("image base / pitch not %d-byte aligned" % align)
+    return C.c_void_p(ptr), pitch, rows, cols
+
+
+def _flat(t):
+    """A flat device list (points, queries): must be contiguous, the ABI has no stride for it."""
+    if not t.is_contiguous():
+        raise ValueError("point list must be contiguous (shape %s, strides %s)" % (tuple(t.shape), t.stride()))
+    return C.c_void_p(t.data_ptr())
+
+
 class Intr:
     """kfusion::Intr (kfusion/include/kfusion/types.hpp:20-27)."""
 
@@ -50,10 +87,13 @@ def download_u16(t):
 
 def compute_dists(depth, intr, dists=None):
     """kfusion::cuda::computeDists (kfusion/src/imgproc.cpp:87-91)."""
-    rows, cols = depth.shape
+    dp, dpitch, rows, cols = _image(depth, U16)
     if dists is None:
-        dists = torch.empty_like(depth)
-    capi.check(capi.lib().dfusion_compute_dists(_ptr(depth), cols * 2, _ptr(dists), cols * 2, cols, rows,
+        dists = torch.empty((rows, cols), dtype=torch.int16, device=depth.device)
+    op, opitch, orows, ocols = _image(dists, U16)
+    if (orows, ocols) != (rows, cols):
+        raise ValueError("dists %s does not match depth %s" % ((orows, ocols), (rows, cols)))
+    capi.check(capi.lib().dfusion_compute_dists(dp, dpitch, op, opitch, cols, rows,
                                                 intr.as_proj(), _stream()), "dfusion_compute_dists")
     return dists
 
@@ -183,14 +223,14 @@ class TsdfVolume:
         """flags: capi.DF_RIGID_* validation switches of THIS call (0 = the product path); n_swept: device int64[1], += the voxels
         the sweep put through the projective sample."""
         vol2cam = affine_mul(affine_inv(np.asarray(camera_pose, F32)), self.pose_)
-        rows, cols = dists.shape
+        dp, pitch, rows, cols = _image(dists, U16)
         if flags == 0 and n_swept is None:
-            capi.check(capi.lib().dfusion_integrate(_ptr(dists), cols * 2, cols, rows, self.c_volume(), self.c_slab(),
+            capi.check(capi.lib().dfusion_integrate(dp, pitch, cols, rows, self.c_volume(), self.c_slab(),
                                                     capi.floats(aff12(vol2cam)), intr.as_proj(),
                                                     _ptr(n_updated) if n_updated is not None else None, _stream()),
                        "dfusion_integrate")
         else:
-            capi.check(capi.lib().dfusion_integrate_ex(_ptr(dists), cols * 2, cols, rows, self.c_volume(), self.c_slab(),
+            capi.check(capi.lib().dfusion_integrate_ex(dp, pitch, cols, rows, self.c_volume(), self.c_slab(),
                                                        capi.floats(aff12(vol2cam)), intr.as_proj(), int(flags),
                                                        _ptr(n_updated) if n_updated is not None else None,
                                                        _ptr(n_swept) if n_swept is not None else None, _stream()),
@@ -210,9 +250,9 @@ class TsdfVolume:
         k = warp_field.k if k is None else k
         world2cam = affine_mul(affine_inv(np.asarray(camera_pose, F32)), warp_field.warp_to_live_)
         warp_field.ensure_index(self, k)
-        rows, cols = dists.shape
+        dp, pitch, rows, cols = _image(dists, U16)
         capi.check(capi.lib().dfusion_integrate_warped(
-            _ptr(dists), cols * 2, cols, rows, self.c_volume(), self.c_slab(), capi.floats(aff12(self.pose_)),
+            dp, pitch, cols, rows, self.c_volume(), self.c_slab(), capi.floats(aff12(self.pose_)),
             capi.floats(aff12(world2cam)), intr.as_proj(), warp_field.handle, k,
             (0 if cull else capi.DF_WARP_NO_CULL) | (0 if use_table else capi.DF_WARP_NO_TABLE) |
             (0 if use_weights else capi.DF_WARP_NO_WEIGHT_TABLE) | (0 if use_lds else capi.DF_WARP_NO_LDS) |
@@ -230,9 +270,9 @@ class TsdfVolume:
         k = warp_field.k if k is None else k
         world2cam = affine_mul(affine_inv(np.asarray(camera_pose, F32)), warp_field.warp_to_live_)
         warp_field.ensure_index(self, k)
-        rows, cols = dists.shape
+        dp, pitch, rows, cols = _image(dists, U16)
         capi.check(capi.lib().dfusion_integrate_warped_prepare(
-            _ptr(dists), cols * 2, cols, rows, self.c_volume(), self.c_slab(), capi.floats(aff12(self.pose_)),
+            dp, pitch, cols, rows, self.c_volume(), self.c_slab(), capi.floats(aff12(self.pose_)),
             capi.floats(aff12(world2cam)), intr.as_proj(), warp_field.handle, k,
             (capi.DF_WARP_STEADY_PREFETCH if prefetch == "steady" else 0 if prefetch else capi.DF_WARP_NO_PREFETCH) |
             (0 if codes else capi.DF_WARP_NO_CODES) |
@@ -246,6 +286,13 @@ class TsdfVolume:
         if sync:
             torch.cuda.current_stream().synchronize()
 
+    @staticmethod
+    def _same_size(img, rows, cols):
+        """(ptr, pitch) of an _image() result that must be rows x cols."""
+        if img[2:] != (rows, cols):
+            raise ValueError("image is %dx%d, expected %dx%d" % (img[2], img[3], rows, cols))
+        return img[0], img[1]
+
     def _raycast_args(self, camera_pose):
         cam2vol = affine_mul(affine_inv(self.pose_), np.asarray(camera_pose, F32))      # tsdf_volume.cpp:162
         Rinv = np.linalg.inv(cam2vol[:3, :3].astype(np.float64)).astype(F32)            # :165 inv(DECOMP_SVD)
@@ -255,17 +302,19 @@ class TsdfVolume:
     # it is a 16-bit [rows, cols] image
     def raycast(self, camera_pose, intr, points, normals, keys=None):
         aff, Rinv = self._raycast_args(camera_pose)
-        rows, cols = normals.shape[0], normals.shape[1]
+        np_, npitch, rows, cols = _image(normals, F4)
         L = capi.lib()
         if points.dtype == torch.float32:
-            capi.check(L.dfusion_raycast_points(self.c_volume(), self.c_slab(), aff, Rinv, intr.as_reproj(), _ptr(points),
-                                                cols * 16, _ptr(normals), cols * 16, cols, rows,
+            pp, ppitch = self._same_size(_image(points, F4), rows, cols)
+            capi.check(L.dfusion_raycast_points(self.c_volume(), self.c_slab(), aff, Rinv, intr.as_reproj(), pp,
+                                                ppitch, np_, npitch, cols, rows,
                                                 self.raycast_step_factor_, self.gradient_delta_factor_,
-                                                _ptr(keys) if keys is not None else None, _stream()),
+                                                _flat(keys) if keys is not None else None, _stream()),
                        "dfusion_raycast_points")
         else:
-            capi.check(L.dfusion_raycast_depth(self.c_volume(), self.c_slab(), aff, Rinv, intr.as_reproj(), _ptr(points),
-                                               cols * 2, _ptr(normals), cols * 16, cols, rows,
+            dp, dpitch = self._same_size(_image(points, U16), rows, cols)
+            capi.check(L.dfusion_raycast_depth(self.c_volume(), self.c_slab(), aff, Rinv, intr.as_reproj(), dp,
+                                               dpitch, np_, npitch, cols, rows,
                                                self.raycast_step_factor_, self.gradient_delta_factor_, _stream()),
                        "dfusion_raycast_depth")
 
@@ -276,7 +325,7 @@ class TsdfVolume:
         aff, _ = self._raycast_args(camera_pose)
         rows, cols = keys64.shape
         capi.check(capi.lib().dfusion_raycast_march(self.c_volume(), self.c_slab(), aff, intr.as_reproj(), cols, rows,
-                                                    self.raycast_step_factor_, int(rank), _ptr(keys64), _stream()),
+                                                    self.raycast_step_factor_, int(rank), _flat(keys64), _stream()),
                    "dfusion_raycast_march")
         return keys64
 
@@ -284,9 +333,11 @@ class TsdfVolume:
         """points may be None: only the normals cross GPUs, the points follow from the merged keys (raycast_points_of_keys)."""
         aff, Rinv = self._raycast_args(camera_pose)
         rows, cols = merged_keys64.shape
+        np_, npitch = self._same_size(_image(normals, F4), rows, cols)
+        pp, ppitch = self._same_size(_image(points, F4), rows, cols) if points is not None else (None, npitch)
         capi.check(capi.lib().dfusion_raycast_shade(self.c_volume(), self.c_slab(), aff, Rinv, intr.as_reproj(),
-                                                    _ptr(merged_keys64), _ptr(points) if points is not None else None, cols * 16,
-                                                    _ptr(normals), cols * 16, cols, rows, self.gradient_delta_factor_,
+                                                    _flat(merged_keys64), pp, ppitch,
+                                                    np_, npitch, cols, rows, self.gradient_delta_factor_,
                                                     _stream()), "dfusion_raycast_shade")
         return points, normals
 
@@ -297,8 +348,10 @@ class TsdfVolume:
         aff, Rinv = self._raycast_args(camera_pose)
         rows, cols = merged_keys64.shape
         nrows = rows - row0 if nrows is None else nrows
-        capi.check(capi.lib().dfusion_raycast_points_of_keys_rows(aff, Rinv, intr.as_reproj(), _ptr(merged_keys64), _ptr(normals), cols * 16,
-                                                                  _ptr(points), cols * 16, cols, rows, int(row0), int(nrows), _stream()),
+        np_, npitch = self._same_size(_image(normals, F4), nrows, cols)
+        pp, ppitch = self._same_size(_image(points, F4), nrows, cols)
+        capi.check(capi.lib().dfusion_raycast_points_of_keys_rows(aff, Rinv, intr.as_reproj(), _flat(merged_keys64), np_, npitch,
+                                                                  pp, ppitch, cols, rows, int(row0), int(nrows), _stream()),
                    "dfusion_raycast_points_of_keys_rows")
         return points
 
@@ -337,10 +390,11 @@ class TsdfVolume:
         pts = torch.zeros((n, 4), dtype=torch.float32, device=self.device)
         pts[:, :3] = warped[:, :3]
         ro = torch.empty(n, dtype=torch.float32, device=self.device)
-        snapshot = dists.clone()
-        rows, cols = dists.shape
-        capi.check(capi.lib().dfusion_project_and_remove(_ptr(snapshot), cols * 2, _ptr(dists), cols * 2, cols, rows,
-                                                         _ptr(pts), n, intr.as_proj(), _ptr(ro), None, _stream()),
+        op, opitch, rows, cols = _image(dists, U16)
+        snapshot = dists.clone(memory_format=torch.contiguous_format)
+        ip, ipitch, _, _ = _image(snapshot, U16)
+        capi.check(capi.lib().dfusion_project_and_remove(ip, ipitch, op, opitch, cols, rows,
+                                                         _flat(pts), n, intr.as_proj(), _ptr(ro), None, _stream()),
                    "dfusion_project_and_remove")
         return (ro, pts) if return_points else ro
 

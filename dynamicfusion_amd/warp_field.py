@@ -11,7 +11,7 @@ import torch
 
 from . import capi
 from .synth import aff12, identity_dq
-from .tsdf_volume import _ptr, _stream
+from .tsdf_volume import _flat, _ptr, _stream
 
 F32 = np.float32
 KNN_NEIGHBOURS = 8           # warp_field.hpp:10 (compile-time there, runtime here)
@@ -87,7 +87,7 @@ class WarpField:
         n = int(queries_dev.shape[0])
         idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
         d2 = torch.empty((n, k), dtype=torch.float32, device=self.device)
-        capi.check(capi.lib().dfusion_knn(self.handle, k, _ptr(queries_dev), n, _ptr(idx), _ptr(d2), _stream()),
+        capi.check(capi.lib().dfusion_knn(self.handle, k, _flat(queries_dev), n, _ptr(idx), _ptr(d2), _stream()),
                    "dfusion_knn")
         return idx, d2
 
@@ -95,8 +95,8 @@ class WarpField:
     def warp(self, points_dev, normals_dev=None, k=None):
         k = self.k if k is None else k
         n = int(points_dev.shape[0])
-        capi.check(capi.lib().dfusion_warp_points(self.handle, k, _ptr(points_dev),
-                                                  _ptr(normals_dev) if normals_dev is not None else None, n,
+        capi.check(capi.lib().dfusion_warp_points(self.handle, k, _flat(points_dev),
+                                                  _flat(normals_dev) if normals_dev is not None else None, n,
                                                   capi.floats(aff12(self.warp_to_live_)), _stream()),
                    "dfusion_warp_points")
 
@@ -132,6 +132,6 @@ class WarpField:
         n = int(canonical_dev.shape[0])
         dq = torch.empty((self.M, 8), dtype=torch.float32, device=self.device)
         en = torch.zeros(2, dtype=torch.float32, device=self.device)
-        capi.check(capi.lib().dfusion_warp_solve_data_term(self.handle, k, _ptr(canonical_dev), _ptr(live_dev), n, int(iters), float(lam),
+        capi.check(capi.lib().dfusion_warp_solve_data_term(self.handle, k, _flat(canonical_dev), _flat(live_dev), n, int(iters), float(lam),
                                                            _ptr(dq), _ptr(en), _stream()), "dfusion_warp_solve_data_term")
         return dq, en

@@ -15,6 +15,10 @@
  *     kfusion/src/safe_call.hpp:13-27; the C++ wrapper maps non-zero to kfusion::cuda::error).
  *   - pointers named *_dev are DEVICE pointers; small parameter blocks (affines, intrinsics)
  *     are HOST pointers read before the call returns (the reference passes them by value).
+ *   - images are pitched: row y starts at base + y * pitch, the pitch a byte count of the caller's choice
+ *     (hipMallocPitch / cudaMallocPitch steps, row bands and column windows of larger images).  Every image
+ *     argument returns DF_E_INVALID when its pitch is smaller than cols * bytes per pixel (u16 2, float4 16,
+ *     BGRA 4; dfusion_transform_points: cols * stride * 4; dfusion_icp_estimate: each level's images).
  *   - an affine is 12 floats: R row-major [9] then t [3]  (device::Aff3f, internal.hpp:26-27,
  *     filled by device_cast, kfusion/src/precomp.hpp:19-28).
  *   - kernels are enqueued on `stream` and NOT synchronised (the reference's integrate ends in
