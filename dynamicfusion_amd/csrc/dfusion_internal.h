@@ -65,6 +65,7 @@ struct DfWarpField {
     int geom_dims[3]; float geom_vs[3]; float geom_aff[12];
     float geom_inv[12]; bool geom_inv_ok;      // world -> volume (locates the brick of a query point)
     bool index_valid;
+    unsigned index_flags; DfSlab index_slab;   // what the last dfusion_warp_build_index was given (dfusion_warp_extend rebuilds with them)
     // per-voxel k-NN table (optional, DF_INDEX_VOXEL_TABLE)
     uint16_t* knn_tab; size_t knn_tab_cap;      // elements (uint16)
     int tab_z0, tab_zn, tab_k; bool tab_valid;
@@ -107,6 +108,9 @@ struct DfWarpField {
     // block blend models: entry-major [DF_BM_NU][blk_cap] node ids, {mid, half width} half pairs of the normalised and of the raw
     // weights (allocated with the first model), bm_cnt entry counts
     uint8_t* blk_state; float* blk_wmax; uint8_t* blk_alive; uint32_t* blk_work; uint32_t* blk_cnt; size_t blk_cap; int blk_phase;
+    // blk_tie [block] 1 = the block's table build met two exactly equidistant candidates (topk_insert's tie branch): its table depends on
+    // the tie tree, and a rebuilt tree (dfusion_warp_extend) may reorder them anywhere
+    uint8_t* blk_tie;
     uint16_t* bm_idx; uint32_t* bm_lam; uint32_t* bm_w; uint8_t* bm_cnt; size_t bm_cap;
     // 4-bit neighbour codes (round 5; round 6: per 4 x 4 x 4 SUB-block, so that they exist at any node density): per voxel of a block
     // the model pass has visited, its k neighbours as positions in the union list of its sub-block (ascending node ids, <= 16).
@@ -127,4 +131,45 @@ struct DfWarpField {
     // builds, [3] sweep number): read WITHOUT synchronisation by a later call -- a hint whether on-demand work is going on (then the side
     // stream is worth its fork / join, ~13 us per frame), never a condition of correctness
     volatile uint32_t* host_report;
+    void* ext_ws; size_t ext_ws_cap;   // scratch of dfusion_warp_extend (grown on demand)
+    void* grow_ws; size_t grow_ws_cap; // df_warp_grow: the brick lists before the update (grown on demand)
 };
+
+// Appends to the node set without dropping what still holds (dfusion_warp.hip; used by dfusion_warp_extend): the handle takes the grown
+// set pos/dq/sigma[Mn] (layout of dfusion_warp_set_nodes; the first M entries are the current nodes), and an index is brought up to date
+// for it in place -- the brick lists are re-made, and only the table blocks whose brick list changed or whose build met an exact
+// distance tie are marked unbuilt.  Blocks until done.
+int df_warp_grow(DfWarpField* wf, const float* pos, const float* dq, const float* sigma, int Mn, hipStream_t st);
+
+// WarpField::weighting (warp_field.cpp:238-241) per neighbour, and WarpField::DQB (:203-217) from the k weights + node indices, then
+// the DualQuaternion ctor (dual_quaternion.hpp:59-63): what dfusion_warp_points and dfusion_warp_extend blend with
+template <int K>
+__device__ __forceinline__ void dqb_weights(const DfWarpView& W, const float (&bd)[K], const int (&bi)[K], float (&wt)[K])
+{
+#pragma unroll
+    for (int i = 0; i < K; ++i) wt[i] = dqb_weight(bd[i], W.pos_sigma[bi[i]].w);
+}
+template <int K>
+__device__ __forceinline__ void dqb_blend_w(const DfWarpView& W, const float (&wt)[K], const int (&bi)[K], quat* rot_out,
+                                            quat* dual_out)
+{
+    quat tsum, rsum;
+    tsum.w = tsum.x = tsum.y = tsum.z = 0.f;
+    rsum.w = rsum.x = rsum.y = rsum.z = 0.f;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        const int j = bi[i];
+        const float w = wt[i];
+        const float4 t4 = W.node_t[j], r4 = W.rot[j];
+        quat t, r;
+        t.w = t4.x; t.x = t4.y; t.y = t4.z; t.z = t4.w;
+        r.w = r4.x; r.x = r4.y; r.y = r4.z; r.z = r4.w;
+        tsum = q_add(tsum, q_scale(w, t));            // :211
+        rsum = q_add(rsum, q_scale(w, r));            // :212
+    }
+    rsum = q_normalize(rsum);                         // :214
+    quat half;
+    half.w = 0.5f * tsum.w; half.x = 0.5f * tsum.x; half.y = 0.5f * tsum.y; half.z = 0.5f * tsum.z;
+    *rot_out = rsum;
+    *dual_out = q_mul(half, rsum);                    // dual_quaternion.hpp:59-63
+}

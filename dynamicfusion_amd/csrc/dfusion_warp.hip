@@ -166,6 +166,7 @@ extern "C" int dfusion_warp_destroy(DfWarpField* wf)
     (void)hipFree(wf->code_tab); (void)hipFree(wf->bm_ids); (void)hipFree(wf->bm_coded);
     (void)hipFree(wf->scan_tmp);
     (void)hipFree(wf->blk_state); (void)hipFree(wf->blk_wmax); (void)hipFree(wf->blk_alive); (void)hipFree(wf->blk_work); (void)hipFree(wf->blk_cnt);
+    (void)hipFree(wf->blk_tie); (void)hipFree(wf->ext_ws); (void)hipFree(wf->grow_ws);
     (void)hipFree(wf->nf_nodes); (void)hipFree(wf->nf_vpos); (void)hipFree(wf->pyr_mem);
     (void)hipFree(wf->plan_mask); (void)hipFree(wf->plan_list); (void)hipFree(wf->plan_hist);
     free(wf);
@@ -400,6 +401,15 @@ __device__ __forceinline__ void topk_insert(float (&bd)[K], int (&bi)[K], float 
         }
     }
 }
+// true when topk_insert(bd, .., d, ..) takes its equal-distance branch (the result then depends on the tie tree)
+template <int K>
+__device__ __forceinline__ bool df_topk_tie(const float (&bd)[K], float d)
+{
+    bool eq = false;
+#pragma unroll
+    for (int i = 0; i < K; ++i) eq = eq || (bd[i] == d);
+    return eq && d <= bd[K - 1];
+}
 template <int K>
 __device__ __forceinline__ void topk_init(float (&bd)[K], int (&bi)[K])
 {
@@ -407,31 +417,7 @@ __device__ __forceinline__ void topk_init(float (&bd)[K], int (&bi)[K])
     for (int i = 0; i < K; ++i) { bd[i] = __uint_as_float(0x7f800000u); bi[i] = 0; }   // +inf
 }
 
-// WarpField::DQB (warp_field.cpp:203-217) from the k weights + node indices, then DualQuaternion ctor :59-63.
-template <int K>
-__device__ __forceinline__ void dqb_blend_w(const DfWarpView& W, const float (&wt)[K], const int (&bi)[K], quat* rot_out,
-                                            quat* dual_out)
-{
-    quat tsum, rsum;
-    tsum.w = tsum.x = tsum.y = tsum.z = 0.f;
-    rsum.w = rsum.x = rsum.y = rsum.z = 0.f;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        const int j = bi[i];
-        const float w = wt[i];
-        const float4 t4 = W.node_t[j], r4 = W.rot[j];
-        quat t, r;
-        t.w = t4.x; t.x = t4.y; t.y = t4.z; t.z = t4.w;
-        r.w = r4.x; r.x = r4.y; r.y = r4.z; r.z = r4.w;
-        tsum = q_add(tsum, q_scale(w, t));            // :211
-        rsum = q_add(rsum, q_scale(w, r));            // :212
-    }
-    rsum = q_normalize(rsum);                         // :214
-    quat half;
-    half.w = 0.5f * tsum.w; half.x = 0.5f * tsum.x; half.y = 0.5f * tsum.y; half.z = 0.5f * tsum.z;
-    *rot_out = rsum;
-    *dual_out = q_mul(half, rsum);                    // dual_quaternion.hpp:59-63
-}
+// dqb_blend_w (WarpField::DQB from the k weights + node indices): dfusion_internal.h
 // Same blend with the node transforms staged in LDS: s_node[2j] = rot_j, s_node[2j+1] = node_t_j (GLOBAL node id j), so
 // the two ds_read_b128 of a node share one address (the second uses the instruction's immediate offset).  The sums are
 // kept as two float2 halves in MEMORY order ((w,x),(y,z)): the backend maps them 1:1 onto v_pk_mul_f32 / v_pk_add_f32
@@ -469,13 +455,7 @@ __device__ __forceinline__ void dqb_blend_lds(const float4* s_node, const float 
     *dual_out = q_mul(half, rsum);                    // dual_quaternion.hpp:59-63
 }
 
-// weights from squared distances: WarpField::weighting (warp_field.cpp:238-241) per neighbour
-template <int K>
-__device__ __forceinline__ void dqb_weights(const DfWarpView& W, const float (&bd)[K], const int (&bi)[K], float (&wt)[K])
-{
-#pragma unroll
-    for (int i = 0; i < K; ++i) wt[i] = dqb_weight(bd[i], W.pos_sigma[bi[i]].w);
-}
+// weights from squared distances (WarpField::weighting per neighbour): dqb_weights, dfusion_internal.h
 template <int K>
 __device__ __forceinline__ void dqb_blend(const DfWarpView& W, const float (&bd)[K], const int (&bi)[K], quat* rot_out,
                                           quat* dual_out)
@@ -1033,16 +1013,9 @@ __global__ __launch_bounds__(256) void df_scan_apply_kernel(const uint32_t* __re
 static int df_build_voxel_table(DfWarpField* wf, const DfVolume& v, const DfSlab& s, const float vol2world[12], int k, bool weights,
                                 bool on_demand, hipStream_t st);
 
-extern "C" int dfusion_warp_build_index(DfWarpField* wf, DfVolume v, const DfSlab* slab, const float vol2world[12], int k,
-                                        unsigned flags, dfStream stream)
+// The brick lists (and the geometry they were made for) of dfusion_warp_build_index, for the node set the handle holds; blocks until built.
+static int df_index_bricks(DfWarpField* wf, const DfVolume& v, const float vol2world[12], int k, hipStream_t st)
 {
-    if (!wf || !vol2world || wf->M <= 0 || k < 1 || k > 8 || wf->M < k) return DF_E_INVALID;
-    if (v.dims[0] <= 0 || v.dims[1] <= 0 || v.dims[2] <= 0) return DF_E_INVALID;
-    DfSlab sl = df_slab_or_full(v, slab);
-    if (sl.z_own_n < 0 || sl.z_own0 < 0 || sl.z_own0 + sl.z_own_n > v.dims[2]) return DF_E_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    df_side_drain(wf);                                         // (look-ahead builds of the tables about to be re-made)
-    wf->prep_valid = false;                                    // (a prepared plan points into the index and tables re-made here: ADVICE r5)
     DfIndexGeom g;
     g.X = v.dims[0]; g.Y = v.dims[1]; g.Z = v.dims[2];
     g.bx = (g.X + DF_BRICK - 1) / DF_BRICK; g.by = (g.Y + DF_BRICK - 1) / DF_BRICK; g.bz = (g.Z + DF_BRICK - 1) / DF_BRICK;
@@ -1131,6 +1104,21 @@ extern "C" int dfusion_warp_build_index(DfWarpField* wf, DfVolume v, const DfSla
         for (int i = 0; i < 3; ++i)
             wf->geom_inv[9 + i] = (float)-((d[3 * i] * m[9] + d[3 * i + 1] * m[10] + d[3 * i + 2] * m[11]) / det);
     }
+    return DF_OK;
+}
+
+extern "C" int dfusion_warp_build_index(DfWarpField* wf, DfVolume v, const DfSlab* slab, const float vol2world[12], int k,
+                                        unsigned flags, dfStream stream)
+{
+    if (!wf || !vol2world || wf->M <= 0 || k < 1 || k > 8 || wf->M < k) return DF_E_INVALID;
+    if (v.dims[0] <= 0 || v.dims[1] <= 0 || v.dims[2] <= 0) return DF_E_INVALID;
+    DfSlab sl = df_slab_or_full(v, slab);
+    if (sl.z_own_n < 0 || sl.z_own0 < 0 || sl.z_own0 + sl.z_own_n > v.dims[2]) return DF_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    df_side_drain(wf);                                         // (look-ahead builds of the tables about to be re-made)
+    wf->prep_valid = false;                                    // (a prepared plan points into the index and tables re-made here: ADVICE r5)
+    { int rc = df_index_bricks(wf, v, vol2world, k, st); if (rc) return rc; }
+    wf->index_flags = flags; wf->index_slab = sl;
     wf->index_valid = true;
     wf->tab_valid = false;
     wf->w_tab_valid = false;
@@ -1195,6 +1183,7 @@ struct DfWarpedArgs {
     float pf_margin;
     unsigned pf_cap;               // look-ahead builds per frame at most (the list's counter may run past it)
     unsigned work_cap;             // list-driven build: entries of the list at most (0 = all)
+    uint8_t* blk_tie;              // table build: per block (blk_wmax's grid), set to 1 when a voxel's top-k met an exact distance tie (nullable)
 };
 // A tile is ZERO-WEIGHT for a frame when tile_wmax * max_j |rot_j| < 2^-76: every component of every voxel's blend sum
 // sum_i w_i rot_i is then below 2^-75 in magnitude (the 2x margin covers the rounding of the sums), its square below 2^-150
@@ -1425,6 +1414,7 @@ __device__ __forceinline__ void df_warp_brick_body(const DfWarpedArgs& a, const 
     topk_init<K>(bd1, bi1);
     const uint32_t off = W.brick_off[b];
     const uint32_t cnt = W.brick_off[b + 1] - off;
+    [[maybe_unused]] bool tie = false;               // (BUILD) topk_insert took its equal-distance branch: the tie tree decided
     // The candidates are visited NEAREST (to the brick's centre) FIRST: the result does not depend on the order (topk_insert places
     // equal distances by the reference's rule whatever the arrival order), but the cost does -- an insert runs for the whole wave when
     // any lane needs it, and with the near nodes seen first the lists are final after a third of the candidates and the rest fail the
@@ -1459,8 +1449,10 @@ __device__ __forceinline__ void df_warp_brick_body(const DfWarpedArgs& a, const 
         for (int c = 0; c < n; ++c) {
             const float4 p = s_pos[c];                 // broadcast ds_read_b128
             const int j = s_idx[c];
-            topk_insert<K>(bd0, bi0, knn_dist2(q0, p.x, p.y, p.z), j, W.nf, q0);
-            topk_insert<K>(bd1, bi1, knn_dist2(q1, p.x, p.y, p.z), j, W.nf, q1);
+            const float d0 = knn_dist2(q0, p.x, p.y, p.z), d1 = knn_dist2(q1, p.x, p.y, p.z);
+            if constexpr (BUILD) tie = tie || df_topk_tie<K>(bd0, d0) || df_topk_tie<K>(bd1, d1);
+            topk_insert<K>(bd0, bi0, d0, j, W.nf, q0);
+            topk_insert<K>(bd1, bi1, d1, j, W.nf, q1);
         }
     }
 
@@ -1468,6 +1460,8 @@ __device__ __forceinline__ void df_warp_brick_body(const DfWarpedArgs& a, const 
     float wt0[K], wt1[K];
     if constexpr (BUILD) {
         const size_t tv0 = df_tab_index(a, x, y, z0), tv1 = df_tab_index(a, x, y, z1);
+        if (tie && a.blk_tie)                               // plain byte store; every lane that saw a tie writes the same 1
+            a.blk_tie[((size_t)((bzz * DF_BRICK - a.tab_z0) / 8) * a.bm_nby + byy) * a.bm_nbx + bxx] = 1;
         float wsum = 0.f;
         if (act0) { knn_tab_store<K>(a.knn_tab, tv0, bi0); if (a.w_tab) { dqb_weights<K>(W, bd0, bi0, wt0); w_tab_store<K>(a.w_tab, a.tab_nvox, tv0, wt0); } }
         if (act1) { knn_tab_store<K>(a.knn_tab, tv1, bi1); if (a.w_tab) { dqb_weights<K>(W, bd1, bi1, wt1); w_tab_store<K>(a.w_tab, a.tab_nvox, tv1, wt1); } }
@@ -2363,6 +2357,7 @@ static DfWarpedArgs df_table_args(const DfWarpField* wf)
     a.bz0 = wf->tab_z0 / DF_BRICK;
     a.bm_nbx = ntx * (DF_TAB_TX / 8); a.bm_nby = nty * (DF_TAB_TY / 8);
     a.code_tab = wf->code_tab; a.bm_ids = wf->bm_ids; a.bm_coded = wf->bm_coded;
+    a.blk_tie = wf->blk_tie;
     return a;
 }
 // LDS a workgroup may ask for on this device (160 KiB on gfx950), what the node-table kernels' "fits" is decided against (the
@@ -2884,9 +2879,10 @@ static int df_build_voxel_table(DfWarpField* wf, const DfVolume& v, const DfSlab
     }
     const size_t nblk = (size_t)ntx * (DF_TAB_TX / 8) * nty * (DF_TAB_TY / 8) * (tzn / 8);
     if (nblk > wf->blk_cap) {
-        (void)hipFree(wf->blk_state); (void)hipFree(wf->blk_wmax); (void)hipFree(wf->blk_alive); (void)hipFree(wf->blk_work);
-        wf->blk_state = nullptr; wf->blk_wmax = nullptr; wf->blk_alive = nullptr; wf->blk_work = nullptr; wf->blk_cap = 0;
+        (void)hipFree(wf->blk_state); (void)hipFree(wf->blk_wmax); (void)hipFree(wf->blk_alive); (void)hipFree(wf->blk_work); (void)hipFree(wf->blk_tie);
+        wf->blk_state = nullptr; wf->blk_wmax = nullptr; wf->blk_alive = nullptr; wf->blk_work = nullptr; wf->blk_tie = nullptr; wf->blk_cap = 0;
         DF_HIP(hipMalloc((void**)&wf->blk_state, nblk));
+        DF_HIP(hipMalloc((void**)&wf->blk_tie, nblk));
         DF_HIP(hipMalloc((void**)&wf->blk_wmax, nblk * sizeof(float)));
         DF_HIP(hipMalloc((void**)&wf->blk_alive, nblk));
         DF_HIP(hipMalloc((void**)&wf->blk_work, 3 * nblk * sizeof(uint32_t)));
@@ -2895,6 +2891,7 @@ static int df_build_voxel_table(DfWarpField* wf, const DfVolume& v, const DfSlab
     if (!wf->blk_cnt) DF_HIP(hipMalloc((void**)&wf->blk_cnt, 16 * sizeof(uint32_t)));
     DF_HIP(hipMemsetAsync(wf->blk_cnt, 0, 16 * sizeof(uint32_t), st));
     DF_HIP(hipMemsetAsync(wf->blk_state, on_demand ? 0 : 1, nblk, st));
+    DF_HIP(hipMemsetAsync(wf->blk_tie, 0, nblk, st));
     DF_HIP(hipMemsetAsync(wf->blk_wmax, 0, nblk * sizeof(float), st));
     wf->blk_phase = 0;
     wf->tab_z0 = tz0; wf->tab_zn = tzn; wf->tab_k = k; wf->tab_valid = true; wf->w_tab_valid = weights;
@@ -2910,5 +2907,81 @@ static int df_build_voxel_table(DfWarpField* wf, const DfVolume& v, const DfSlab
         wf->tab_valid = false; wf->w_tab_valid = false; wf->tab_complete = false;
         return (int)e;
     }
+    return DF_OK;
+}
+
+// ====================================================================================== growth (dfusion_warp_extend)
+// A table block is stale after growth when its brick's list changed (then a new node may be among its voxels' k nearest, and the lists
+// are what the table build ranks), or when its build met an exact distance tie (the rebuilt tie tree may order the equidistant old nodes
+// differently).  Otherwise its voxels rank the same candidates at the same distances without consulting the tree: the same tables,
+// weights, blend model and codes.  Stale blocks go back to "not built", as after dfusion_warp_build_index with on-demand tables.
+__global__ __launch_bounds__(256) void df_grow_dirty_kernel(const uint32_t* __restrict__ old_off, const uint16_t* __restrict__ old_list,
+                                                            const uint32_t* __restrict__ off, const uint16_t* __restrict__ list,
+                                                            int bx, int by, int bz, int nbx, int nby, int nbz, int bz0,
+                                                            uint8_t* __restrict__ blk_state, float* __restrict__ blk_wmax, uint8_t* __restrict__ blk_tie)
+{
+    const size_t blk = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (blk >= (size_t)nbx * nby * nbz) return;
+    const int x = (int)(blk % (size_t)nbx), y = (int)((blk / (size_t)nbx) % (size_t)nby), z = (int)(blk / ((size_t)nbx * nby));
+    if (x >= bx || y >= by || z + bz0 >= bz) return;                       // (blocks of the table's padding hold no voxels)
+    const size_t b = ((size_t)(z + bz0) * by + y) * bx + x;
+    const uint32_t o0 = old_off[b], n0 = old_off[b + 1] - o0, o1 = off[b], n1 = off[b + 1] - o1;
+    bool dirty = blk_tie[blk] != 0 || n0 != n1;
+    for (uint32_t i = 0; !dirty && i < n1; ++i) dirty = old_list[o0 + i] != list[o1 + i];
+    if (dirty) {
+        blk_state[blk] = 0; blk_tie[blk] = 0;
+        if (blk_wmax) blk_wmax[blk] = 0.f;
+    }
+}
+
+int df_warp_grow(DfWarpField* wf, const float* pos, const float* dq, const float* sigma, int Mn, hipStream_t st)
+{
+    if (!wf || !pos || !dq || !sigma || Mn < wf->M || Mn > 65535) return DF_E_INVALID;
+    df_side_drain(wf);                                         // (look-ahead builds read the node arrays and write the tables)
+    wf->prep_valid = false;                                    // (a prepared plan was made for the old node set)
+    if (Mn > wf->cap) {                                        // headroom: a run of small extends does not reallocate every time
+        int cap = wf->cap + wf->cap / 2 + 256;
+        cap = cap < Mn ? Mn : cap > 65535 ? 65535 : cap;
+        int rc = df_warp_reserve(wf, cap);                     // (waits for every split sweep; the arrays are re-packed whole below)
+        if (rc) return rc;
+    }
+    { int rc = df_wait_split_sweep(wf, st); if (rc) return rc; }
+    wf->M = Mn;
+    { int rc = df_warp_pack_current(wf, pos, dq, sigma, st); if (rc) return rc; }   // (bounds, the sigma bound [4] included)
+    { int rc = df_warp_build_tie_tree(wf, st); if (rc) return rc; }
+    if (!wf->index_valid) return DF_OK;
+    const size_t nb = (size_t)wf->bx * wf->by * wf->bz;
+    const bool tabs = wf->tab_valid && wf->blk_state && wf->blk_tie;
+    uint32_t* old_off = nullptr; uint16_t* old_list = nullptr;
+    if (tabs) {                                                // the lists before the update, to find the bricks whose list changes
+        const size_t off_bytes = ((nb + 1) * sizeof(uint32_t) + 255) & ~(size_t)255, need = off_bytes + wf->list_cap * sizeof(uint16_t);
+        if (need > wf->grow_ws_cap) {
+            (void)hipFree(wf->grow_ws); wf->grow_ws = nullptr; wf->grow_ws_cap = 0;
+            DF_HIP(hipMalloc(&wf->grow_ws, need));
+            wf->grow_ws_cap = need;
+        }
+        old_off = (uint32_t*)wf->grow_ws; old_list = (uint16_t*)((char*)wf->grow_ws + off_bytes);
+        DF_HIP(hipMemcpyAsync(old_off, wf->brick_off, (nb + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        DF_HIP(hipMemcpyAsync(old_list, wf->brick_list, wf->list_cap * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
+    }
+    wf->index_valid = false;                                   // (until the lists are re-made)
+    DfVolume v; memset(&v, 0, sizeof(v));
+    memcpy(v.dims, wf->geom_dims, sizeof(v.dims)); memcpy(v.voxel_size, wf->geom_vs, sizeof(v.voxel_size));
+    float aff[12]; memcpy(aff, wf->geom_aff, sizeof(aff));
+    { int rc = df_index_bricks(wf, v, aff, wf->k_built, st); if (rc) return rc; }
+    wf->index_valid = true;
+    if (!tabs) return DF_OK;
+    const DfWarpedArgs a = df_table_args(wf);
+    const int nbz = wf->tab_zn / 8;
+    const size_t nblk = (size_t)a.bm_nbx * a.bm_nby * nbz;
+    hipLaunchKernelGGL(df_grow_dirty_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, old_off, old_list, wf->brick_off, wf->brick_list,
+                       wf->bx, wf->by, wf->bz, a.bm_nbx, a.bm_nby, nbz, wf->tab_z0 / DF_BRICK, wf->blk_state, a.blk_wmax, wf->blk_tie);
+    DF_LAUNCH_CHECK();
+    wf->alive_valid = false; wf->tab_complete = false;
+    if (!((wf->index_flags & DF_INDEX_TABLES_ON_DEMAND) && wf->w_tab_valid)) {   // eager tables: the stale blocks are re-made here
+        int rc = df_tables_complete(wf, st);
+        if (rc) return rc;
+    }
+    DF_HIP(hipStreamSynchronize(st));
     return DF_OK;
 }

@@ -139,9 +139,46 @@ static int dqb_mode(const char* fin, const char* fout)
     return 0;
 }
 
+// `warp_tests extend IN OUT`: WarpField::extend through the mirror.  IN: u32 M, N, k; f32 radius, sigma_new; then pos f32[M*3],
+// dq f32[M*8], sigma f32[M], points f32[N*3].  OUT: u32 node count, nodes added; then the node store after the call (getNodes):
+// vertex f32[3], transform f32[8], weight f32 per node.
+static int extend_mode(const char* fin, const char* fout)
+{
+    FILE* f = std::fopen(fin, "rb");
+    if (!f) return 2;
+    unsigned hdr[3]; float par[2];
+    if (std::fread(hdr, 4, 3, f) != 3 || std::fread(par, 4, 2, f) != 2) return 2;
+    const unsigned M = hdr[0], N = hdr[1], k = hdr[2];
+    std::vector<float> pos(3 * (size_t)M), dq(8 * (size_t)M), sigma(M), pts(3 * (size_t)N);
+    if (std::fread(pos.data(), 4, pos.size(), f) != pos.size() || std::fread(dq.data(), 4, dq.size(), f) != dq.size() ||
+        std::fread(sigma.data(), 4, sigma.size(), f) != sigma.size() || std::fread(pts.data(), 4, pts.size(), f) != pts.size()) return 2;
+    std::fclose(f);
+    kfusion::WarpField wf((int)k);
+    std::vector<Vec3f> seeds(M), points(N);
+    for (unsigned i = 0; i < M; ++i) seeds[i] = Vec3f(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]);
+    for (unsigned i = 0; i < N; ++i) points[i] = Vec3f(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
+    wf.init(seeds);
+    std::vector<kfusion::deformation_node>& nodes = *wf.getNodes();
+    if (nodes.size() != M) return 3;
+    for (unsigned i = 0; i < M; ++i) { std::memcpy((void*)nodes[i].transform.raw(), &dq[8 * i], 32); nodes[i].weight = sigma[i]; }
+    wf.commit(true);
+    const int added = wf.extend(points, par[0], par[1]);
+    const std::vector<kfusion::deformation_node>& out = *wf.getNodes();
+    if (out.size() != M + (size_t)added || wf.nodeCount() != out.size()) return 4;
+    FILE* o = std::fopen(fout, "wb");
+    if (!o) return 2;
+    const unsigned ohdr[2] = {(unsigned)out.size(), (unsigned)added};
+    std::fwrite(ohdr, 4, 2, o);
+    for (const kfusion::deformation_node& n : out) { std::fwrite(n.vertex.val, 4, 3, o); std::fwrite(n.transform.raw(), 4, 8, o); std::fwrite(&n.weight, 4, 1, o); }
+    std::fclose(o);
+    std::printf("warp_tests extend ok: %u nodes + %d\n", M, added);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     if (argc == 4 && !std::strcmp(argv[1], "dqb")) return dqb_mode(argv[2], argv[3]);
+    if (argc == 4 && !std::strcmp(argv[1], "extend")) return extend_mode(argv[2], argv[3]);
     struct { const char* name; bool (*fn)(); } tests[] = {
         {"EnergyDataSingleVertexTest", EnergyDataSingleVertexTest}, {"EnergyDataRigidTest", EnergyDataRigidTest},
         {"WarpAndReverseTest", WarpAndReverseTest}, {"MultipleNodesTest", MultipleNodesTest}, {"NonRigidTest", NonRigidTest}};

@@ -63,6 +63,10 @@ namespace kfusion
         /// node transforms that are ALREADY on the device (8 floats a node: rotation_, translation_ -- what a device-side solver leaves):
         /// no host round trip, nothing synchronises; the host node store follows on its next access (getNodes)
         void setTransformsDevice(const cuda::DeviceArray<float>& dq8);
+        /// grows the field (DynamicFusion section 3.4; dfusion_warp_extend): one node, dg_w = `sigma`, for the lowest-index point of every
+        /// `radius` grid cell whose points have no node within its dg_w among their k() nearest; the new nodes (transform: DQB over
+        /// the old ones) are appended to the node store, and a k-NN index stays valid.  Returns the number of nodes added.
+        int extend(const std::vector<Vec3f>& points, float radius, float sigma);
 
         /// warp_field.cpp:180-195, on the GPU; vectors are modified in place
         void warp(std::vector<Vec3f>& points, std::vector<Vec3f>& normals) const;

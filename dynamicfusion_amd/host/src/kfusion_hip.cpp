@@ -1,6 +1,7 @@
 // kfusion_hip.cpp -- host side of the drop-in boundary: kfusion::cuda::{DeviceMemory, TsdfVolume, computeDists} and
 // kfusion::WarpField implemented over the C-ABI (include/dfusion.h) and the HIP runtime.  The call sequences mirror
 // /root/reference/kfusion/src/tsdf_volume.cpp, device_memory.cpp, imgproc.cpp and warp_field.cpp (cited per function).
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -511,6 +512,32 @@ void WarpField::setTransformsDevice(const cuda::DeviceArray<float>& dq8)
     solve_dq_.create(M * 8);                                 // what the host node store is refreshed from when it is next looked at
     KF_HIP(hipMemcpyAsync(solve_dq_.ptr(), dq8.ptr(), M * 8 * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
     nodes_stale_ = true;
+}
+
+int WarpField::extend(const std::vector<Vec3f>& points, float radius, float sigma)
+{
+    static_assert(sizeof(Vec3f) == 12, "Vec3f must be 3 packed floats");
+    pullNodes();                                           // (the appended nodes follow the current ones)
+    const int M = (int)nodes_.size(), N = (int)points.size();
+    const int cap = std::max(0, std::min(N, 65535 - M));
+    DeviceArray<float> d_pts, d_pos(std::max(cap, 1) * 3), d_dq(std::max(cap, 1) * 8), d_sigma(std::max(cap, 1));
+    if (N) d_pts.upload(points[0].val, (size_t)N * 3);
+    int added = 0, winners = 0;
+    const int rc = dfusion_warp_extend(handle_, k_, N ? d_pts.ptr() : nullptr, N, radius, sigma, cap, d_pos.ptr(), d_dq.ptr(), d_sigma.ptr(),
+                                       &added, &winners, nullptr);
+    if (rc != DF_OK) index_ok_ = false;                    // (if the nodes went in, they are appended below before the error is raised)
+    if (added == 0) { KF_DF(rc); return 0; }
+    std::vector<float> pos((size_t)d_pos.size()), dq((size_t)d_dq.size()), sg((size_t)d_sigma.size());
+    d_pos.download(pos); d_dq.download(dq); d_sigma.download(sg);
+    for (int i = 0; i < added; ++i) {
+        deformation_node n;
+        n.vertex = Vec3f(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]);
+        std::memcpy((void*)n.transform.raw(), &dq[8 * (size_t)i], 32);
+        n.weight = sg[i];
+        nodes_.push_back(n);
+    }
+    KF_DF(rc);
+    return added;
 }
 
 void WarpField::energy_data(const cuda::DeviceArray<float>& canonical_vertices, const cuda::DeviceArray<float>& live_vertices, int n)

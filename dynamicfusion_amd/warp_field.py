@@ -33,6 +33,7 @@ class WarpField:
         self.M = 0
         self._index_key = None
         self._keep = []
+        self._dq = None
 
     def __del__(self):
         try:
@@ -54,14 +55,51 @@ class WarpField:
     def set_nodes(self, pos_dev, dq_dev, sigma_dev):
         self.M = int(pos_dev.shape[0])
         self._keep = [pos_dev, dq_dev, sigma_dev]
+        self._dq = dq_dev                              # the transforms the handle holds now (set_transforms / energy_data replace them)
         capi.check(capi.lib().dfusion_warp_set_nodes(self.handle, _ptr(pos_dev), _ptr(dq_dev), _ptr(sigma_dev), self.M,
                                                      _stream()), "dfusion_warp_set_nodes")
         self._index_key = None
+
+    def extend(self, points_dev, radius, sigma=None, max_new=None, k=None):
+        """Grow the field (include/dfusion.h dfusion_warp_extend): a node for the lowest-index unsupported point of every `radius` grid
+        cell, dg_w = `sigma` (None: the lower median dg_w of the current nodes), at most `max_new` (None: as many as fit 65535).  The
+        k-NN index, if any, is updated on the handle for the same volume geometry, so the index key stays valid.  Returns
+        (n_added, n_winners).  The added nodes are kept as self.new_nodes = (pos [n,3], dq [n,8], sigma [n]) device tensors: the
+        next set_transforms takes M + n_added transforms, the new nodes' following the old ones.  self._keep becomes the grown set as
+        the handle now holds it (the current transforms of the old nodes, then the new ones)."""
+        k = self.k if k is None else int(k)
+        old_pos, old_dq, old_sigma = self._keep
+        if sigma is None:
+            sigma = float(torch.median(old_sigma.reshape(-1).float()).item())
+        cap = max(0, 65535 - self.M) if max_new is None else int(max_new)
+        pts = points_dev.reshape(-1, 3)
+        n = int(pts.shape[0])
+        m = max(0, min(cap, n))
+        new_pos = torch.empty((m, 3), dtype=torch.float32, device=self.device)
+        new_dq = torch.empty((m, 8), dtype=torch.float32, device=self.device)
+        new_sigma = torch.empty(m, dtype=torch.float32, device=self.device)
+        added, winners = C.c_int(0), C.c_int(0)
+        rc = (capi.lib().dfusion_warp_extend(self.handle, k, _flat(pts) if n else None, n, float(radius), float(sigma), cap,
+                                                  _ptr(new_pos) if m else None, _ptr(new_dq) if m else None, _ptr(new_sigma) if m else None,
+                                                  C.byref(added), C.byref(winners), _stream()))
+        a = added.value                                # (also set when the nodes went in and a later step failed: the handle holds them)
+        self.new_nodes = (new_pos[:a], new_dq[:a], new_sigma[:a])
+        if a:
+            self.M += a
+            cur = self._dq if self._dq is not None else old_dq
+            self._keep = [torch.cat([old_pos.reshape(-1, 3), new_pos[:a]]), torch.cat([cur.reshape(-1, 8), new_dq[:a]]),
+                          torch.cat([old_sigma.reshape(-1), new_sigma[:a]])]
+            self._dq = self._keep[1]
+        if rc != 0:
+            self._index_key = None                     # (the index update did not complete)
+        capi.check(rc, "dfusion_warp_extend")
+        return a, winners.value
 
     def set_transforms(self, dq_dev):
         """What the warp optimiser writes back every frame (CombinedSolver.h:189-197)."""
         capi.check(capi.lib().dfusion_warp_set_transforms(self.handle, _ptr(dq_dev), _stream()),
                    "dfusion_warp_set_transforms")
+        self._dq = dq_dev
 
     def setWarpToLive(self, pose):     # warp_field.cpp:302-305
         self.warp_to_live_ = np.asarray(pose, F32).reshape(4, 4).copy()
@@ -134,4 +172,5 @@ class WarpField:
         en = torch.zeros(2, dtype=torch.float32, device=self.device)
         capi.check(capi.lib().dfusion_warp_solve_data_term(self.handle, k, _flat(canonical_dev), _flat(live_dev), n, int(iters), float(lam),
                                                            _ptr(dq), _ptr(en), _stream()), "dfusion_warp_solve_data_term")
+        self._dq = dq
         return dq, en

@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define DFUSION_ABI_VERSION 7   /* 7: dfusion_raycast_min_pieces (the sharded cast's key merge as direct exchanges: all-to-all of row bands, local MIN, all-gather); 6: dfusion_cloud_to_depth; the planned warped sweep takes every node count (no LDS node table: DF_WARP_NO_LDS now only selects the plain gather kernel), a prepared plan is also voided by set_nodes / build_index / a second set_transforms; 5: dfusion_integrate_warped_prepare / _sweep (the frame's integrate in two calls, for cross-frame overlap), dfusion_raycast_sum_pieces (direct row-band merge), DF_WARP_STEADY_PREFETCH, dfusion_selftest_exact_forms takes TEN counters ([8], [9]: the f32-division form of the blend's first normalisation), DF_WARP_NO_CODES + dfusion_warp_coded_blocks (4-bit neighbour codes of modelled blocks); 4: no process-wide state left: dfusion_integrate_ex (validation flags + swept counter per call) replaces dfusion_debug_rigid / dfusion_debug_rigid_counters, dfusion_warp_debug_counters (per handle) replaces dfusion_debug_warp_counters; dfusion_warp_alive_blocks; dfusion_raycast_points_of_keys_rows; DF_WARP_NO_PREFETCH; 3: dfusion_raycast_points_of_keys (dfusion_raycast_shade's points nullable), dfusion_release_scratch, DF_INDEX_TABLES_ON_DEMAND, DF_WARP_*_BLOCK_MODEL flags; 2: sharded cast merges on one key (no vertex exchange), dfusion_debug_rigid_counters, selftest counts[6] */
+#define DFUSION_ABI_VERSION 7   /* 7: dfusion_warp_extend (additive); dfusion_raycast_min_pieces (the sharded cast's key merge as direct exchanges: all-to-all of row bands, local MIN, all-gather); 6: dfusion_cloud_to_depth; the planned warped sweep takes every node count (no LDS node table: DF_WARP_NO_LDS now only selects the plain gather kernel), a prepared plan is also voided by set_nodes / build_index / a second set_transforms; 5: dfusion_integrate_warped_prepare / _sweep (the frame's integrate in two calls, for cross-frame overlap), dfusion_raycast_sum_pieces (direct row-band merge), DF_WARP_STEADY_PREFETCH, dfusion_selftest_exact_forms takes TEN counters ([8], [9]: the f32-division form of the blend's first normalisation), DF_WARP_NO_CODES + dfusion_warp_coded_blocks (4-bit neighbour codes of modelled blocks); 4: no process-wide state left: dfusion_integrate_ex (validation flags + swept counter per call) replaces dfusion_debug_rigid / dfusion_debug_rigid_counters, dfusion_warp_debug_counters (per handle) replaces dfusion_debug_warp_counters; dfusion_warp_alive_blocks; dfusion_raycast_points_of_keys_rows; DF_WARP_NO_PREFETCH; 3: dfusion_raycast_points_of_keys (dfusion_raycast_shade's points nullable), dfusion_release_scratch, DF_INDEX_TABLES_ON_DEMAND, DF_WARP_*_BLOCK_MODEL flags; 2: sharded cast merges on one key (no vertex exchange), dfusion_debug_rigid_counters, selftest counts[6] */
 
 typedef void *dfStream; /* hipStream_t */
 
@@ -291,6 +291,27 @@ int dfusion_warp_set_transforms(DfWarpField *wf, const float *dq_dev, dfStream s
  * frames: only transforms are optimised).  `geometry.data` is not dereferenced.  Blocks until built. */
 int dfusion_warp_build_index(DfWarpField *wf, DfVolume geometry, const DfSlab *slab, const float vol2world[12], int k,
                              unsigned flags, dfStream stream);
+
+/* Grows the warp field (DynamicFusion section 3.4, "extending the warp field"; the reference never adds nodes) -- an ABI-7 addition.
+ * points_dev[N*3] are canonical surface points.  With the current M nodes {v_i, dq_i, sigma_i}:
+ *   - p is UNSUPPORTED when it is finite, M >= k, and d2_i >= sigma_i * sigma_i (f32) for each of its k nearest nodes i (what
+ *     dfusion_knn returns, nanoflann's tie order included);
+ *   - cell of p = ((int)floorf(p.x / radius), (int)floorf(p.y / radius), (int)floorf(p.z / radius)), IEEE f32 division; points with
+ *     |p / radius| >= 2^30 on an axis are skipped; in each cell the unsupported point with the LOWEST index wins;
+ *   - the winners with the lowest indices, at most min(max_new, 65535 - M) of them, are appended as nodes M, M+1, ... in increasing
+ *     point index: vertex = p, dg_w = sigma_new, transform = WarpField::DQB(p) over the OLD nodes (warp_field.cpp:203-217) -- or, when
+ *     all k weights are 0, the transform of p's nearest node.  Old nodes keep their index, position, transform and dg_w.
+ * Afterwards every result of the handle (k-NN, warp, solver, warped integrate, index info) is, bit for bit, that of
+ * dfusion_warp_set_nodes(grown set) + dfusion_warp_build_index(geometry, k and flags of the last build, if there was one) on a fresh
+ * handle.  The index is updated in place: brick lists re-made, and only the per-voxel table blocks whose brick list changed or whose
+ * build met an exact distance tie are re-made (on demand, or inside this call for eager tables).  A prepared plan is voided when
+ * nodes are added.  If a step after the nodes went in fails, *n_added still reports them and the handle has no index.
+ *   new_pos_dev[max_new*3], new_dq_dev[max_new*8], new_sigma_dev[max_new]  nullable: the added nodes (layout of dfusion_warp_set_nodes)
+ *   n_added, n_winners  host: nodes added, and cells won (n_added < n_winners when truncated)
+ * N = 0 or no winner: DF_OK, *n_added = 0, the handle untouched.  DF_E_INVALID: k outside 1..8, M < k, radius <= 0 or not finite,
+ * sigma_new not finite, N < 0 or > 2^28, max_new < 0.  Blocks until done.                                                                      */
+int dfusion_warp_extend(DfWarpField *wf, int k, const float *points_dev, int N, float radius, float sigma_new, int max_new,
+                        float *new_pos_dev, float *new_dq_dev, float *new_sigma_dev, int *n_added, int *n_winners, dfStream stream);
 
 /* Introspection of the k-NN index (blocking): total candidate-list entries, number of 8^3 bricks, k it was built for. */
 int dfusion_warp_index_info(const DfWarpField *wf, unsigned long long *total_entries, unsigned int *n_bricks, int *k_built);
