@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include <memory>
+#include <utility>
 #include "dfusion.h"
 #include "dfusion_device.h"
 #include "dfusion_nanoflann.h"
@@ -53,53 +55,78 @@ struct DfWarpView {
     DfNfView nf;               // nanoflann's tree over the nodes: orders exactly equidistant nodes (dfusion_nanoflann.h)
 };
 
-struct DfWarpField {
-    int device;
-    int M, cap;
-    float4 *pos_sigma, *rot, *dual, *node_t;
+// A device allocation the handle owns: pointer and capacity (in elements) change together, and the memory is freed exactly once.
+// reserve() frees FIRST (the old and the new buffer never exist together) and then allocates exactly n elements: no headroom, no copy of
+// the old contents, no zeroing and no synchronisation -- a caller that needs one of those does it itself.  Reads as a T*.
+template <typename T>
+struct DfDevBuf {
+    T* p = nullptr; size_t cap = 0;
+    DfDevBuf() = default;
+    DfDevBuf(DfDevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DfDevBuf& operator=(DfDevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DfDevBuf() { (void)hipFree(p); }
+    operator T*() const { return p; }
+    void release() { (void)hipFree(p); p = nullptr; cap = 0; }
+    int reserve(size_t n)                      // DF_OK or the HIP error; null / 0 after a failure
+    {
+        if (n <= cap) return DF_OK;
+        release();
+        DF_HIP(hipMalloc((void**)&p, n * sizeof(T)));
+        cap = n;
+        return DF_OK;
+    }
+};
+
+struct DfPrepared;                             // (dfusion_warp.hip)
+
+struct __attribute__((visibility("hidden"))) DfWarpField {     // (opaque in dfusion.h: the library exports none of its members)
+    DfWarpField(); ~DfWarpField();             // (dfusion_warp.hip, where DfPrepared is complete)
+    int device = 0;
+    int M = 0, cap = 0;
+    DfDevBuf<float4> pos_sigma, rot, dual, node_t;
     // index
-    uint32_t* brick_off; uint32_t* brick_cnt; uint16_t* brick_list; float* brick_thr;
-    size_t off_cap, list_cap;
-    uint32_t* scan_tmp; size_t scan_cap;       // tile sums / tile offsets of the brick-count scan
-    int bx, by, bz, k_built;
-    int geom_dims[3]; float geom_vs[3]; float geom_aff[12];
-    float geom_inv[12]; bool geom_inv_ok;      // world -> volume (locates the brick of a query point)
-    bool index_valid;
-    unsigned index_flags; DfSlab index_slab;   // what the last dfusion_warp_build_index was given (dfusion_warp_extend rebuilds with them)
+    DfDevBuf<uint32_t> brick_off, brick_cnt; DfDevBuf<uint16_t> brick_list; DfDevBuf<float> brick_thr;
+    size_t off_cap = 0;
+    DfDevBuf<uint32_t> scan_tmp; size_t scan_cap = 0;       // tile sums / tile offsets of the brick-count scan
+    int bx = 0, by = 0, bz = 0, k_built = 0;
+    int geom_dims[3] = {}; float geom_vs[3] = {}; float geom_aff[12] = {};
+    float geom_inv[12] = {}; bool geom_inv_ok = false;      // world -> volume (locates the brick of a query point)
+    bool index_valid = false;
+    unsigned index_flags = 0; DfSlab index_slab = {};   // what the last dfusion_warp_build_index was given (dfusion_warp_extend rebuilds with them)
     // per-voxel k-NN table (optional, DF_INDEX_VOXEL_TABLE)
-    uint16_t* knn_tab; size_t knn_tab_cap;      // elements (uint16)
-    int tab_z0, tab_zn, tab_k; bool tab_valid;
-    float* w_tab; size_t w_tab_cap; bool w_tab_valid;   // per-voxel blend weights (optional, DF_INDEX_WEIGHT_TABLE)
-    float* tile_wmax; size_t tile_wmax_cap;             // per table tile: max over its voxels of the weight sum (with w_tab)
+    DfDevBuf<uint16_t> knn_tab;
+    int tab_z0 = 0, tab_zn = 0, tab_k = 0; bool tab_valid = false;
+    DfDevBuf<float> w_tab; bool w_tab_valid = false;   // per-voxel blend weights (optional, DF_INDEX_WEIGHT_TABLE)
+    DfDevBuf<float> tile_wmax;                          // per table tile: max over its voxels of the weight sum (with w_tab)
     // device scalars for the conservative brick cull: [0] max |t_i|, [1] max sin(theta_i/2), [2] max dists
-    float* bounds_dev;
-    int max_phase;                    // which of bounds_dev[6], [7] this frame's capped pyramid leaves the image-wide maximum in
+    DfDevBuf<float> bounds_dev;
+    int max_phase = 0;                // which of bounds_dev[6], [7] this frame's capped pyramid leaves the image-wide maximum in
     // dfusion_integrate_warped_prepare / _sweep (round 5): the launch state a prepare call leaves for the sweep call (opaque here: the
     // argument structs live in dfusion_warp.hip), and the two events that order the halves when they are issued on different streams
-    void* prep; bool prep_valid;
-    hipEvent_t ev_prep_done, ev_sweep_done[2]; bool split_events;
+    std::unique_ptr<DfPrepared> prep; bool prep_valid = false;
+    hipEvent_t ev_prep_done = nullptr, ev_sweep_done[2] = {}; bool split_events = false;
     // What a sweep issued through the split API may still be READING when the next frame's set_transforms / prepare arrive on another
     // stream is double-buffered, so that they can run BESIDE that sweep instead of after it: the node transform arrays (rot / dual / node_t
     // and their alternates), the launch plan (two sets of mask + bins; FOUR counter sets, zeroed two frames ahead).  Sweeps are numbered;
     // a buffer remembers the last sweep that reads it, the ring of two events holds the last two sweeps (all sweeps on one stream).
-    float4 *rot_alt, *dual_alt, *node_t_alt;
-    float4 *rt, *rt_alt;                             // {rot, node_t} interleaved, and its alternate (see DfWarpView)
-    unsigned long long seq, recorded_seq;            // sweeps prepared / recorded so far
-    unsigned long long ring_seq[2];                  // the sweep whose completion ev_sweep_done[i] stands for (0: none)
-    unsigned long long node_reader[2]; int nphase;  // [nphase] = the current node set's last reader, [nphase ^ 1] = the alternate's
-    unsigned long long plan_reader[2];
-    unsigned long long* plan_mask2[2]; unsigned int* plan_list2[2]; int pphase; unsigned hphase;
-    unsigned long long* plan_code2[2];               // per strip item: which of its (patch, layer) cells read 4-bit codes
-    uint16_t* pyr_mem; size_t pyr_cap;      // max-pyramid of the frame's dists image (warped sweep's depth cull), entries
+    DfDevBuf<float4> rot_alt, dual_alt, node_t_alt;
+    DfDevBuf<float4> rt, rt_alt;                     // {rot, node_t} interleaved, and its alternate (see DfWarpView)
+    unsigned long long seq = 0, recorded_seq = 0;    // sweeps prepared / recorded so far
+    unsigned long long ring_seq[2] = {};             // the sweep whose completion ev_sweep_done[i] stands for (0: none)
+    unsigned long long node_reader[2] = {}; int nphase = 0;  // [nphase] = the current node set's last reader, [nphase ^ 1] = the alternate's
+    unsigned long long plan_reader[2] = {};
+    DfDevBuf<unsigned long long> plan_mask2[2]; DfDevBuf<unsigned int> plan_list2[2]; int pphase = 0; unsigned hphase = 0;
+    DfDevBuf<unsigned long long> plan_code2[2];      // per strip item: which of its (patch, layer) cells read 4-bit codes
+    DfDevBuf<uint16_t> pyr_mem;             // max-pyramid of the frame's dists image (warped sweep's depth cull), entries
     // scratch of dfusion_warp_solve_data_term (grown on demand)
-    void* solver_ws; size_t solver_ws_cap;
+    DfDevBuf<char> solver_ws;
     // points an indexed k-NN / warp pass left to the scan kernel: [0] count, [1..] ids
-    int* pt_ids; size_t pt_ids_cap;
-    int pt_image_cols;                                 // dfusion_warp_set_point_tiling: 0 = point queries in linear order
+    DfDevBuf<int> pt_ids;
+    int pt_image_cols = 0;                             // dfusion_warp_set_point_tiling: 0 = point queries in linear order
     // replica of the reference's nanoflann tree over the node positions (rebuilt by dfusion_warp_set_nodes)
-    DfNfNode* nf_nodes; uint16_t* nf_vpos; size_t nf_nodes_cap, nf_vpos_cap; bool nf_ok; int nf_depth;
+    DfDevBuf<DfNfNode> nf_nodes; DfDevBuf<uint16_t> nf_vpos; bool nf_ok = false; int nf_depth = 0;
     // pipelined warped sweep: the launch plan (verdict masks of the strip items, the alive ones sorted by work), dfusion_warp.hip
-    unsigned long long* plan_mask; unsigned int* plan_list; unsigned int* plan_hist; size_t plan_cap; int plan_phase;
+    DfDevBuf<unsigned int> plan_hist; size_t plan_cap = 0;
     // per 8x8x8 block of the table planes (dfusion_warp_blocks.h; block grid blk_nbx x blk_nby x tab_zn / 8, whole table tiles):
     //   blk_state  0 = tables not built (DF_INDEX_TABLES_ON_DEMAND), 1 = built, 2 = built and a blend-model record written
     //   blk_wmax   max over the block's voxels of the weight sum (0 until built)
@@ -107,32 +134,32 @@ struct DfWarpField {
     //   blk_cnt [2 sets][8] their lengths and the build passes' cursors (the sets alternate between passes: each pass zeroes the other one)
     // block blend models: entry-major [DF_BM_NU][blk_cap] node ids, {mid, half width} half pairs of the normalised and of the raw
     // weights (allocated with the first model), bm_cnt entry counts
-    uint8_t* blk_state; float* blk_wmax; uint8_t* blk_alive; uint32_t* blk_work; uint32_t* blk_cnt; size_t blk_cap; int blk_phase;
+    DfDevBuf<uint8_t> blk_state; DfDevBuf<float> blk_wmax; DfDevBuf<uint8_t> blk_alive; DfDevBuf<uint32_t> blk_work, blk_cnt; size_t blk_cap = 0; int blk_phase = 0;
     // blk_tie [block] 1 = the block's table build met two exactly equidistant candidates (topk_insert's tie branch): its table depends on
     // the tie tree, and a rebuilt tree (dfusion_warp_extend) may reorder them anywhere
-    uint8_t* blk_tie;
-    uint16_t* bm_idx; uint32_t* bm_lam; uint32_t* bm_w; uint8_t* bm_cnt; size_t bm_cap;
+    DfDevBuf<uint8_t> blk_tie;
+    DfDevBuf<uint16_t> bm_idx; DfDevBuf<uint32_t> bm_lam, bm_w; DfDevBuf<uint8_t> bm_cnt; size_t bm_cap = 0;
     // 4-bit neighbour codes (round 5; round 6: per 4 x 4 x 4 SUB-block, so that they exist at any node density): per voxel of a block
     // the model pass has visited, its k neighbours as positions in the union list of its sub-block (ascending node ids, <= 16).
     //   bm_ids   [block][64] u32: entry q * 16 + e = union entry e of column quadrant q (x >> 2 & 1 | (y >> 2 & 1) << 1), low half
     //            word for planes 0-3 of the block, high half word for planes 4-7 -- the dword a sweep lane loads to refill its wave's copies
     //   bm_coded [block] 1 = every sub-block's union fits 16 entries and the codes are written
     //   code_tab one u32 per voxel, tile-major like the tables but PATCH-major inside a tile plane
-    uint32_t* code_tab; size_t code_cap; uint32_t* bm_ids; uint8_t* bm_coded;
-    bool tab_complete;           // every block's tables are built
-    int tab_sweeps;              // sweeps over the current tables so far (the models are made from the second one on)
-    unsigned long long* dbg_swept;   // dfusion_warp_debug_counters: nullable device counter the sweeps through this handle add to
-    bool alive_valid;            // blk_alive holds the verdicts of a sweep over the current tables (dfusion_warp_alive_blocks)
+    DfDevBuf<uint32_t> code_tab; size_t code_cap = 0; DfDevBuf<uint32_t> bm_ids; DfDevBuf<uint8_t> bm_coded;
+    bool tab_complete = false;   // every block's tables are built
+    int tab_sweeps = 0;          // sweeps over the current tables so far (the models are made from the second one on)
+    unsigned long long* dbg_swept = nullptr;   // dfusion_warp_debug_counters: nullable device counter (the caller's) the sweeps through this handle add to
+    bool alive_valid = false;    // blk_alive holds the verdicts of a sweep over the current tables (dfusion_warp_alive_blocks)
     // look-ahead work (tables / models of blocks a sweep does not need yet) runs on a side stream the handle owns, beside the sweep on
     // the caller's stream: ev_fork (caller's stream, after the verdict pass) releases it, ev_join (side stream, after its last kernel)
     // is waited for by the next call that touches the tables
-    hipStream_t side; hipEvent_t ev_fork, ev_join; bool side_pending;
+    hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool side_pending = false;
     // the verdict pass's list lengths, reported to pinned host memory by the plan kernel ([0] urgent builds, [1] models, [2] look-ahead
     // builds, [3] sweep number): read WITHOUT synchronisation by a later call -- a hint whether on-demand work is going on (then the side
     // stream is worth its fork / join, ~13 us per frame), never a condition of correctness
-    volatile uint32_t* host_report;
-    void* ext_ws; size_t ext_ws_cap;   // scratch of dfusion_warp_extend (grown on demand)
-    void* grow_ws; size_t grow_ws_cap; // df_warp_grow: the brick lists before the update (grown on demand)
+    volatile uint32_t* host_report = nullptr;
+    DfDevBuf<char> ext_ws;             // scratch of dfusion_warp_extend (grown on demand)
+    DfDevBuf<char> grow_ws;            // df_warp_grow: the brick lists before the update (grown on demand)
 };
 
 // Appends to the node set without dropping what still holds (dfusion_warp.hip; used by dfusion_warp_extend): the handle takes the grown

@@ -334,15 +334,6 @@ __global__ __launch_bounds__(256) void df_sv_writeback_kernel(const float4* __re
     o[0] = r.w; o[1] = r.x; o[2] = r.y; o[3] = r.z; o[4] = d.w; o[5] = d.x; o[6] = d.y; o[7] = d.z;
 }
 
-static int sv_reserve(DfWarpField* wf, size_t bytes)
-{
-    if (bytes <= wf->solver_ws_cap) return DF_OK;
-    (void)hipFree(wf->solver_ws); wf->solver_ws = nullptr; wf->solver_ws_cap = 0;
-    DF_HIP(hipMalloc(&wf->solver_ws, bytes));
-    wf->solver_ws_cap = bytes;
-    return DF_OK;
-}
-
 extern "C" int dfusion_warp_solve_data_term(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda,
                                             float* dq_out, float* energy, dfStream stream)
 {
@@ -362,9 +353,9 @@ extern "C" int dfusion_warp_solve_data_term(DfWarpField* wf, int k, const float*
     DF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned int*)nullptr, (unsigned int*)nullptr, (const unsigned int*)nullptr,
                                               (unsigned int*)nullptr, (int)E, 0, 17, st));
     const size_t o_sort = take(sort_bytes);
-    int rc = sv_reserve(wf, off);
+    int rc = wf->solver_ws.reserve(off);
     if (rc) return rc;
-    char* ws = (char*)wf->solver_ws;
+    char* ws = wf->solver_ws;
     int* idx = (int*)(ws + o_idx); float* d2 = (float*)(ws + o_d2); float* w = (float*)(ws + o_w);
     unsigned int* keys = (unsigned int*)(ws + o_keys); unsigned int* vals = (unsigned int*)(ws + o_vals);
     unsigned int* skeys = (unsigned int*)(ws + o_skeys); unsigned int* svals = (unsigned int*)(ws + o_svals);

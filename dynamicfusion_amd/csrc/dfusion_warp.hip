@@ -80,7 +80,7 @@ extern "C" int dfusion_warp_create(DfWarpField** out)
     if (!out) return DF_E_INVALID;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return DF_E_NO_DEVICE;
-    DfWarpField* wf = (DfWarpField*)calloc(1, sizeof(DfWarpField));
+    DfWarpField* wf = new (std::nothrow) DfWarpField();
     if (!wf) return DF_E_INVALID;
     wf->device = dev;
     *out = wf;
@@ -127,7 +127,6 @@ static void df_side_drain(DfWarpField* wf)
     wf->side_pending = false;
 }
 
-static void df_prep_free(DfWarpField* wf);       // (defined with the sweep's argument structs below)
 // A sweep issued through dfusion_integrate_warped_sweep may still be reading the node arrays, the launch plan and the verdict bytes on ITS
 // stream when the next frame's set_transforms / prepare arrive on another one: they wait for it on the device.
 static int df_wait_split_sweep(DfWarpField* wf, hipStream_t st)            // every sweep recorded so far
@@ -155,21 +154,8 @@ extern "C" int dfusion_warp_destroy(DfWarpField* wf)
     df_side_drain(wf);
     if (wf->side) { (void)hipEventDestroy(wf->ev_fork); (void)hipEventDestroy(wf->ev_join); (void)hipStreamDestroy(wf->side); }
     if (wf->split_events) { (void)hipEventDestroy(wf->ev_prep_done); (void)hipEventDestroy(wf->ev_sweep_done[0]); (void)hipEventDestroy(wf->ev_sweep_done[1]); }
-    (void)hipFree(wf->rot_alt); (void)hipFree(wf->dual_alt); (void)hipFree(wf->node_t_alt); (void)hipFree(wf->rt); (void)hipFree(wf->rt_alt);
-    (void)hipFree(wf->plan_mask2[1]); (void)hipFree(wf->plan_list2[1]); (void)hipFree(wf->plan_code2[0]); (void)hipFree(wf->plan_code2[1]);
-    df_prep_free(wf);
     if (wf->host_report) (void)hipHostFree((void*)wf->host_report);
-    (void)hipFree(wf->pos_sigma); (void)hipFree(wf->rot); (void)hipFree(wf->dual); (void)hipFree(wf->node_t);
-    (void)hipFree(wf->brick_off); (void)hipFree(wf->brick_cnt); (void)hipFree(wf->brick_list); (void)hipFree(wf->bounds_dev); (void)hipFree(wf->brick_thr);
-    (void)hipFree(wf->knn_tab); (void)hipFree(wf->w_tab); (void)hipFree(wf->solver_ws); (void)hipFree(wf->pt_ids); (void)hipFree(wf->tile_wmax);
-    (void)hipFree(wf->bm_idx); (void)hipFree(wf->bm_lam); (void)hipFree(wf->bm_w); (void)hipFree(wf->bm_cnt);
-    (void)hipFree(wf->code_tab); (void)hipFree(wf->bm_ids); (void)hipFree(wf->bm_coded);
-    (void)hipFree(wf->scan_tmp);
-    (void)hipFree(wf->blk_state); (void)hipFree(wf->blk_wmax); (void)hipFree(wf->blk_alive); (void)hipFree(wf->blk_work); (void)hipFree(wf->blk_cnt);
-    (void)hipFree(wf->blk_tie); (void)hipFree(wf->ext_ws); (void)hipFree(wf->grow_ws);
-    (void)hipFree(wf->nf_nodes); (void)hipFree(wf->nf_vpos); (void)hipFree(wf->pyr_mem);
-    (void)hipFree(wf->plan_mask); (void)hipFree(wf->plan_list); (void)hipFree(wf->plan_hist);
-    free(wf);
+    delete wf;
     return DF_OK;
 }
 
@@ -182,22 +168,19 @@ static int df_warp_reserve(DfWarpField* wf, int M)
 {
     if (M <= wf->cap) return DF_OK;
     { int rc = df_wait_all_sweeps_host(wf); if (rc) return rc; }        // (a split sweep may still read what is freed here)
-    (void)hipFree(wf->pos_sigma); (void)hipFree(wf->rot); (void)hipFree(wf->dual); (void)hipFree(wf->node_t);
-    (void)hipFree(wf->rot_alt); (void)hipFree(wf->dual_alt); (void)hipFree(wf->node_t_alt); (void)hipFree(wf->rt); (void)hipFree(wf->rt_alt);
-    wf->pos_sigma = wf->rot = wf->dual = wf->node_t = wf->rot_alt = wf->dual_alt = wf->node_t_alt = wf->rt = wf->rt_alt = nullptr; wf->cap = 0;
+    wf->cap = 0;
     wf->prep_valid = false;                                               // (a prepared plan points into the arrays freed here)
-    size_t bytes = (size_t)M * sizeof(float4);
-    DF_HIP(hipMalloc((void**)&wf->pos_sigma, bytes));
-    DF_HIP(hipMalloc((void**)&wf->rot, bytes));
-    DF_HIP(hipMalloc((void**)&wf->dual, bytes));
-    DF_HIP(hipMalloc((void**)&wf->node_t, bytes));
-    DF_HIP(hipMalloc((void**)&wf->rot_alt, bytes));                       // (the alternate set the next set_transforms writes)
-    DF_HIP(hipMalloc((void**)&wf->dual_alt, bytes));
-    DF_HIP(hipMalloc((void**)&wf->node_t_alt, bytes));
-    DF_HIP(hipMalloc((void**)&wf->rt, 2 * bytes));
-    DF_HIP(hipMalloc((void**)&wf->rt_alt, 2 * bytes));
+    { int rc = wf->pos_sigma.reserve((size_t)M); if (rc) return rc; }
+    { int rc = wf->rot.reserve((size_t)M); if (rc) return rc; }
+    { int rc = wf->dual.reserve((size_t)M); if (rc) return rc; }
+    { int rc = wf->node_t.reserve((size_t)M); if (rc) return rc; }
+    { int rc = wf->rot_alt.reserve((size_t)M); if (rc) return rc; }       // (the alternate set the next set_transforms writes)
+    { int rc = wf->dual_alt.reserve((size_t)M); if (rc) return rc; }
+    { int rc = wf->node_t_alt.reserve((size_t)M); if (rc) return rc; }
+    { int rc = wf->rt.reserve(2 * (size_t)M); if (rc) return rc; }
+    { int rc = wf->rt_alt.reserve(2 * (size_t)M); if (rc) return rc; }
     wf->node_reader[0] = wf->node_reader[1] = 0;
-    if (!wf->bounds_dev) { DF_HIP(hipMalloc((void**)&wf->bounds_dev, 8 * sizeof(float))); DF_HIP(hipMemset(wf->bounds_dev, 0, 8 * sizeof(float))); }   // ([6]: the capped pyramid's image-wide maximum, 0 between frames)
+    if (!wf->bounds_dev) { int rc = wf->bounds_dev.reserve(8); if (rc) return rc; DF_HIP(hipMemset(wf->bounds_dev, 0, 8 * sizeof(float))); }   // ([6]: the capped pyramid's image-wide maximum, 0 between frames)
     wf->cap = M;
     return DF_OK;
 }
@@ -301,16 +284,8 @@ static int df_warp_build_tie_tree(DfWarpField* wf, hipStream_t st)
     for (size_t i = 0; i < (size_t)M * 4; ++i) if ((i & 3) != 3 && !(host[i] == host[i])) return DF_OK;     // NaN position: no tree
     DfNfBuild B;
     B.build(host.data(), M);
-    if (B.nodes.size() > wf->nf_nodes_cap) {
-        (void)hipFree(wf->nf_nodes); wf->nf_nodes = nullptr; wf->nf_nodes_cap = 0;
-        DF_HIP(hipMalloc((void**)&wf->nf_nodes, B.nodes.size() * sizeof(DfNfNode)));
-        wf->nf_nodes_cap = B.nodes.size();
-    }
-    if ((size_t)M > wf->nf_vpos_cap) {
-        (void)hipFree(wf->nf_vpos); wf->nf_vpos = nullptr; wf->nf_vpos_cap = 0;
-        DF_HIP(hipMalloc((void**)&wf->nf_vpos, (size_t)M * sizeof(uint16_t)));
-        wf->nf_vpos_cap = (size_t)M;
-    }
+    { int rc = wf->nf_nodes.reserve(B.nodes.size()); if (rc) return rc; }
+    { int rc = wf->nf_vpos.reserve((size_t)M); if (rc) return rc; }
     std::vector<uint16_t> vpos((size_t)M);
     for (int i = 0; i < M; ++i) vpos[B.vind[i]] = (uint16_t)i;
     DF_HIP(hipMemcpyAsync(wf->nf_nodes, B.nodes.data(), B.nodes.size() * sizeof(DfNfNode), hipMemcpyHostToDevice, st));
@@ -736,11 +711,7 @@ extern "C" int dfusion_warp_index_info(const DfWarpField* wf, unsigned long long
 // [0] = count, [1..] = ids of the points the indexed pass left to the scan; zeroed per call
 static int df_point_fallback_reserve(DfWarpField* wf, int N, hipStream_t st)
 {
-    if ((size_t)N + 1 > wf->pt_ids_cap) {
-        (void)hipFree(wf->pt_ids); wf->pt_ids = nullptr; wf->pt_ids_cap = 0;
-        DF_HIP(hipMalloc((void**)&wf->pt_ids, ((size_t)N + 1) * sizeof(int)));
-        wf->pt_ids_cap = (size_t)N + 1;
-    }
+    { int rc = wf->pt_ids.reserve((size_t)N + 1); if (rc) return rc; }
     DF_HIP(hipMemsetAsync(wf->pt_ids, 0, sizeof(int), st));
     return DF_OK;
 }
@@ -1036,11 +1007,10 @@ static int df_index_bricks(DfWarpField* wf, const DfVolume& v, const float vol2w
     }
     const size_t nb = (size_t)g.bx * g.by * g.bz;
     if (nb + 1 > wf->off_cap) {
-        (void)hipFree(wf->brick_off); (void)hipFree(wf->brick_cnt); wf->brick_off = wf->brick_cnt = nullptr; wf->off_cap = 0;
-        DF_HIP(hipMalloc((void**)&wf->brick_off, (nb + 1) * sizeof(uint32_t)));
-        DF_HIP(hipMalloc((void**)&wf->brick_cnt, (nb + 1) * sizeof(uint32_t)));
-        (void)hipFree(wf->brick_thr); wf->brick_thr = nullptr;
-        DF_HIP(hipMalloc((void**)&wf->brick_thr, 2 * (nb + 1) * sizeof(float)));     // [nb + 1] list radii, then [nb + 1] nearest-node distances
+        wf->off_cap = 0;
+        { int rc = wf->brick_off.reserve(nb + 1); if (rc) return rc; }
+        { int rc = wf->brick_cnt.reserve(nb + 1); if (rc) return rc; }
+        { int rc = wf->brick_thr.reserve(2 * (nb + 1)); if (rc) return rc; }     // [nb + 1] list radii, then [nb + 1] nearest-node distances
         wf->off_cap = nb + 1;
     }
     // (one workgroup per 4 x 4 x 4 bricks; df_brick_index_kernel, one wave per brick over all M nodes, makes the same lists)
@@ -1065,8 +1035,8 @@ static int df_index_bricks(DfWarpField* wf, const DfVolume& v, const float vol2w
     {   // exclusive scan of the counts: tile sums, a one-workgroup scan of those, then the tiles (388 us -> 3 short launches at 512^3)
         const int ntile = (int)((nb + DF_SCAN_TILE - 1) / DF_SCAN_TILE);
         if ((size_t)ntile + 1 > wf->scan_cap) {
-            (void)hipFree(wf->scan_tmp); wf->scan_tmp = nullptr; wf->scan_cap = 0;
-            DF_HIP(hipMalloc((void**)&wf->scan_tmp, 2 * ((size_t)ntile + 1) * sizeof(uint32_t)));
+            wf->scan_cap = 0;
+            { int rc = wf->scan_tmp.reserve(2 * ((size_t)ntile + 1)); if (rc) return rc; }
             wf->scan_cap = (size_t)ntile + 1;
         }
         uint32_t* sums = wf->scan_tmp; uint32_t* sums_off = wf->scan_tmp + wf->scan_cap;
@@ -1078,12 +1048,7 @@ static int df_index_bricks(DfWarpField* wf, const DfVolume& v, const float vol2w
     uint32_t total = 0;
     DF_HIP(hipMemcpyAsync(&total, wf->brick_off + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DF_HIP(hipStreamSynchronize(st));
-    if ((size_t)total > wf->list_cap) {
-        (void)hipFree(wf->brick_list); wf->brick_list = nullptr; wf->list_cap = 0;
-        size_t cap = (size_t)total + (size_t)total / 8 + 1024;
-        DF_HIP(hipMalloc((void**)&wf->brick_list, cap * sizeof(uint16_t)));
-        wf->list_cap = cap;
-    }
+    if ((size_t)total > wf->brick_list.cap) { int rc = wf->brick_list.reserve((size_t)total + (size_t)total / 8 + 1024); if (rc) return rc; }
     DF_DISPATCH_K(k, df_brick_index_super_kernel<K, true><<<grid, dim3(256), 0, st>>>(wf->pos_sigma, wf->M, g, super_d, (uint32_t*)nullptr,
                                                                                       (const uint32_t*)wf->brick_off, wf->brick_list, wf->brick_thr,
                                                                                       (float*)nullptr));
@@ -2434,21 +2399,19 @@ static int df_block_verdicts(DfWarpField* wf, DfWarpedArgs& a, int k, unsigned f
     const bool use_models = !(flags & DF_WARP_NO_BLOCK_MODEL) && (k == 8 || k == 4);
     const int want_models = !use_models ? 0 : (flags & DF_WARP_BLOCK_MODEL_NOW) ? 2 : wf->tab_sweeps >= 1 ? 1 : 0;
     if (want_models && nblk > wf->bm_cap) {
-        (void)hipFree(wf->bm_idx); (void)hipFree(wf->bm_lam); (void)hipFree(wf->bm_w); (void)hipFree(wf->bm_cnt);
-        wf->bm_idx = nullptr; wf->bm_lam = nullptr; wf->bm_w = nullptr; wf->bm_cnt = nullptr; wf->bm_cap = 0;
-        DF_HIP(hipMalloc((void**)&wf->bm_idx, nblk * DF_BM_NU * sizeof(uint16_t)));
-        DF_HIP(hipMalloc((void**)&wf->bm_lam, nblk * DF_BM_NU * sizeof(uint32_t)));
-        DF_HIP(hipMalloc((void**)&wf->bm_w, nblk * DF_BM_NU * sizeof(uint32_t)));
-        DF_HIP(hipMalloc((void**)&wf->bm_cnt, nblk));
+        wf->bm_cap = 0;
+        { int rc = wf->bm_idx.reserve(nblk * DF_BM_NU); if (rc) return rc; }
+        { int rc = wf->bm_lam.reserve(nblk * DF_BM_NU); if (rc) return rc; }
+        { int rc = wf->bm_w.reserve(nblk * DF_BM_NU); if (rc) return rc; }
+        { int rc = wf->bm_cnt.reserve(nblk); if (rc) return rc; }
         wf->bm_cap = nblk;
     }
     // 4-bit neighbour codes + the sub-blocks' union lists (the sweep reads them at k = 8 only: no 4 bytes a voxel for the others)
     if (want_models && k == 8 && (nblk * 512 > wf->code_cap || !wf->bm_ids || !wf->code_tab || !wf->bm_coded)) {
-        (void)hipFree(wf->bm_ids); (void)hipFree(wf->code_tab); (void)hipFree(wf->bm_coded);
-        wf->bm_ids = nullptr; wf->code_tab = nullptr; wf->bm_coded = nullptr; wf->code_cap = 0;
-        DF_HIP(hipMalloc((void**)&wf->bm_ids, nblk * 64 * sizeof(uint32_t)));
-        DF_HIP(hipMalloc((void**)&wf->code_tab, nblk * 512 * sizeof(uint32_t)));
-        DF_HIP(hipMalloc((void**)&wf->bm_coded, nblk));
+        wf->code_cap = 0;
+        { int rc = wf->bm_ids.reserve(nblk * 64); if (rc) return rc; }
+        { int rc = wf->code_tab.reserve(nblk * 512); if (rc) return rc; }
+        { int rc = wf->bm_coded.reserve(nblk); if (rc) return rc; }
         DF_HIP(hipMemsetAsync(wf->bm_coded, 0, nblk, st));
         wf->code_cap = nblk * 512;
     }
@@ -2533,7 +2496,8 @@ static int df_block_verdicts(DfWarpField* wf, DfWarpedArgs& a, int k, unsigned f
 // The launch state dfusion_integrate_warped_prepare leaves for dfusion_integrate_warped_sweep
 typedef void (*df_lds_kernel_t)(const DfWarpedArgs, const DfWarpView, int);
 struct DfPrepared { DfWarpedArgs a; DfWarpView W; df_lds_kernel_t kern; dim3 grid; unsigned threads; size_t lds; int tiles_x; DfVolume v; DfSlab s; unsigned long long seq; };
-static void df_prep_free(DfWarpField* wf) { delete (DfPrepared*)wf->prep; wf->prep = nullptr; wf->prep_valid = false; }
+DfWarpField::DfWarpField() = default;
+DfWarpField::~DfWarpField() = default;
 enum { DF_MODE_WHOLE = 0, DF_MODE_PREPARE = 1 };
 
 static int df_integrate_warped_impl(const uint16_t* dists, size_t pitch, int cols, int rows, DfVolume v, const DfSlab* slab,
@@ -2577,7 +2541,7 @@ extern "C" int dfusion_integrate_warped_sweep(DfVolume v, const DfSlab* slab, Df
     const DfSlab s = df_slab_or_full(v, slab);
     if (!df_slab_valid(v, s)) return DF_E_INVALID;
     if (s.z_own_n == 0) return DF_OK;                                // (as dfusion_integrate_warped: nothing to sweep, nothing was prepared)
-    DfPrepared* P = (DfPrepared*)wf->prep;
+    DfPrepared* P = wf->prep.get();
     if (!P || !wf->prep_valid) return DF_E_INVALID;                  // no prepare call pending on this handle
     if (memcmp(P->v.dims, v.dims, sizeof(v.dims)) || memcmp(P->v.voxel_size, v.voxel_size, sizeof(v.voxel_size)) || P->v.trunc_dist != v.trunc_dist ||
         P->v.max_weight != v.max_weight || memcmp(&P->s, &s, sizeof(s))) return DF_E_INVALID;       // not the volume the plan was made for
@@ -2652,11 +2616,7 @@ static int df_integrate_warped_impl(const uint16_t* dists, size_t pitch, int col
     if (!(flags & DF_WARP_NO_CULL) && proj[0] > 0.f && proj[1] > 0.f) {
         if (!(flags & DF_WARP_NO_DEPTH_PYRAMID)) {
             const size_t elems = df_pyramid_elems(cols, rows);
-            if (elems > wf->pyr_cap) {
-                (void)hipFree(wf->pyr_mem); wf->pyr_mem = nullptr; wf->pyr_cap = 0;
-                DF_HIP(hipMalloc((void**)&wf->pyr_mem, elems * sizeof(uint16_t)));
-                wf->pyr_cap = elems;
-            }
+            { int rc = wf->pyr_mem.reserve(elems); if (rc) return rc; }
             // the pipelined sweep (the product path) reads the pyramid in its verdict pass only, and its plan kernel re-arms the
             // image-maximum word: levels 1..5 in ONE launch.  The other kernels take the full pyramid (two launches).
             const bool pipe_path = pipe_sweep;
@@ -2665,7 +2625,7 @@ static int df_integrate_warped_impl(const uint16_t* dists, size_t pitch, int col
             // one (zeroed by the plan kernel before), and that call's plan kernel cleans both (no memset node per frame).
             wf->max_phase ^= 1;
             unsigned int* max_word = (unsigned int*)(wf->bounds_dev + 6 + wf->max_phase);
-            int rc = df_build_dists_pyramid(dists, pitch, cols, rows, wf->pyr_mem, wf->pyr_cap, &a.py, st, pipe_path, nullptr,
+            int rc = df_build_dists_pyramid(dists, pitch, cols, rows, wf->pyr_mem, wf->pyr_mem.cap, &a.py, st, pipe_path, nullptr,
                                             pipe_path ? max_word : nullptr);
             if (rc) return rc;
         }
@@ -2746,21 +2706,16 @@ static int df_integrate_warped_impl(const uint16_t* dists, size_t pitch, int col
             // the plan after next: a sweep issued through the split API may still be reading its plan while the next frame's is made.
             if (n_items > wf->plan_cap) {
                 { int rc = df_wait_all_sweeps_host(wf); if (rc) return rc; }
+                wf->plan_cap = 0;
                 for (int i = 0; i < 2; ++i) {
-                    (void)hipFree(wf->plan_mask2[i]); (void)hipFree(wf->plan_list2[i]); wf->plan_mask2[i] = nullptr; wf->plan_list2[i] = nullptr;
-                    (void)hipFree(wf->plan_code2[i]); wf->plan_code2[i] = nullptr;
+                    { int rc = wf->plan_mask2[i].reserve(n_items); if (rc) return rc; }
+                    { int rc = wf->plan_list2[i].reserve((size_t)n_items * DF_PLAN_BINS); if (rc) return rc; }      // the bins
+                    { int rc = wf->plan_code2[i].reserve(n_items); if (rc) return rc; }
                 }
-                wf->plan_cap = 0; wf->plan_mask = nullptr; wf->plan_list = nullptr;
-                for (int i = 0; i < 2; ++i) {
-                    DF_HIP(hipMalloc((void**)&wf->plan_mask2[i], (size_t)n_items * sizeof(unsigned long long)));
-                    DF_HIP(hipMalloc((void**)&wf->plan_list2[i], (size_t)n_items * DF_PLAN_BINS * sizeof(unsigned int)));      // the bins
-                    DF_HIP(hipMalloc((void**)&wf->plan_code2[i], (size_t)n_items * sizeof(unsigned long long)));
-                }
-                wf->plan_mask = wf->plan_mask2[0]; wf->plan_list = wf->plan_list2[0];       // (the names the destructor frees)
                 wf->plan_cap = n_items; wf->plan_reader[0] = wf->plan_reader[1] = 0;
             }
             if (!wf->plan_hist) {
-                DF_HIP(hipMalloc((void**)&wf->plan_hist, 4 * 128 * sizeof(unsigned int)));
+                { int rc = wf->plan_hist.reserve(4 * 128); if (rc) return rc; }
                 DF_HIP(hipMemsetAsync(wf->plan_hist, 0, 4 * 128 * sizeof(unsigned int), st));
                 wf->hphase = 0;
             }
@@ -2811,8 +2766,8 @@ static int df_integrate_warped_impl(const uint16_t* dists, size_t pitch, int col
         }
         if (mode == DF_MODE_PREPARE) {
             if (!pipe) return DF_E_INVALID;                                // (the split exists for the cached, pipelined sweep only)
-            if (!wf->prep) wf->prep = new DfPrepared();
-            DfPrepared* P = (DfPrepared*)wf->prep;
+            if (!wf->prep) wf->prep.reset(new DfPrepared());
+            DfPrepared* P = wf->prep.get();
             P->a = a; P->W = W; P->kern = kern; P->grid = grid; P->threads = wg_threads; P->lds = lds; P->tiles_x = tiles_x; P->v = v; P->s = s;
             P->seq = wf->seq;
             wf->prep_valid = true;
@@ -2858,37 +2813,24 @@ static int df_build_voxel_table(DfWarpField* wf, const DfVolume& v, const DfSlab
     if (ntx * (DF_TAB_TX / 8) > 1023 || nty * (DF_TAB_TY / 8) > 1023 || bz_hi > 4095) return DF_E_INVALID;    // packed brick coordinates of the work lists
     const size_t nvox = (size_t)ntx * DF_TAB_TX * nty * DF_TAB_TY * tzn;          // padded to whole tiles
     const size_t need = nvox * k;
-    if (need > wf->knn_tab_cap) {
-        (void)hipFree(wf->knn_tab); wf->knn_tab = nullptr; wf->knn_tab_cap = 0;
-        DF_HIP(hipMalloc((void**)&wf->knn_tab, need * sizeof(uint16_t)));
-        wf->knn_tab_cap = need;
-    }
-    if (weights && need > wf->w_tab_cap) {
-        (void)hipFree(wf->w_tab); wf->w_tab = nullptr; wf->w_tab_cap = 0;
-        DF_HIP(hipMalloc((void**)&wf->w_tab, need * sizeof(float)));
-        wf->w_tab_cap = need;
-    }
+    { int rc = wf->knn_tab.reserve(need); if (rc) return rc; }
+    if (weights) { int rc = wf->w_tab.reserve(need); if (rc) return rc; }
     const size_t ntile = (size_t)ntx * nty * (tzn / DF_TAB_TZ);
     if (weights) {
-        if (ntile > wf->tile_wmax_cap) {
-            (void)hipFree(wf->tile_wmax); wf->tile_wmax = nullptr; wf->tile_wmax_cap = 0;
-            DF_HIP(hipMalloc((void**)&wf->tile_wmax, ntile * sizeof(float)));
-            wf->tile_wmax_cap = ntile;
-        }
+        { int rc = wf->tile_wmax.reserve(ntile); if (rc) return rc; }
         DF_HIP(hipMemsetAsync(wf->tile_wmax, 0, ntile * sizeof(float), st));
     }
     const size_t nblk = (size_t)ntx * (DF_TAB_TX / 8) * nty * (DF_TAB_TY / 8) * (tzn / 8);
     if (nblk > wf->blk_cap) {
-        (void)hipFree(wf->blk_state); (void)hipFree(wf->blk_wmax); (void)hipFree(wf->blk_alive); (void)hipFree(wf->blk_work); (void)hipFree(wf->blk_tie);
-        wf->blk_state = nullptr; wf->blk_wmax = nullptr; wf->blk_alive = nullptr; wf->blk_work = nullptr; wf->blk_tie = nullptr; wf->blk_cap = 0;
-        DF_HIP(hipMalloc((void**)&wf->blk_state, nblk));
-        DF_HIP(hipMalloc((void**)&wf->blk_tie, nblk));
-        DF_HIP(hipMalloc((void**)&wf->blk_wmax, nblk * sizeof(float)));
-        DF_HIP(hipMalloc((void**)&wf->blk_alive, nblk));
-        DF_HIP(hipMalloc((void**)&wf->blk_work, 3 * nblk * sizeof(uint32_t)));
+        wf->blk_cap = 0;
+        { int rc = wf->blk_state.reserve(nblk); if (rc) return rc; }
+        { int rc = wf->blk_tie.reserve(nblk); if (rc) return rc; }
+        { int rc = wf->blk_wmax.reserve(nblk); if (rc) return rc; }
+        { int rc = wf->blk_alive.reserve(nblk); if (rc) return rc; }
+        { int rc = wf->blk_work.reserve(3 * nblk); if (rc) return rc; }
         wf->blk_cap = nblk;
     }
-    if (!wf->blk_cnt) DF_HIP(hipMalloc((void**)&wf->blk_cnt, 16 * sizeof(uint32_t)));
+    { int rc = wf->blk_cnt.reserve(16); if (rc) return rc; }
     DF_HIP(hipMemsetAsync(wf->blk_cnt, 0, 16 * sizeof(uint32_t), st));
     DF_HIP(hipMemsetAsync(wf->blk_state, on_demand ? 0 : 1, nblk, st));
     DF_HIP(hipMemsetAsync(wf->blk_tie, 0, nblk, st));
@@ -2954,15 +2896,11 @@ int df_warp_grow(DfWarpField* wf, const float* pos, const float* dq, const float
     const bool tabs = wf->tab_valid && wf->blk_state && wf->blk_tie;
     uint32_t* old_off = nullptr; uint16_t* old_list = nullptr;
     if (tabs) {                                                // the lists before the update, to find the bricks whose list changes
-        const size_t off_bytes = ((nb + 1) * sizeof(uint32_t) + 255) & ~(size_t)255, need = off_bytes + wf->list_cap * sizeof(uint16_t);
-        if (need > wf->grow_ws_cap) {
-            (void)hipFree(wf->grow_ws); wf->grow_ws = nullptr; wf->grow_ws_cap = 0;
-            DF_HIP(hipMalloc(&wf->grow_ws, need));
-            wf->grow_ws_cap = need;
-        }
-        old_off = (uint32_t*)wf->grow_ws; old_list = (uint16_t*)((char*)wf->grow_ws + off_bytes);
+        const size_t off_bytes = ((nb + 1) * sizeof(uint32_t) + 255) & ~(size_t)255, need = off_bytes + wf->brick_list.cap * sizeof(uint16_t);
+        { int rc = wf->grow_ws.reserve(need); if (rc) return rc; }
+        old_off = (uint32_t*)wf->grow_ws.p; old_list = (uint16_t*)(wf->grow_ws + off_bytes);
         DF_HIP(hipMemcpyAsync(old_off, wf->brick_off, (nb + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-        DF_HIP(hipMemcpyAsync(old_list, wf->brick_list, wf->list_cap * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
+        DF_HIP(hipMemcpyAsync(old_list, wf->brick_list, wf->brick_list.cap * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
     }
     wf->index_valid = false;                                   // (until the lists are re-made)
     DfVolume v; memset(&v, 0, sizeof(v));

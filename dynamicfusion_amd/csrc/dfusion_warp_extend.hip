@@ -180,13 +180,9 @@ static inline size_t df_ext_align(size_t x) { return (x + 255) & ~(size_t)255; }
 // the handle's extend scratch, grown when too small (kept between calls)
 static int df_ext_scratch(DfWarpField* wf, size_t bytes, char** out)
 {
-    if (bytes > wf->ext_ws_cap) {
-        (void)hipFree(wf->ext_ws); wf->ext_ws = nullptr; wf->ext_ws_cap = 0;
-        DF_HIP(hipMalloc(&wf->ext_ws, bytes));
-        wf->ext_ws_cap = bytes;
-    }
-    *out = (char*)wf->ext_ws;
-    return DF_OK;
+    int rc = wf->ext_ws.reserve(bytes);
+    *out = wf->ext_ws;
+    return rc;
 }
 
 extern "C" int dfusion_warp_extend(DfWarpField* wf, int k, const float* points, int N, float radius, float sigma_new, int max_new,
