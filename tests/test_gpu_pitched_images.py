@@ -12,6 +12,7 @@ import torch
 import oracle_lib as O
 from dynamicfusion_amd import Intr, capi, compute_dists, frontend, synth
 from frontend_ref import BILATERAL, level_intr, thresholds
+from nonrigid_loop import transform_ref as _transform_ref      # the numpy restatement of dfusion_transform_points
 from scene import Scene
 from test_gpu_parity import _filled, assert_volume_parity, make_gpu_volume, make_gpu_warp
 
@@ -220,15 +221,6 @@ def test_icp_pitched(cfg, variant):
 
 
 # ---------------------------------------------------------------------------------------------------------------- transform_points
-def _transform_ref(pts, aff):
-    """numpy float32 restatement: R(i,0)*x + R(i,1)*y + R(i,2)*z + t(i), products summed left to right."""
-    x, y, z = pts[..., 0], pts[..., 1], pts[..., 2]
-    if aff is None:
-        return np.stack([x, y, z], -1)
-    R, t = aff[:9].reshape(3, 3), aff[9:]
-    return np.stack([((R[i, 0] * x + R[i, 1] * y) + R[i, 2] * z) + t[i] for i in range(3)], -1).astype(F32)
-
-
 @pytest.mark.parametrize("rows,cols", [(117, 203), (1, 1000)], ids=["203x117", "rows1"])
 @pytest.mark.parametrize("sin,sout", [(3, 3), (4, 3), (3, 4)])
 @pytest.mark.parametrize("affine", [True, False], ids=["affine", "copy"])
