@@ -4,6 +4,7 @@ The .so is git-ignored but travels to the GPU box with the gpurun snapshot, so a
 the sources' mtimes changing never rebuilds.  hipcc cross-compiles without a GPU.
 """
 import os
+import re
 import shutil
 import subprocess
 
@@ -12,9 +13,10 @@ REPO_DIR = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libdfusion_hip.so")
 
-SOURCES = ["dfusion_volume.hip", "dfusion_warp.hip", "dfusion_raycast.hip", "dfusion_frontend.hip", "dfusion_solver.hip", "dfusion_selftest.hip",
-           "dfusion_warp_extend.hip"]
-HEADERS = ["dfusion_device.h", "dfusion_internal.h", "dfusion_nanoflann.h", "dfusion_pyramid.h", "dfusion_warp_blocks.h", os.path.join(REPO_DIR, "include", "dfusion.h")]
+SOURCES = ["dfusion_volume.hip", "dfusion_warp.hip", "dfusion_warp_nodes.hip", "dfusion_warp_points.hip", "dfusion_warp_index.hip",
+           "dfusion_raycast.hip", "dfusion_frontend.hip", "dfusion_solver.hip", "dfusion_selftest.hip", "dfusion_warp_extend.hip"]
+HEADERS = ["dfusion_device.h", "dfusion_internal.h", "dfusion_nanoflann.h", "dfusion_pyramid.h", "dfusion_warp_topk.h", "dfusion_warp_sweep.h",
+           "dfusion_warp_blocks.h", "dfusion_warp_pipe.h", os.path.join(REPO_DIR, "include", "dfusion.h")]
 
 # -ffp-contract=off: fused multiply-adds only where the reference writes __fmaf_rn (explicit fmaf);
 # that is what makes the kernels bit-comparable with the IEEE CPU oracle.
@@ -37,17 +39,31 @@ def _stale():
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _csrc_includes(name, seen):
+    """`name` and every csrc header it includes (transitively), each once, in include order."""
+    if name in seen:
+        return seen
+    seen.append(name)
+    for inc in re.findall(r'^#include "([^"]+)"', open(os.path.join(CSRC, name)).read(), re.M):
+        if os.path.exists(os.path.join(CSRC, inc)):
+            _csrc_includes(inc, seen)
+    return seen
+
+
 def kernel_source_sha(kernel):
-    """sha256 over the sources a kernel (by name) is built from: its .hip plus the device headers.  Stamps profiles/pmc_latest.json
-    (tools/pmc_summary.py); bench.py drops counters whose stamp is not the tree's."""
+    """sha256 over the sources a kernel (by name) is built from: the .hip that emits it and exactly the csrc headers that .hip includes.
+    Stamps profiles/pmc_latest.json (tools/pmc_summary.py); bench.py drops counters whose stamp is not the tree's."""
     import hashlib
     k = kernel.replace("void ", "")
-    f = ("dfusion_warp.hip" if k.startswith(("df_warp", "df_sweep", "df_block", "df_blocks", "df_brick", "df_scan", "df_pack", "df_node", "df_points"))
+    f = ("dfusion_warp_nodes.hip" if k.startswith(("df_pack", "df_node"))
+         else "dfusion_warp_points.hip" if k.startswith("df_points")
+         else "dfusion_warp_index.hip" if k.startswith(("df_brick", "df_scan", "df_grow"))
+         else "dfusion_warp.hip" if k.startswith(("df_warp", "df_sweep", "df_block", "df_blocks", "df_dists_max", "df_alive"))
          else "dfusion_raycast.hip" if k.startswith(("df_raycast", "df_extract"))
          else "dfusion_solver.hip" if k.startswith("df_sv")
          else "dfusion_volume.hip")
     h = hashlib.sha256()
-    for name in (f, "dfusion_warp_blocks.h", "dfusion_device.h", "dfusion_internal.h", "dfusion_pyramid.h"):
+    for name in _csrc_includes(f, []):
         h.update(open(os.path.join(CSRC, name), "rb").read())
     return h.hexdigest()
 

@@ -102,7 +102,7 @@ struct __attribute__((visibility("hidden"))) DfWarpField {     // (opaque in dfu
     DfDevBuf<float> bounds_dev;
     int max_phase = 0;                // which of bounds_dev[6], [7] this frame's capped pyramid leaves the image-wide maximum in
     // dfusion_integrate_warped_prepare / _sweep (round 5): the launch state a prepare call leaves for the sweep call (opaque here: the
-    // argument structs live in dfusion_warp.hip), and the two events that order the halves when they are issued on different streams
+    // argument structs live in dfusion_warp_sweep.h), and the two events that order the halves when they are issued on different streams
     std::unique_ptr<DfPrepared> prep; bool prep_valid = false;
     hipEvent_t ev_prep_done = nullptr, ev_sweep_done[2] = {}; bool split_events = false;
     // What a sweep issued through the split API may still be READING when the next frame's set_transforms / prepare arrive on another
@@ -162,7 +162,42 @@ struct __attribute__((visibility("hidden"))) DfWarpField {     // (opaque in dfu
     DfDevBuf<char> grow_ws;            // df_warp_grow: the brick lists before the update (grown on demand)
 };
 
-// Appends to the node set without dropping what still holds (dfusion_warp.hip; used by dfusion_warp_extend): the handle takes the grown
+#define DF_DISPATCH_K(k, ...)                             \
+    switch (k) {                                          \
+        case 1: { constexpr int K = 1; __VA_ARGS__; } break; \
+        case 2: { constexpr int K = 2; __VA_ARGS__; } break; \
+        case 3: { constexpr int K = 3; __VA_ARGS__; } break; \
+        case 4: { constexpr int K = 4; __VA_ARGS__; } break; \
+        case 5: { constexpr int K = 5; __VA_ARGS__; } break; \
+        case 6: { constexpr int K = 6; __VA_ARGS__; } break; \
+        case 7: { constexpr int K = 7; __VA_ARGS__; } break; \
+        case 8: { constexpr int K = 8; __VA_ARGS__; } break; \
+        default: return DF_E_INVALID;                     \
+    }
+
+// Host helpers of the warp field that one dfusion_warp*.hip translation unit defines and another calls (the library exports none of them).
+struct DfWarpedArgs;                           // (dfusion_warp_sweep.h)
+#define DF_LOCAL __attribute__((visibility("hidden")))
+// dfusion_warp_nodes.hip
+DF_LOCAL DfWarpView df_view(const DfWarpField* wf);
+DF_LOCAL int df_side_init(DfWarpField* wf);
+DF_LOCAL int df_side_join(DfWarpField* wf, hipStream_t st);
+DF_LOCAL void df_side_drain(DfWarpField* wf);
+DF_LOCAL int df_wait_split_sweep(DfWarpField* wf, hipStream_t st);
+DF_LOCAL int df_wait_reader(DfWarpField* wf, unsigned long long reader, hipStream_t st);
+DF_LOCAL int df_wait_all_sweeps_host(DfWarpField* wf);
+DF_LOCAL int df_warp_reserve(DfWarpField* wf, int M);
+DF_LOCAL int df_warp_pack_current(DfWarpField* wf, const float* pos, const float* dq, const float* sigma, hipStream_t st);
+DF_LOCAL int df_warp_build_tie_tree(DfWarpField* wf, hipStream_t st);
+// dfusion_warp_index.hip
+DF_LOCAL int df_index_bricks(DfWarpField* wf, const DfVolume& v, const float vol2world[12], int k, hipStream_t st);
+// dfusion_warp.hip
+DF_LOCAL DfWarpedArgs df_table_args(const DfWarpField* wf);
+DF_LOCAL int df_tables_complete(DfWarpField* wf, hipStream_t st);
+DF_LOCAL int df_build_voxel_table(DfWarpField* wf, const DfVolume& v, const DfSlab& s, const float vol2world[12], int k, bool weights,
+                                  bool on_demand, hipStream_t st);
+
+// Appends to the node set without dropping what still holds (dfusion_warp_index.hip; used by dfusion_warp_extend): the handle takes the grown
 // set pos/dq/sigma[Mn] (layout of dfusion_warp_set_nodes; the first M entries are the current nodes), and an index is brought up to date
 // for it in place -- the brick lists are re-made, and only the table blocks whose brick list changed or whose build met an exact
 // distance tie are marked unbuilt.  Blocks until done.

@@ -11,7 +11,7 @@
 // it never visits (pruned subtree) is strictly farther than the k-th, and a node arriving with a distance already in the
 // set goes behind it (strict `>` in addPoint, strict `<` against the leaf's worst distance).
 //
-// The k-NN kernels of dfusion_warp.hip rank candidates by distance; when (and only when) two distances are EQUAL they ask
+// The k-NN kernels (topk_insert, dfusion_warp_topk.h) rank candidates by distance; when (and only when) two distances are EQUAL they ask
 // df_nf_visited_before() which of the two nodes the reference's walk meets first.  That needs no search: the walk visits
 // the near child of every tree node first, so the order of two nodes is decided at the tree node where their root paths
 // part (by the query's side of that node's split, exactly searchLevel's `(diff1 + diff2) < 0`), or, inside one leaf, by

@@ -1,5 +1,5 @@
-// Block blend models: a second, much tighter conservative verdict for the warped sweep's launch plan (included by dfusion_warp.hip
-// after DfWarpedArgs / df_tab_index / the pyramid).
+// Block blend models: a second, much tighter conservative verdict for the warped sweep's launch plan (launched from dfusion_warp.hip;
+// DfWarpedArgs / df_tab_index / df_tile_culled / the pyramid come with dfusion_warp_sweep.h).
 //
 // df_tile_culled() bounds a block's warped positions by a ball around its UNWARPED centre whose radius is the largest motion any
 // node could cause (max angle x lever arm + k max|t|).  On the headline scene that ball keeps 57 % of the 8 x 8 x 8 blocks alive
@@ -29,6 +29,7 @@
 // (The sweep forms the translation as (0.5 tsum rn) * 2 conj(rn): its vector part is tsum's whatever tsum's scalar part, up to
 // rounding relative to |tsum| -- inside the inflation for any translation the volume could hold.)
 #pragma once
+#include "dfusion_warp_sweep.h"
 
 #define DF_BM_NU 16                 // entries per block model
 #define DF_BM_NONE 0xffu            // count byte: no model for this block

@@ -7,7 +7,7 @@
 //   * winners become nodes in increasing index order, at most min(max_new, 65535 - M) of them: vertex = p, dg_w = sigma_new,
 //     transform = WarpField::DQB(p) over the OLD node set (warp_field.cpp:203-217), or, when all k weights are 0, the transform of p's
 //     nearest node.
-// The handle then takes the grown set (df_warp_grow, dfusion_warp.hip): node arrays re-packed with headroom, tie tree re-made, brick lists
+// The handle then takes the grown set (df_warp_grow, dfusion_warp_index.hip): node arrays re-packed with headroom, tie tree re-made, brick lists
 // re-made, and only the table blocks whose brick list changed or whose build met an exact distance tie marked unbuilt -- every result
 // is what dfusion_warp_set_nodes + dfusion_warp_build_index make of the grown set on a fresh handle.
 //
@@ -252,7 +252,7 @@ extern "C" int dfusion_warp_extend(DfWarpField* wf, int k, const float* points, 
     if (new_pos) DF_HIP(hipMemcpyAsync(new_pos, gpos + 3 * (size_t)M, (size_t)n * 12, hipMemcpyDeviceToDevice, st));
     if (new_dq) DF_HIP(hipMemcpyAsync(new_dq, gdq + 8 * (size_t)M, (size_t)n * 32, hipMemcpyDeviceToDevice, st));
     if (new_sigma) DF_HIP(hipMemcpyAsync(new_sigma, gsig + M, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    // the handle takes the grown set; its index, if any, is updated in place (dfusion_warp.hip df_warp_grow).  Once the nodes are in,
+    // the handle takes the grown set; its index, if any, is updated in place (dfusion_warp_index.hip df_warp_grow).  Once the nodes are in,
     // *n_added reports them even if the index update then fails (the handle then has no index: DF_E_NO_INDEX until build_index)
     const int rc = df_warp_grow(wf, gpos, gdq, gsig, Mn, st);
     if (wf->M == Mn) *n_added = n;

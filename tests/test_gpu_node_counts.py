@@ -2,7 +2,7 @@
 
   * the data-term solve (dfusion_solver.hip): the CG step kernels df_sv_step_reg_kernel<2 / 5 / 8> and df_sv_step_kernel (M <= 2048,
     <= 5120, <= 8192, larger), W p with a compile-time k (4, 8) and with a run-time one (df_sv_w_apply_kernel<0>: every other k);
-  * node packing (dfusion_warp.hip df_warp_pack_current): the one-workgroup pack + bounds (M <= 8192) and the pack + atomic bounds
+  * node packing (dfusion_warp_nodes.hip df_warp_pack_current): the one-workgroup pack + bounds (M <= 8192) and the pack + atomic bounds
     (M > 8192) with the sigma bound forced to "unknown", switched both ways on one handle, and the cull built on those bounds;
   * the brick index's super-brick gather past its LDS list (DF_SUPER_CAP = 1024 candidates: every brick scans all M nodes);
   * 16-bit node ids up to 65 534 in the brick lists, the per-voxel tables, the tie tree and the block models;
@@ -18,7 +18,7 @@ from dynamicfusion_amd import Intr, TsdfVolume, WarpField, synth, upload_u16
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-SUPER_CAP = 1024                       # DF_SUPER_CAP, dfusion_warp.hip
+SUPER_CAP = 1024                       # DF_SUPER_CAP, dfusion_warp_index.hip
 
 
 def bits(a):

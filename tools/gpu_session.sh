@@ -38,7 +38,7 @@ echo "== probes: copy forms, RMW access patterns"
 hipcc --offload-arch=gfx950 -O3 tools/copy_probe.hip -o build/copy_probe 2>/dev/null; timeout 200 build/copy_probe > gpurun_out/${T}_copy_probe.txt 2>&1; grep "1 GiB" -A12 gpurun_out/${T}_copy_probe.txt | grep "chunk x4 nt\|stride x1 " | head -4
 hipcc --offload-arch=gfx950 -O3 tools/rmw_probe.hip -o build/rmw_probe 2>/dev/null; timeout 100 build/rmw_probe > gpurun_out/${T}_rmw_probe.txt 2>&1; head -13 gpurun_out/${T}_rmw_probe.txt
 echo "== per-wave timelines"
-python tools/build_variant.py trace --only dfusion_volume.hip,dfusion_warp.hip -DDF_TRACE_WG=1 > /dev/null
+python tools/build_variant.py trace --only dfusion_volume.hip,dfusion_warp.hip,dfusion_warp_index.hip -DDF_TRACE_WG=1 > /dev/null
 (timeout 300 python tools/trace_sweep.py 512 2>&1 | grep -v amdgpu.ids) > gpurun_out/${T}_trace_sweep_512.txt; head -2 gpurun_out/${T}_trace_sweep_512.txt
 (timeout 300 python tools/trace_sweep.py 512 rigid 2>&1 | grep -v amdgpu.ids) > gpurun_out/${T}_trace_rigid_512.txt; head -1 gpurun_out/${T}_trace_rigid_512.txt
 python tools/build_variant.py vtrace --only dfusion_warp.hip -DDF_TRACE_VERDICT=1 > /dev/null

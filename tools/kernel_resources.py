@@ -3,7 +3,8 @@
 import os, re, subprocess, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 srcs = sys.argv[1:] or [os.path.join(REPO, "dynamicfusion_amd", "csrc", f) for f in
-                        ("dfusion_volume.hip", "dfusion_warp.hip", "dfusion_raycast.hip")]
+                        ("dfusion_volume.hip", "dfusion_warp.hip", "dfusion_warp_nodes.hip", "dfusion_warp_points.hip", "dfusion_warp_index.hip",
+                         "dfusion_raycast.hip")]
 for src in srcs:
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
            "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "dynamicfusion_amd", "csrc"),

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Per-wave timeline of one warped-sweep launch: build/libdfusion_hip_trace.so (tools/build_variant.py trace -DDF_TRACE_WG=1) stamps
+"""Per-wave timeline of one warped-sweep launch: build/libdfusion_hip_trace.so (tools/build_variant.py trace -DDF_TRACE_WG=1, or with
+--only dfusion_volume.hip,dfusion_warp.hip,dfusion_warp_index.hip: the define adds a member to DfWarpedArgs, which the last two share) stamps
 every wave's start / end (s_memrealtime, 100 MHz), hardware id and alive-layer count; this writes gpurun_out/sweep_trace_<cfg>.npz and
 prints the slot occupancy over time."""
 import os, sys
