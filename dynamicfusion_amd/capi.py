@@ -60,7 +60,7 @@ SYMBOLS = [
     "dfusion_icp_workspace_floats", "dfusion_icp_sums_points", "dfusion_icp_sums_depth", "dfusion_transform_points", "dfusion_warp_solve_data_term", "dfusion_warp_index_info", "dfusion_icp_estimate", "dfusion_release_scratch", "dfusion_raycast_points_of_keys",
     "dfusion_selftest_exact_forms", "dfusion_warp_set_point_tiling", "dfusion_integrate_ex", "dfusion_warp_debug_counters", "dfusion_warp_alive_blocks", "dfusion_warp_coded_blocks", "dfusion_raycast_points_of_keys_rows", "dfusion_raycast_sum_pieces", "dfusion_raycast_min_pieces", "dfusion_integrate_warped_prepare", "dfusion_integrate_warped_sweep",
     "dfusion_render_image_points", "dfusion_render_image_depth", "dfusion_render_tangent_colors", "dfusion_cloud_to_depth",
-    "dfusion_warp_extend",
+    "dfusion_warp_extend", "dfusion_warp_solve", "dfusion_warp_node_graph",
 ]
 
 
@@ -141,6 +141,8 @@ def load(path, strict=True):
     L.dfusion_resize_points_normals.argtypes = [vp, sz, vp, sz, C.c_int, C.c_int, vp, sz, vp, sz, vp]
     L.dfusion_transform_points.argtypes = [vp, sz, C.c_int, vp, sz, C.c_int, C.c_int, C.c_int, fp, vp]
     L.dfusion_warp_solve_data_term.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]
+    L.dfusion_warp_solve.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp, vp, vp]
+    L.dfusion_warp_node_graph.argtypes = [vp, C.c_int, vp, vp, vp]
     L.dfusion_warp_extend.argtypes = [vp, C.c_int, vp, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp, C.POINTER(C.c_int),
                                       C.POINTER(C.c_int), vp]
     L.dfusion_warp_index_info.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint), C.POINTER(C.c_int)]

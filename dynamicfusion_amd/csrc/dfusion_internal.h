@@ -120,6 +120,11 @@ struct __attribute__((visibility("hidden"))) DfWarpField {     // (opaque in dfu
     DfDevBuf<uint16_t> pyr_mem;             // max-pyramid of the frame's dists image (warped sweep's depth cull), entries
     // scratch of dfusion_warp_solve_data_term (grown on demand)
     DfDevBuf<char> solver_ws;
+    // node graph of the regularised solve (dfusion_solver.hip): node i's graph_kg nearest other nodes nbr[M * kg], the edge weights
+    // alpha[M * kg], the incoming edges of every node (CSR: in_off[M + 1] into in_edge, ascending edge ids) and the build's scratch.
+    // graph_kg = 0: none -- dfusion_warp_set_nodes and an extend that adds nodes drop it, the next regularised solve rebuilds it
+    DfDevBuf<int> graph_nbr; DfDevBuf<float> graph_alpha; DfDevBuf<unsigned int> graph_in_off, graph_in_edge; DfDevBuf<char> graph_ws;
+    int graph_kg = 0;
     // points an indexed k-NN / warp pass left to the scan kernel: [0] count, [1..] ids
     DfDevBuf<int> pt_ids;
     int pt_image_cols = 0;                             // dfusion_warp_set_point_tiling: 0 = point queries in linear order

@@ -15,6 +15,7 @@
 //                                       a fixed tree -- no float atomics, so the result is reproducible (and bit-comparable
 //                                       with the restatement in oracle/dfusion_frontend_oracle.c);
 //   dot products / vector updates     : one 1024-thread workgroup (M <= 65535), fixed tree.
+// dfusion_warp_solve adds DynamicFusion's regularisation term over a node graph to the same solve (second half of this file).
 // Nothing returns to the host between iterations: once every component has converged (scal[3] == 0) the kernels of the remaining
 // steps return at once.
 #include <hipcub/hipcub.hpp>
@@ -187,7 +188,8 @@ __device__ __forceinline__ void sv_block_sum3(float (&s)[3], float* lds /* [3][1
 }
 
 // scal: [0..2] rr (0 = component converged / frozen), [3] number of components still iterating, [4] initial energy,
-// [5] final energy, [6..8] rr of the first residual (the convergence test is relative to it)
+// [5] final energy, [6..8] rr of the first residual (the convergence test is relative to it); the regularised solve reports through
+// [12..15] instead of [4], [5]: E_data before, after, E_reg before, after
 #define SV_REL_TOL2 1.0e-10f        // stop a component once |r|^2 <= 1e-10 |r0|^2
 __global__ __launch_bounds__(SV_BLOCK) void df_sv_init_kernel(const float* __restrict__ r, int M, float* __restrict__ x, float* __restrict__ p,
                                                               float* __restrict__ scal)
@@ -334,8 +336,159 @@ __global__ __launch_bounds__(256) void df_sv_writeback_kernel(const float4* __re
     o[0] = r.w; o[1] = r.x; o[2] = r.y; o[3] = r.z; o[4] = d.w; o[5] = d.x; o[6] = d.y; o[7] = d.z;
 }
 
-extern "C" int dfusion_warp_solve_data_term(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda,
-                                            float* dq_out, float* energy, dfStream stream)
+// ---------------------------------------------------------------- regularisation over the node graph
+// E_reg = sum_e alpha_e |g_e + delta_i - delta_j|^2 over the directed edges e = (i -> j), j one of node i's kg nearest other nodes:
+//   g_e = T_i(v_j) - T_j(v_j) at the transforms the solve starts from, alpha_e = max(dg_w_i, dg_w_j)  (DynamicFusion eq. 8, psi quadratic).
+// Edge e = i * kg + s (s = slot in i's list).  A node's sums run over its outgoing edges in slot order, then over its incoming edges in
+// ascending edge id (a CSR transpose made with the graph by a stable sort of the edge ids by head node): one thread per node, no atomics.
+__global__ __launch_bounds__(256) void df_sv_graph_pos_kernel(const float4* __restrict__ pos_sigma, int M, float* __restrict__ pos3)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= M) return;
+    const float4 p = pos_sigma[n];
+    pos3[3 * n] = p.x; pos3[3 * n + 1] = p.y; pos3[3 * n + 2] = p.z;
+}
+
+// node i's list: its kg + 1 nearest nodes without the entry whose id is i -- or without the last one when none is (duplicate positions)
+__global__ __launch_bounds__(256) void df_sv_graph_kernel(const int* __restrict__ idx, const float4* __restrict__ pos_sigma, int M, int kg,
+                                                          int* __restrict__ nbr, float* __restrict__ alpha, unsigned int* __restrict__ keys,
+                                                          unsigned int* __restrict__ vals)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= M) return;
+    const float si = pos_sigma[i].w;
+    int drop = kg;
+    for (int s = kg; s >= 0; --s) if (idx[i * (kg + 1) + s] == i) drop = s;        // the first entry that is i itself
+    for (int s = 0; s < kg; ++s) {
+        const int j = min(max(idx[i * (kg + 1) + s + (s >= drop ? 1 : 0)], 0), M - 1);   // (clamped: a NaN position must not index outside)
+        const int e = i * kg + s;
+        nbr[e] = j;
+        alpha[e] = fmaxf(si, pos_sigma[j].w);
+        keys[e] = (unsigned int)j; vals[e] = (unsigned int)e;
+    }
+}
+
+__global__ __launch_bounds__(256) void df_sv_reg_edge_kernel(const int* __restrict__ nbr, const float4* __restrict__ pos_sigma,
+                                                             const float4* __restrict__ rot, const float4* __restrict__ dual, int E, int kg,
+                                                             float* __restrict__ g)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    const int i = e / kg, j = nbr[e];
+    const float4 pj = pos_sigma[j], ri = rot[i], di = dual[i], rj = rot[j], dj = dual[j];
+    quat a, b;
+    a.w = ri.x; a.x = ri.y; a.y = ri.z; a.z = ri.w; b.w = di.x; b.x = di.y; b.y = di.z; b.z = di.w;
+    const f3 ti = dq_transform(a, b, mk3(pj.x, pj.y, pj.z));
+    a.w = rj.x; a.x = rj.y; a.y = rj.z; a.z = rj.w; b.w = dj.x; b.x = dj.y; b.y = dj.z; b.z = dj.w;
+    const f3 tj = dq_transform(a, b, mk3(pj.x, pj.y, pj.z));
+    g[3 * e] = ti.x - tj.x; g[3 * e + 1] = ti.y - tj.y; g[3 * e + 2] = ti.z - tj.z;
+}
+
+// r_n = r_n - lambda_reg * acc_n, acc_n = sum_out alpha_e g_e - sum_in alpha_e g_e  (r holds W^T e0)
+__global__ __launch_bounds__(256) void df_sv_reg_rhs_kernel(const float* __restrict__ alpha, const unsigned int* __restrict__ in_off,
+                                                            const unsigned int* __restrict__ in_edge, int M, int kg,
+                                                            const float* __restrict__ g, float lambda_reg, float* __restrict__ r)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= M) return;
+    float acc[3] = {0.f, 0.f, 0.f};
+    for (int s = 0; s < kg; ++s) {
+        const int e = n * kg + s;
+        const float a = alpha[e];
+        for (int c = 0; c < 3; ++c) acc[c] = acc[c] + a * g[3 * e + c];
+    }
+    for (unsigned int i = in_off[n]; i < in_off[n + 1]; ++i) {
+        const unsigned int e = in_edge[i];
+        const float a = alpha[e];
+        for (int c = 0; c < 3; ++c) acc[c] = acc[c] - a * g[3 * e + c];
+    }
+    for (int c = 0; c < 3; ++c) r[3 * n + c] = r[3 * n + c] - lambda_reg * acc[c];
+}
+
+// q_n = q_n + lambda_reg * (L p)_n, the edge differences p_i - p_j formed in the node's thread (q holds (W^T W + lambda I) p)
+__global__ __launch_bounds__(256) void df_sv_reg_apply_kernel(const int* __restrict__ nbr, const float* __restrict__ alpha,
+                                                              const unsigned int* __restrict__ in_off, const unsigned int* __restrict__ in_edge,
+                                                              int M, int kg, const float* __restrict__ p, float lambda_reg,
+                                                              float* __restrict__ q, const float* __restrict__ active)
+{
+    if (active && *active == 0.f) return;                               // see df_sv_w_apply_kernel
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= M) return;
+    const float pn[3] = {p[3 * n], p[3 * n + 1], p[3 * n + 2]};
+    float acc[3] = {0.f, 0.f, 0.f};
+    for (int s = 0; s < kg; ++s) {
+        const int e = n * kg + s, j = nbr[e];
+        const float a = alpha[e];
+        for (int c = 0; c < 3; ++c) acc[c] = acc[c] + a * (pn[c] - p[3 * j + c]);
+    }
+    for (unsigned int i = in_off[n]; i < in_off[n + 1]; ++i) {
+        const unsigned int e = in_edge[i], t = e / (unsigned int)kg;     // the edge t -> n
+        const float a = alpha[e];
+        for (int c = 0; c < 3; ++c) acc[c] = acc[c] - a * (p[3 * t + c] - pn[c]);
+    }
+    for (int c = 0; c < 3; ++c) q[3 * n + c] = q[3 * n + c] + lambda_reg * acc[c];
+}
+
+// ---- E_reg = sum_e alpha_e |(g_e + x_i) - x_j|^2 (x nullable = 0), reduced like df_sv_energy_kernel over the edges
+__global__ __launch_bounds__(SV_BLOCK) void df_sv_reg_energy_kernel(const int* __restrict__ nbr, const float* __restrict__ alpha,
+                                                                    const float* __restrict__ g, const float* __restrict__ x, int E, int kg,
+                                                                    float* __restrict__ out)
+{
+    __shared__ float lds[3 * SV_BLOCK];
+    float s[3] = {0.f, 0.f, 0.f};
+    for (int e = threadIdx.x; e < E; e += SV_BLOCK) {
+        const int i = e / kg, j = nbr[e];
+        const float a = alpha[e];
+        for (int c = 0; c < 3; ++c) {
+            const float h = x ? (g[3 * e + c] + x[3 * i + c]) - x[3 * j + c] : g[3 * e + c];
+            s[c] = s[c] + a * (h * h);
+        }
+    }
+    sv_block_sum3(s, lds);
+    if (threadIdx.x == 0) *out = (s[0] + s[1]) + s[2];
+}
+
+// The node graph of the handle for `kg` neighbours, made on first use and kept until the node set changes (graph_kg = 0).
+static int df_sv_graph(DfWarpField* wf, int kg, dfStream stream)
+{
+    if (wf->graph_kg == kg) return DF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int M = wf->M, kq = kg + 1;
+    const size_t E = (size_t)M * kg;
+    wf->graph_kg = 0;
+    int rc;
+    if ((rc = wf->graph_nbr.reserve(E)) || (rc = wf->graph_alpha.reserve(E)) || (rc = wf->graph_in_off.reserve((size_t)M + 2)) ||
+        (rc = wf->graph_in_edge.reserve(E))) return rc;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_pos = take((size_t)M * 12), o_idx = take((size_t)M * kq * 4), o_d2 = take((size_t)M * kq * 4), o_keys = take(E * 4),
+                 o_vals = take(E * 4), o_skeys = take(E * 4);
+    size_t sort_bytes = 0;
+    DF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned int*)nullptr, (unsigned int*)nullptr, (const unsigned int*)nullptr,
+                                              (unsigned int*)nullptr, (int)E, 0, 16, st));
+    const size_t o_sort = take(sort_bytes);
+    if ((rc = wf->graph_ws.reserve(off))) return rc;
+    char* ws = wf->graph_ws;
+    float* pos3 = (float*)(ws + o_pos); int* idx = (int*)(ws + o_idx); float* d2 = (float*)(ws + o_d2);
+    unsigned int* keys = (unsigned int*)(ws + o_keys); unsigned int* vals = (unsigned int*)(ws + o_vals);
+    unsigned int* skeys = (unsigned int*)(ws + o_skeys);
+    const dim3 gM((M + 255) / 256);
+    hipLaunchKernelGGL(df_sv_graph_pos_kernel, gM, dim3(256), 0, st, wf->pos_sigma, M, pos3);
+    DF_LAUNCH_CHECK();
+    if ((rc = dfusion_knn(wf, kq, pos3, M, idx, d2, stream))) return rc;
+    hipLaunchKernelGGL(df_sv_graph_kernel, gM, dim3(256), 0, st, idx, wf->pos_sigma, M, kg, wf->graph_nbr.p, wf->graph_alpha.p, keys, vals);
+    DF_LAUNCH_CHECK();
+    DF_HIP(hipcub::DeviceRadixSort::SortPairs(ws + o_sort, sort_bytes, keys, skeys, vals, wf->graph_in_edge.p, (int)E, 0, 16, st));   // stable
+    hipLaunchKernelGGL(df_sv_offsets_kernel, dim3((unsigned)((E + 1 + 255) / 256)), dim3(256), 0, st, skeys, (int)E, M, wf->graph_in_off);
+    DF_LAUNCH_CHECK();
+    wf->graph_kg = kg;
+    return DF_OK;
+}
+
+// The solve behind both entry points.  kg = 0: the data term alone -- exactly the launches dfusion_warp_solve_data_term always made,
+// energy = 2 floats.  kg > 0: with lambda_reg * E_reg, energy = 4 floats {E_data before, after, E_reg before, after}.
+static int df_sv_solve(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int kg,
+                       float lambda_reg, float* dq_out, float* energy, dfStream stream)
 {
     if (!wf || !canonical || !live || N <= 0 || iters < 0 || !(lambda >= 0.f) || wf->M <= 0 || k < 1 || k > 8 || wf->M < k) return DF_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
@@ -349,6 +502,8 @@ extern "C" int dfusion_warp_solve_data_term(DfWarpField* wf, int k, const float*
                  o_svals = take(E * 4), o_spt = take(E * 4), o_sw = take(E * 4), o_e0 = take((size_t)N * 12), o_u = take((size_t)N * 12), o_off = take(((size_t)M + 2) * 4),
                  o_x = take((size_t)M * 12), o_r = take((size_t)M * 12), o_p = take((size_t)M * 12), o_q = take((size_t)M * 12),
                  o_scal = take(64), o_dq = take((size_t)M * 32);
+    const int Eg = M * kg;                                              // graph edges (0: no regularisation)
+    const size_t o_g = take((size_t)Eg * 12);
     size_t sort_bytes = 0;
     DF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned int*)nullptr, (unsigned int*)nullptr, (const unsigned int*)nullptr,
                                               (unsigned int*)nullptr, (int)E, 0, 17, st));
@@ -362,7 +517,9 @@ extern "C" int dfusion_warp_solve_data_term(DfWarpField* wf, int k, const float*
     unsigned int* spt = (unsigned int*)(ws + o_spt); float* sw = (float*)(ws + o_sw);
     float* e0 = (float*)(ws + o_e0); float* u = (float*)(ws + o_u); unsigned int* offs = (unsigned int*)(ws + o_off);
     float* x = (float*)(ws + o_x); float* r = (float*)(ws + o_r); float* p = (float*)(ws + o_p); float* q = (float*)(ws + o_q);
-    float* scal = (float*)(ws + o_scal); float* dq = (float*)(ws + o_dq);
+    float* scal = (float*)(ws + o_scal); float* dq = (float*)(ws + o_dq); float* g = (float*)(ws + o_g);
+    float* const en = kg ? scal + 12 : scal + 4;                        // {E_data before, after} and, regularised, {E_reg before, after}
+    if (kg) { rc = df_sv_graph(wf, kg, stream); if (rc) return rc; }
 
     rc = dfusion_knn(wf, k, canonical, N, idx, d2, stream);           // getWeightsAndUpdateKNN's k-NN (NaN queries are masked below)
     if (rc) return rc;
@@ -374,30 +531,69 @@ extern "C" int dfusion_warp_solve_data_term(DfWarpField* wf, int k, const float*
     DF_LAUNCH_CHECK();
     hipLaunchKernelGGL(df_sv_sorted_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, svals, w, (int)E, k, spt, sw);
     DF_LAUNCH_CHECK();
-    if (energy) { hipLaunchKernelGGL(df_sv_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, e0, N, scal + 4); DF_LAUNCH_CHECK(); }
+    if (energy) { hipLaunchKernelGGL(df_sv_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, e0, N, en); DF_LAUNCH_CHECK(); }
     auto step = M <= 2 * SV_BLOCK ? df_sv_step_reg_kernel<2> : M <= 5 * SV_BLOCK ? df_sv_step_reg_kernel<5> : M <= 8 * SV_BLOCK ? df_sv_step_reg_kernel<8> : df_sv_step_kernel;
     auto w_apply = k == 8 ? df_sv_w_apply_kernel<8> : k == 4 ? df_sv_w_apply_kernel<4> : df_sv_w_apply_kernel<0>;
     // r0 = W^T e0 ; p0 = r0 ; x0 = 0
     const dim3 gW(M);
     hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, offs, spt, sw, M, e0, 0.f, (const float*)nullptr, r, (const float*)nullptr);
     DF_LAUNCH_CHECK();
+    if (kg) {                                                           // r0 = W^T e0 - lambda_reg * b
+        hipLaunchKernelGGL(df_sv_reg_edge_kernel, dim3((Eg + 255) / 256), dim3(256), 0, st, wf->graph_nbr, wf->pos_sigma, wf->rot, wf->dual, Eg, kg, g);
+        hipLaunchKernelGGL(df_sv_reg_rhs_kernel, gM, dim3(256), 0, st, wf->graph_alpha, wf->graph_in_off, wf->graph_in_edge, M, kg, g, lambda_reg, r);
+        if (energy) hipLaunchKernelGGL(df_sv_reg_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, wf->graph_nbr, wf->graph_alpha, g, (const float*)nullptr, Eg, kg, en + 2);
+        DF_LAUNCH_CHECK();
+    }
     hipLaunchKernelGGL(df_sv_init_kernel, dim3(1), dim3(SV_BLOCK), 0, st, r, M, x, p, scal);
     DF_LAUNCH_CHECK();
     for (int it = 0; it < iters; ++it) {
         hipLaunchKernelGGL(w_apply, gN, dim3(256), 0, st, w, keys, N, k, M, p, u, (const float*)(scal + 3));
         hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, offs, spt, sw, M, u, lambda, p, q, (const float*)(scal + 3));
+        if (kg) hipLaunchKernelGGL(df_sv_reg_apply_kernel, gM, dim3(256), 0, st, wf->graph_nbr, wf->graph_alpha, wf->graph_in_off, wf->graph_in_edge, M, kg, p,
+                                   lambda_reg, q, (const float*)(scal + 3));
         hipLaunchKernelGGL(step, dim3(1), dim3(SV_BLOCK), 0, st, q, M, x, r, p, scal);
         DF_LAUNCH_CHECK();
     }
     if (energy) {
         hipLaunchKernelGGL(w_apply, gN, dim3(256), 0, st, w, keys, N, k, M, x, u, (const float*)nullptr);
         hipLaunchKernelGGL(df_sv_residual_kernel, dim3((unsigned)((3 * (size_t)N + 255) / 256)), dim3(256), 0, st, e0, u, 3 * N, u);
-        hipLaunchKernelGGL(df_sv_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, u, N, scal + 5);
+        hipLaunchKernelGGL(df_sv_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, u, N, en + 1);
+        if (kg) hipLaunchKernelGGL(df_sv_reg_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, wf->graph_nbr, wf->graph_alpha, g, (const float*)x, Eg, kg, en + 3);
         DF_LAUNCH_CHECK();
-        DF_HIP(hipMemcpyAsync(energy, scal + 4, 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        DF_HIP(hipMemcpyAsync(energy, en, (kg ? 4 : 2) * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     hipLaunchKernelGGL(df_sv_writeback_kernel, gM, dim3(256), 0, st, wf->rot, wf->node_t, x, M, dq);
     DF_LAUNCH_CHECK();
     if (dq_out) DF_HIP(hipMemcpyAsync(dq_out, dq, (size_t)M * 32, hipMemcpyDeviceToDevice, st));
     return dfusion_warp_set_transforms(wf, dq, stream);
+}
+
+extern "C" int dfusion_warp_solve_data_term(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda,
+                                            float* dq_out, float* energy, dfStream stream)
+{
+    return df_sv_solve(wf, k, canonical, live, N, iters, lambda, 0, 0.f, dq_out, energy, stream);
+}
+
+extern "C" int dfusion_warp_solve(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int kg,
+                                  float lambda_reg, float* dq_out, float* energy, dfStream stream)
+{
+    if (!wf || kg < 0 || kg > 7 || (kg > 0 && wf->M < kg + 1) || !(lambda_reg >= 0.f)) return DF_E_INVALID;
+    if (kg == 0 || lambda_reg == 0.f) {                                 // off: the data-term call, bit for bit and launch for launch
+        const int rc = df_sv_solve(wf, k, canonical, live, N, iters, lambda, 0, 0.f, dq_out, energy, stream);
+        static const float zeros[2] = {0.f, 0.f};                       // (a copy from the host, not a fill: no kernel of any kind is added)
+        if (rc == DF_OK && energy) DF_HIP(hipMemcpyAsync(energy + 2, zeros, sizeof(zeros), hipMemcpyHostToDevice, (hipStream_t)stream));
+        return rc;
+    }
+    return df_sv_solve(wf, k, canonical, live, N, iters, lambda, kg, lambda_reg, dq_out, energy, stream);
+}
+
+extern "C" int dfusion_warp_node_graph(DfWarpField* wf, int kg, int* nbr, float* alpha, dfStream stream)
+{
+    if (!wf || !nbr || kg < 1 || kg > 7 || wf->M < kg + 1) return DF_E_INVALID;
+    const int rc = df_sv_graph(wf, kg, stream);
+    if (rc) return rc;
+    const size_t E = (size_t)wf->M * kg;
+    DF_HIP(hipMemcpyAsync(nbr, wf->graph_nbr, E * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (alpha) DF_HIP(hipMemcpyAsync(alpha, wf->graph_alpha, E * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return DF_OK;
 }

@@ -368,7 +368,9 @@ int df_warp_grow(DfWarpField* wf, const float* pos, const float* dq, const float
         if (rc) return rc;
     }
     { int rc = df_wait_split_sweep(wf, st); if (rc) return rc; }
+    const int M_old = wf->M;
     wf->M = Mn;
+    if (Mn > M_old) wf->graph_kg = 0;                          // (the solver's node graph: rebuilt by the next regularised solve)
     { int rc = df_warp_pack_current(wf, pos, dq, sigma, st); if (rc) return rc; }   // (bounds, the sigma bound [4] included)
     { int rc = df_warp_build_tie_tree(wf, st); if (rc) return rc; }
     if (!wf->index_valid) return DF_OK;

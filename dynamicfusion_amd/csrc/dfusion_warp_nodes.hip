@@ -282,6 +282,7 @@ extern "C" int dfusion_warp_set_nodes(DfWarpField* wf, const float* pos, const f
     int rc = df_warp_reserve(wf, M);
     if (rc) return rc;
     wf->M = M;
+    wf->graph_kg = 0;                                          // (the solver's node graph belongs to the old node set)
     wf->index_valid = false;
     wf->tab_valid = false; wf->w_tab_valid = false;
     rc = df_warp_pack(wf, pos, dq, sigma, (hipStream_t)stream);

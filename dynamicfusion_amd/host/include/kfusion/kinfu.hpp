@@ -48,6 +48,8 @@ namespace kfusion
         bool device_resident = true;         // dynamicfusion() keeps its point sets on the GPU; false = the reference's host staging
         int warp_solver_iterations = 40;     // CG steps of the warp data term per frame, 0 = off (Opt's cap is linearIter = 100,
                                              // kinfu.cpp:118; the synthetic sequence has converged to 4 digits by 40)
+        int warp_reg_neighbours = 0;         // regularisation of the warp solve (WarpField::setRegularisation): graph neighbours per node,
+        float warp_reg_lambda = 0.f;         // and the term's weight; 0 = off, the data term alone as in the reference
     };
 
     class KinFu

@@ -1,7 +1,7 @@
 // kfusion/warp_field.hpp -- WarpField with the reference's hot-path interface
 // (/root/reference/kfusion/include/kfusion/warp_field.hpp:41-88): host node store + GPU k-NN / DQB / warp through the
 // C-ABI.  energy_data is the GPU data-term solve; energy / energy_reg / clear exist with the reference's (empty) behaviour -- no
-// regularisation term is ever added to the reference's problem either.  tests/test_mirror_headers.py checks every public name of the
+// regularisation term is ever added to the reference's problem either; setRegularisation adds the paper's to energy_data.  tests/test_mirror_headers.py checks every public name of the
 // reference's header against this one.
 #pragma once
 #include <utility>
@@ -82,6 +82,13 @@ namespace kfusion
         void setSolverIterations(int iters) { solver_iters_ = iters; }
         int getSolverIterations() const { return solver_iters_; }
         void setSolverDamping(float lambda) { solver_lambda_ = lambda; }
+        /// DynamicFusion's regularisation term (section 3.3, eq. 8) in energy_data: every node is tied to its `neighbours` (0..7)
+        /// nearest other nodes with weight `lambda` (dfusion_warp_solve).  Off by default (neighbours = 0 or lambda = 0): energy_data is
+        /// then the data term alone, as in the reference.
+        void setRegularisation(int neighbours, float lambda) { reg_neighbours_ = neighbours; reg_lambda_ = lambda; }
+        /// E_reg before / after the last regularised energy_data (with setTrackEnergy; 0 while the term is off)
+        float lastRegEnergyBefore() const { return last_energy_[2]; }
+        float lastRegEnergyAfter() const { return last_energy_[3]; }
         /// E before / after the last energy_data (evaluated only when asked for: two extra passes over the points)
         void setTrackEnergy(bool on) { track_energy_ = on; }
         float lastEnergyBefore() const { return last_energy_[0]; }
@@ -131,7 +138,9 @@ namespace kfusion
         mutable float index_key_[20] = {0};                  // dims, voxel size, pose, slab of the geometry the index was built for
         int solver_iters_ = 100;
         float solver_lambda_ = 0.f;
-        float last_energy_[2] = {0.f, 0.f};
+        int reg_neighbours_ = 0;
+        float reg_lambda_ = 0.f;
+        float last_energy_[4] = {0.f, 0.f, 0.f, 0.f};
         bool track_energy_ = false;
     };
 }

@@ -544,10 +544,17 @@ void WarpField::energy_data(const cuda::DeviceArray<float>& canonical_vertices, 
 {
     const size_t M = nodes_.size();
     if (!M || n <= 0) return;
-    solve_dq_.create(M * 8); solve_energy_.create(2);      // no-ops after the first frame
-    KF_DF(dfusion_warp_solve_data_term(handle_, k_, canonical_vertices.ptr(), live_vertices.ptr(), n, solver_iters_, solver_lambda_, solve_dq_.ptr(),
-                                       track_energy_ ? solve_energy_.ptr() : nullptr, nullptr));
-    if (track_energy_) solve_energy_.download(last_energy_);
+    solve_dq_.create(M * 8); solve_energy_.create(4);      // no-ops after the first frame
+    if (reg_neighbours_ != 0 && reg_lambda_ != 0.f)        // with the regularisation term over the node graph
+        KF_DF(dfusion_warp_solve(handle_, k_, canonical_vertices.ptr(), live_vertices.ptr(), n, solver_iters_, solver_lambda_, reg_neighbours_,
+                                 reg_lambda_, solve_dq_.ptr(), track_energy_ ? solve_energy_.ptr() : nullptr, nullptr));
+    else
+        KF_DF(dfusion_warp_solve_data_term(handle_, k_, canonical_vertices.ptr(), live_vertices.ptr(), n, solver_iters_, solver_lambda_, solve_dq_.ptr(),
+                                           track_energy_ ? solve_energy_.ptr() : nullptr, nullptr));
+    if (track_energy_) {
+        solve_energy_.download(last_energy_);
+        if (!(reg_neighbours_ != 0 && reg_lambda_ != 0.f)) last_energy_[2] = last_energy_[3] = 0.f;   // (the data term wrote two floats)
+    }
     nodes_stale_ = true;                                   // the host node store follows (updateWarp, optimisation.hpp:211-218) -- when it is looked at
 }
 
@@ -938,6 +945,7 @@ void KinFu::optimiseWarp(std::vector<Vec3f>& canonical, std::vector<Vec3f>& cano
 {
     if (params_.warp_solver_iterations <= 0) return;
     warp_->setSolverIterations(params_.warp_solver_iterations);
+    warp_->setRegularisation(params_.warp_reg_neighbours, params_.warp_reg_lambda);
     warp_->energy_data(canonical, canonical_normals, live, canonical_normals);
 }
 
@@ -1078,6 +1086,7 @@ void KinFu::dynamicfusion(cuda::Depth& depth, cuda::Cloud live_frame, cuda::Norm
             KF_DF(dfusion_transform_points((const float*)live_frame.ptr(), live_frame.step(), 4, df_live3_.ptr(), (size_t)depth.cols() * 12, 3,
                                            depth.cols(), depth.rows(), nullptr, nullptr));
             warp_->setSolverIterations(params_.warp_solver_iterations);
+            warp_->setRegularisation(params_.warp_reg_neighbours, params_.warp_reg_lambda);
             warp_->energy_data(df_points3_, df_live3_, (int)n);
         }
         warp_->warp(df_points3_, df_normals3_, (int)n);                      // :391

@@ -174,3 +174,26 @@ class WarpField:
                                                            _ptr(dq), _ptr(en), _stream()), "dfusion_warp_solve_data_term")
         self._dq = dq
         return dq, en
+
+    def solve(self, canonical_dev, live_dev, iters=100, lam=0.0, reg_neighbours=0, reg_lambda=0.0, k=None):
+        """energy_data with DynamicFusion's regularisation term over the node graph (include/dfusion.h dfusion_warp_solve): every node
+        is tied to its `reg_neighbours` nearest other nodes with weight `reg_lambda`, so that nodes few or no points constrain follow
+        their neighbours.  reg_neighbours = 0 or reg_lambda = 0: energy_data's result.  Returns (dq [M,8] device tensor, energy device
+        tensor [E_data before, E_data after, E_reg before, E_reg after])."""
+        k = self.k if k is None else k
+        n = int(canonical_dev.shape[0])
+        dq = torch.empty((self.M, 8), dtype=torch.float32, device=self.device)
+        en = torch.zeros(4, dtype=torch.float32, device=self.device)
+        capi.check(capi.lib().dfusion_warp_solve(self.handle, k, _flat(canonical_dev), _flat(live_dev), n, int(iters), float(lam),
+                                                 int(reg_neighbours), float(reg_lambda), _ptr(dq), _ptr(en), _stream()), "dfusion_warp_solve")
+        self._dq = dq
+        return dq, en
+
+    def node_graph(self, kg):
+        """The graph solve() regularises over: (nbr int32 [M, kg], alpha float32 [M, kg]) device tensors -- node i's kg nearest other
+        nodes and the edge weights max(dg_w_i, dg_w_j)."""
+        kg = int(kg)
+        nbr = torch.empty((self.M, max(kg, 0)), dtype=torch.int32, device=self.device)
+        alpha = torch.empty((self.M, max(kg, 0)), dtype=torch.float32, device=self.device)
+        capi.check(capi.lib().dfusion_warp_node_graph(self.handle, kg, _ptr(nbr), _ptr(alpha), _stream()), "dfusion_warp_node_graph")
+        return nbr, alpha

@@ -372,6 +372,28 @@ int dfusion_warp_points(DfWarpField *wf, int k, float *points_dev, float *normal
 int dfusion_warp_solve_data_term(DfWarpField *wf, int k, const float *canonical_dev, const float *live_dev, int N, int iters,
                                  float lambda, float *dq_out_dev, float *energy_dev, dfStream stream);
 
+/* The same solve with DynamicFusion's regularisation term (section 3.3, eq. 8; declared and left empty by the reference: WarpField::energy_reg,
+ * DynamicFusionRegEnergy) over a node graph -- additions to ABI 7.  Edge e = i * kg + s runs from node i to the s-th of its kg nearest
+ * OTHER nodes j: dfusion_knn with k = kg + 1 on the node positions (nanoflann's tie order) without the entry whose id is i, or without
+ * the last entry when none is (duplicate positions).  With g_e = T_i(v_j) - T_j(v_j) at the transforms the handle holds when the call
+ * starts (v_j node j's position, T_n = DualQuaternion::transform of node n) and alpha_e = max(dg_w_i, dg_w_j):
+ *     E_reg(delta) = sum_e alpha_e | g_e + delta_i - delta_j |^2                       (psi quadratic; rotations stay fixed)
+ * and the call takes `iters` conjugate-gradient steps on (W^T W + lambda I + lambda_reg L) delta = W^T e0 - lambda_reg b, where
+ * L delta and b are the node sums of alpha_e (delta_i - delta_j) and alpha_e g_e: + over a node's outgoing edges in slot order, then
+ * - over its incoming edges in ascending edge id.  Fixed sum orders, no atomics: reproducible, and restated in tests/solver_reg_ref.py.
+ *   kg          graph neighbours, 0..7; kg > 0 needs M >= kg + 1
+ *   lambda_reg  weight of E_reg, >= 0
+ *   energy_dev  (nullable) 4 floats: E_data before, E_data after, E_reg before, E_reg after (E_reg without lambda_reg)
+ * kg == 0 or lambda_reg == 0 switches the term off: the call is dfusion_warp_solve_data_term, launch for launch and bit for bit, and
+ * energy_dev[2..3] = 0.  The graph is kept on the handle for (node set, kg); dfusion_warp_set_nodes and a dfusion_warp_extend that adds
+ * nodes drop it and the next regularised solve rebuilds it; dfusion_warp_set_transforms leaves it alone.
+ * DF_E_INVALID: what dfusion_warp_solve_data_term refuses, kg outside 0..7, kg > 0 with M < kg + 1, lambda_reg negative or NaN.         */
+int dfusion_warp_solve(DfWarpField *wf, int k, const float *canonical_dev, const float *live_dev, int N, int iters, float lambda,
+                       int kg, float lambda_reg, float *dq_out_dev, float *energy_dev, dfStream stream);
+/* The node graph dfusion_warp_solve uses for `kg` (1..7, M >= kg + 1; built now if the handle does not hold it):
+ * nbr_dev[M*kg] int32 the head node of every edge, alpha_dev[M*kg] (nullable) the edge weights.                                      */
+int dfusion_warp_node_graph(DfWarpField *wf, int kg, int *nbr_dev, float *alpha_dev, dfStream stream);
+
 /* The north-star kernel: per-voxel DQB (WarpField::DQB, warp_field.cpp:203-217) composed with
  * TsdfIntegrator (tsdf_volume.cu:77-104): x_c = vol2world*voxel, x_w = DQB(x_c).transform(x_c),
  * vc = world2cam*x_w, then the projective update.  Requires dfusion_warp_build_index.         */
