@@ -60,7 +60,7 @@ SYMBOLS = [
     "dfusion_icp_workspace_floats", "dfusion_icp_sums_points", "dfusion_icp_sums_depth", "dfusion_transform_points", "dfusion_warp_solve_data_term", "dfusion_warp_index_info", "dfusion_icp_estimate", "dfusion_release_scratch", "dfusion_raycast_points_of_keys",
     "dfusion_selftest_exact_forms", "dfusion_warp_set_point_tiling", "dfusion_integrate_ex", "dfusion_warp_debug_counters", "dfusion_warp_alive_blocks", "dfusion_warp_coded_blocks", "dfusion_raycast_points_of_keys_rows", "dfusion_raycast_sum_pieces", "dfusion_raycast_min_pieces", "dfusion_integrate_warped_prepare", "dfusion_integrate_warped_sweep",
     "dfusion_render_image_points", "dfusion_render_image_depth", "dfusion_render_tangent_colors", "dfusion_cloud_to_depth",
-    "dfusion_warp_extend", "dfusion_warp_solve", "dfusion_warp_node_graph",
+    "dfusion_warp_extend", "dfusion_warp_solve", "dfusion_warp_node_graph", "dfusion_extract_mesh",
 ]
 
 
@@ -121,6 +121,7 @@ def load(path, strict=True):
     L.dfusion_raycast_points_of_keys_rows.argtypes = [fp, fp, fp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.dfusion_extract_cloud.argtypes = [DfVolume, C.POINTER(DfSlab), fp, vp, C.c_ulonglong, vp, vp]
     L.dfusion_extract_normals.argtypes = [DfVolume, C.POINTER(DfSlab), fp, fp, vp, C.c_ulonglong, C.c_float, vp, vp]
+    L.dfusion_extract_mesh.argtypes = [DfVolume, C.POINTER(DfSlab), fp, vp, C.c_ulonglong, vp, C.c_ulonglong, vp, vp]
     L.dfusion_warp_create.argtypes = [C.POINTER(vp)]
     L.dfusion_warp_destroy.argtypes = [vp]
     L.dfusion_warp_set_nodes.argtypes = [vp, vp, vp, vp, C.c_int, vp]

@@ -784,6 +784,9 @@ static DfScratchEntry* df_rigid_scratch_acquire(hipStream_t st, size_t bytes, ch
     *mem_out = e->mem;
     return e;
 }
+// the same buffer for dfusion_mesh.hip (which declares these two): calls on one stream are ordered, so they can share it
+DF_LOCAL void* df_scratch_acquire(hipStream_t st, size_t bytes, char** mem_out) { return df_rigid_scratch_acquire(st, bytes, mem_out); }
+DF_LOCAL void df_scratch_release(void* entry) { ((DfScratchEntry*)entry)->busy.unlock(); }
 extern "C" int dfusion_release_scratch(void)
 {
     std::lock_guard<std::mutex> lock(g_df_scratch_mutex);

@@ -9,6 +9,9 @@
 //          With the trailing `surface_fusion` argument the body of KinFu::dynamicfusion (kinfu.cpp:344-391, minus the solver)
 //          then runs on the last frame: ray-cast points -> canonical -> WarpField::warp -> TsdfVolume::surface_fusion, and
 //          out.bin continues with: warped f32[rows*cols*3], depth after removal u16[rows*cols], volume u32[dims^3].
+//   headless_frame mesh <out.ply> <the arguments above>: the same run, and the volume's surface after the frames (before any
+//          surface_fusion) as a triangle mesh, TsdfVolume::fetchMesh, in a binary little-endian PLY -- byte for byte the file
+//          dynamicfusion_amd.mesh_io.write_ply makes of the Python mirror's fetchMesh.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -110,9 +113,29 @@ static int bench_mode(int argc, char** argv)
     return 0;
 }
 
+static int write_mesh_ply(const cuda::TsdfVolume& volume, const char* path)
+{
+    cuda::DeviceArray<Point> vertices; cuda::DeviceArray<int> triangles;
+    volume.fetchMesh(vertices, triangles);
+    std::vector<Point> v; std::vector<int> t;
+    vertices.download(v); triangles.download(t);
+    FILE* f = std::fopen(path, "wb");
+    if (!f) { std::perror("ply"); return 2; }
+    std::fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
+                    "element face %zu\nproperty list uchar int vertex_indices\nend_header\n", v.size(), t.size() / 3);
+    for (size_t i = 0; i < v.size(); ++i) std::fwrite(&v[i], 4, 3, f);
+    const unsigned char three = 3;
+    for (size_t i = 0; i < t.size() / 3; ++i) { std::fwrite(&three, 1, 1, f); std::fwrite(&t[3 * i], 4, 3, f); }
+    std::fclose(f);
+    std::printf("mesh: %zu vertices, %zu triangles\n", v.size(), t.size() / 3);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     if (argc >= 2 && !std::strcmp(argv[1], "bench")) return bench_mode(argc, argv);
+    const char* mesh_path = nullptr;
+    if (argc >= 3 && !std::strcmp(argv[1], "mesh")) { mesh_path = argv[2]; argv[2] = argv[0]; argv += 2; argc -= 2; }
     if (argc != 10 && argc != 11) { std::fprintf(stderr, "usage: %s dims size cols rows frames nodes k in.bin out.bin\n", argv[0]); return 2; }
     const int dims = std::atoi(argv[1]); const float size = (float)std::atof(argv[2]);
     const int cols = std::atoi(argv[3]), rows = std::atoi(argv[4]), frames = std::atoi(argv[5]), M = std::atoi(argv[6]), k = std::atoi(argv[7]);
@@ -188,6 +211,7 @@ int main(int argc, char** argv)
         std::fwrite(volume.get_cloud_host().data(), 16, cnt, out);
         std::fwrite(volume.get_normal_host().data(), 16, cnt, out);
     }
+    if (mesh_path && write_mesh_ply(volume, mesh_path)) return 2;
     if (argc == 11 && M > 0) {
         const Affine3f camera_pose = cam[frames - 1];
         const Affine3f inverse_pose = camera_pose.inv();                             // kinfu.cpp:357

@@ -96,6 +96,9 @@ public:
     // ---- surface extraction (tsdf_volume.cpp:181-218, 313-325)
     DeviceArray<Point> fetchCloud(DeviceArray<Point>& cloud_buffer) const;
     void fetchNormals(const DeviceArray<Point>& cloud, DeviceArray<Normal>& normals) const;
+    // (no reference counterpart) the same surface as a triangle mesh, include/dfusion.h dfusion_extract_mesh: vertices in the rule's order,
+    // triangles 3 vertex indices each; both arrays are sized exactly (a count-only call, then one of that size)
+    void fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& triangles) const;
     void compute_points();
     void compute_normals();
 #ifdef KFUSION_USE_OPENCV

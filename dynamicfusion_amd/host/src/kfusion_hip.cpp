@@ -300,6 +300,20 @@ void TsdfVolume::fetchNormals(const DeviceArray<Point>& cloud, DeviceArray<Norma
                                   (float*)normals.ptr(), nullptr));
 }
 
+void TsdfVolume::fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& triangles) const
+{
+    float aff[12]; affine_to_aff12(pose_, aff);
+    DeviceArray<unsigned long long> counts(2);
+    KF_DF(dfusion_extract_mesh(c_volume(*this), c_slab(*this).ptr(), aff, nullptr, 0, nullptr, 0, counts.ptr(), nullptr));
+    unsigned long long n[2] = {0, 0};
+    counts.download(n);
+    vertices.create((size_t)n[0]);
+    triangles.create((size_t)n[1] * 3);
+    if (!n[0] && !n[1]) return;
+    KF_DF(dfusion_extract_mesh(c_volume(*this), c_slab(*this).ptr(), aff, n[0] ? (float*)vertices.ptr() : nullptr, n[0],
+                               n[1] ? (unsigned int*)triangles.ptr() : nullptr, n[1], counts.ptr(), nullptr));
+}
+
 void TsdfVolume::compute_points()
 {
     cloud_ = fetchCloud(cloud_buffer_);

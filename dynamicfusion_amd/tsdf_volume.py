@@ -381,6 +381,26 @@ class TsdfVolume:
                    "dfusion_extract_normals")
         return normals
 
+    # ---- no reference counterpart: the surface as a triangle mesh (include/dfusion.h dfusion_extract_mesh)
+    def fetchMesh(self, with_normals=False):
+        """-> (vertices float32 [n, 4], triangles int32 [m, 3] (uint32 bits)) device tensors, in the rule's order; with_normals: also
+        fetchNormals(vertices).  One count-only call, then one of exactly that size; the counts stay in last_mesh_counts_."""
+        aff = capi.floats(aff12(self.pose_))
+        counts = torch.empty(2, dtype=torch.int64, device=self.device)
+        capi.check(capi.lib().dfusion_extract_mesh(self.c_volume(), self.c_slab(), aff, None, 0, None, 0, _ptr(counts), _stream()),
+                   "dfusion_extract_mesh")
+        nv, nt = (int(c) for c in counts.tolist())
+        self.last_mesh_counts_ = (nv, nt)
+        vertices = torch.empty((nv, 4), dtype=torch.float32, device=self.device)
+        triangles = torch.empty((nt, 3), dtype=torch.int32, device=self.device)
+        if nv or nt:
+            capi.check(capi.lib().dfusion_extract_mesh(self.c_volume(), self.c_slab(), aff, _ptr(vertices) if nv else None, nv,
+                                                       _ptr(triangles) if nt else None, nt, _ptr(counts), _stream()),
+                       "dfusion_extract_mesh")
+        if with_normals:
+            return vertices, triangles, self.fetchNormals(vertices)
+        return vertices, triangles
+
     # ---- tsdf_volume.cpp:266-292 psdf (device::project_and_remove + the per-point K^-1 arithmetic, fused on the GPU)
     def psdf(self, warped, dists, intr, return_points=False):
         """warped: float32 [n, 3] or [n, 4] device tensor of camera-frame points; dists: u16 [rows, cols] device tensor,

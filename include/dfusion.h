@@ -266,6 +266,33 @@ int dfusion_extract_normals(DfVolume v, const DfSlab *slab, const float aff[12],
                             const float *points_dev, unsigned long long n, float gradient_delta_factor,
                             float *normals_dev, dfStream stream);
 
+/* A triangle mesh of the same surface (no reference counterpart; additive, ABI 7): marching tetrahedra on the Kuhn subdivision of
+ * every voxel cell -- no ambiguous cases, consistent across cell faces, so the mesh is closed wherever the cells around the surface
+ * are meshed.  DESIGN.md states the rule in full; tests/mesh_ref.py restates it in numpy and the output equals it bit for bit.
+ *   - a voxel is valid by the extractor's rule (weight != 0, tsdf != 1), inside iff its tsdf < 0 (+0 and -0 are outside), and sits
+ *     at ((x + .5) vsx, (y + .5) vsy, (z + .5) vsz);
+ *   - voxel p owns the 7 edges p -> p + d, d in {0,1}^3 \ 0, slot s = dx + 2 dy + 4 dz - 1 (axis edges 0, 1, 3; face diagonals
+ *     2, 4, 5; the body diagonal 6); an edge carries a vertex iff both ends are valid and exactly one is inside: with F, Fn the
+ *     absolute tsdf of p and p + d and d_inv = 1.f / (F + Fn), every coordinate c with d_c = 1 becomes (V_c Fn + (V_c + vs_c) F)
+ *     d_inv; then aff.  On an axis edge this is dfusion_extract_cloud's point, bit for bit.  vertices_dev: float4 (x, y, z, 0)
+ *     in ascending (linear voxel index of the owner, slot);
+ *   - a cell (corners p + {0,1}^3) is meshed iff all 8 corners are valid; its 6 tetrahedra (axis permutations xyz, xzy, yxz, yzx,
+ *     zxy, zyx; corners p, p + e_a, p + e_a + e_b, p + (1,1,1)) give 0, 1 or 2 triangles each, turned so that the normal
+ *     (p1 - p0) x (p2 - p0) points from inside to outside.  triangles_dev: 3 uint32 vertex indices each, in ascending (linear cell
+ *     index, tetrahedron, triangle).  Triangles with coincident vertices (a corner's tsdf is exactly 0) are kept.
+ * With a slab: cells in planes [z_own0, z_end), z_end = min(z_own0 + z_own_n, dims[2] - 1), owners in planes [z_own0, z_end]
+ * restricted to edges that end in a plane <= z_end; plane z_end must be stored (one halo plane above, as for
+ * dfusion_extract_cloud).  A slab's mesh is complete on its own; neighbouring slabs repeat the vertices of the shared plane.
+ * counts_dev[0], [1] (device) are WRITTEN (not incremented): the number of vertices and of triangles the rule yields.  Nothing is
+ * written past either capacity; if a count exceeds its capacity the contents of BOTH arrays are unspecified (size the buffers
+ * and call again).  Both capacities 0 (arrays may be NULL): counts only, one pass over the volume.  Workspace: 32 bytes per 256
+ * voxels + 8 bytes per vertex of capacity, from the per-(device, stream) scratch of dfusion_integrate (dfusion_release_scratch).
+ * Vertex indices are 32-bit: meshes with more than 2^32 - 1 vertices are out of scope.  DF_E_INVALID for what
+ * dfusion_extract_cloud refuses, and for a NULL array with a non-zero capacity.                                                  */
+int dfusion_extract_mesh(DfVolume v, const DfSlab *slab, const float aff[12], float *vertices_dev,
+                         unsigned long long vertex_capacity, unsigned int *triangles_dev,
+                         unsigned long long triangle_capacity, unsigned long long *counts_dev, dfStream stream);
+
 /* ---- warp field -----------------------------------------------------------------------------
  * WarpField::WarpField / ~WarpField (warp_field.cpp:17-34).                                    */
 int dfusion_warp_create(DfWarpField **out);
