@@ -587,6 +587,239 @@ extern "C" int dfusion_warp_solve(DfWarpField* wf, int k, const float* canonical
     return df_sv_solve(wf, k, canonical, live, N, iters, lambda, kg, lambda_reg, dq_out, energy, stream);
 }
 
+// ---------------------------------------------------------------- robust solve: Tukey data term, Huber regularisation, IRLS
+// A round is one solve of above with weights: omega_v (Tukey, from the residual the round starts at) multiplied into the node-major copy
+// of the entry weights, omega_e (Huber, from the round's g_e) into a copy of alpha.  Everything that depends only on the canonical points and
+// the node positions (k-NN, exp weights, sort, lists, graph) is made once per call; the kernels of the plain solve are launched unchanged.
+
+// e0 at the transforms the handle holds now, from the stored entries: df_sv_setup_kernel's sums in its order (keys[e] = M: invalid point)
+__global__ __launch_bounds__(256) void df_sv_round_e0_kernel(const float* __restrict__ canonical, const float* __restrict__ live, int N, int k,
+                                                             const unsigned int* __restrict__ keys, const float* __restrict__ w,
+                                                             const float4* __restrict__ node_t, int M, float* __restrict__ e0)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= N) return;
+    const bool valid = keys[v * k] < (unsigned int)M;                   // (a point's k entries are valid together)
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    for (int j = 0; j < k; ++j) {
+        const int e = v * k + j;
+        const unsigned int n = keys[e];
+        if (valid && n < (unsigned int)M) {
+            const float wj = w[e];
+            const float4 t = node_t[n];
+            sx = sx + wj * t.y; sy = sy + wj * t.z; sz = sz + wj * t.w;
+        }
+    }
+    e0[3 * v] = valid ? (live[3 * v] - canonical[3 * v]) - sx : 0.f;
+    e0[3 * v + 1] = valid ? (live[3 * v + 1] - canonical[3 * v + 1]) - sy : 0.f;
+    e0[3 * v + 2] = valid ? (live[3 * v + 2] - canonical[3 * v + 2]) - sz : 0.f;
+}
+
+// omega_v = (1 - s / c^2)^2 for s = |e_v|^2 < c^2, else 0 (a NaN s compares false: 0)
+__global__ __launch_bounds__(256) void df_sv_tukey_kernel(const float* __restrict__ e, int N, float c2, float* __restrict__ omega)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= N) return;
+    const float ex = e[3 * v], ey = e[3 * v + 1], ez = e[3 * v + 2];
+    const float s = (ex * ex + ey * ey) + ez * ez;
+    const float u = 1.f - s / c2;
+    omega[v] = (s < c2) ? u * u : 0.f;
+}
+
+// sorted_w'[i] = omega_pt(i) * sorted_w[i]: list order, so the two entry reads and the write are coalesced; omega is a gather (ascending
+// point ids inside a node's list)
+__global__ __launch_bounds__(256) void df_sv_scale_list_kernel(const unsigned int* __restrict__ sorted_pt, const float* __restrict__ sorted_w,
+                                                               const float* __restrict__ omega, int E, float* __restrict__ scaled_w)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= E) return;
+    scaled_w[i] = omega[sorted_pt[i]] * sorted_w[i];
+}
+
+// omega_e = 1 for s = |g_e|^2 <= delta^2, else delta / |g_e|; alpha'_e = alpha_e * omega_e
+__global__ __launch_bounds__(256) void df_sv_huber_kernel(const float* __restrict__ g, const float* __restrict__ alpha, int E, float delta, float d2,
+                                                          float* __restrict__ omega_e, float* __restrict__ alpha_w)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    const float gx = g[3 * e], gy = g[3 * e + 1], gz = g[3 * e + 2];
+    const float s = (gx * gx + gy * gy) + gz * gz;
+    const float om = (s <= d2) ? 1.f : delta / sqrtf(s);
+    omega_e[e] = om;
+    alpha_w[e] = alpha[e] * om;
+}
+
+// ---- E_data = sum_v rho(|e_v|^2), rho(s) = c^2/3 (1 - (1 - s/c^2)^3) below c^2 and c^2/3 above: one value per point, thread t owns
+// points t, t + 1024, ..., then the 1024-tree (df_sv_energy_kernel's shape)
+__global__ __launch_bounds__(SV_BLOCK) void df_sv_tukey_energy_kernel(const float* __restrict__ e, int N, float c2, float* __restrict__ out)
+{
+    __shared__ float lds[3 * SV_BLOCK];
+    float acc[3] = {0.f, 0.f, 0.f};
+    const float third = c2 / 3.f;
+    for (int v = threadIdx.x; v < N; v += SV_BLOCK) {
+        const float ex = e[3 * v], ey = e[3 * v + 1], ez = e[3 * v + 2];
+        const float s = (ex * ex + ey * ey) + ez * ez;
+        const float u = 1.f - s / c2;
+        acc[0] = acc[0] + ((s < c2) ? third * (1.f - (u * u) * u) : third);
+    }
+    sv_block_sum3(acc, lds);
+    if (threadIdx.x == 0) *out = acc[0];
+}
+
+// ---- E_reg = sum_e alpha_e psi(|h_e|^2), h = (g_e + x_i) - x_j (x nullable = 0), psi(s) = s up to delta^2 and 2 delta sqrt(s) - delta^2 above
+__global__ __launch_bounds__(SV_BLOCK) void df_sv_huber_energy_kernel(const int* __restrict__ nbr, const float* __restrict__ alpha,
+                                                                      const float* __restrict__ g, const float* __restrict__ x, int E, int kg,
+                                                                      float delta, float d2, float* __restrict__ out)
+{
+    __shared__ float lds[3 * SV_BLOCK];
+    float acc[3] = {0.f, 0.f, 0.f};
+    const float two_delta = 2.f * delta;
+    for (int e = threadIdx.x; e < E; e += SV_BLOCK) {
+        const int i = e / kg, j = nbr[e];
+        float h[3];
+        for (int c = 0; c < 3; ++c) h[c] = x ? (g[3 * e + c] + x[3 * i + c]) - x[3 * j + c] : g[3 * e + c];
+        const float s = (h[0] * h[0] + h[1] * h[1]) + h[2] * h[2];
+        acc[0] = acc[0] + alpha[e] * ((s <= d2) ? s : two_delta * sqrtf(s) - d2);
+    }
+    sv_block_sum3(acc, lds);
+    if (threadIdx.x == 0) *out = acc[0];
+}
+
+extern "C" int dfusion_warp_solve_robust(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int kg,
+                                         float lambda_reg, int rounds, float tukey_c, float huber_delta, float* dq_out, float* energy,
+                                         float* point_weights, float* edge_weights, dfStream stream)
+{
+    if (!wf || !canonical || !live || N <= 0 || iters < 0 || !(lambda >= 0.f) || wf->M <= 0 || k < 1 || k > 8 || wf->M < k) return DF_E_INVALID;
+    if (kg < 0 || kg > 7 || (kg > 0 && wf->M < kg + 1) || !(lambda_reg >= 0.f)) return DF_E_INVALID;
+    if (rounds < 1 || !(tukey_c >= 0.f) || !(huber_delta >= 0.f)) return DF_E_INVALID;
+    const bool reg = kg > 0 && lambda_reg != 0.f;
+    if (!reg) kg = 0;
+    if (edge_weights && !reg) return DF_E_INVALID;
+    const bool tukey = tukey_c != 0.f, huber = reg && huber_delta != 0.f;
+    hipStream_t st = (hipStream_t)stream;
+    const int M = wf->M;
+    const size_t E = (size_t)N * k;
+    if (E > 0x7fffffffu) return DF_E_INVALID;
+    const int Eg = M * kg;                                              // graph edges (0: no regularisation)
+    if (!tukey && !huber && rounds == 1) {                              // all off: the plain solve, launch for launch
+        const int rc = dfusion_warp_solve(wf, k, canonical, live, N, iters, lambda, kg, lambda_reg, dq_out, energy, stream);
+        if (rc) return rc;
+        if (point_weights) DF_HIP(hipMemsetD32Async((hipDeviceptr_t)point_weights, 0x3f800000, (size_t)N, st));
+        if (edge_weights) DF_HIP(hipMemsetD32Async((hipDeviceptr_t)edge_weights, 0x3f800000, (size_t)Eg, st));
+        return DF_OK;
+    }
+    // workspace carve-up (256-byte aligned pieces): df_sv_solve's, then omega, sorted_w', alpha', omega_e
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_idx = take(E * 4), o_d2 = take(E * 4), o_w = take(E * 4), o_keys = take(E * 4), o_vals = take(E * 4), o_skeys = take(E * 4),
+                 o_svals = take(E * 4), o_spt = take(E * 4), o_sw = take(E * 4), o_e0 = take((size_t)N * 12), o_u = take((size_t)N * 12), o_off = take(((size_t)M + 2) * 4),
+                 o_x = take((size_t)M * 12), o_r = take((size_t)M * 12), o_p = take((size_t)M * 12), o_q = take((size_t)M * 12),
+                 o_scal = take(64), o_dq = take((size_t)M * 32), o_g = take((size_t)Eg * 12),
+                 o_om = take(tukey ? (size_t)N * 4 : 0), o_sw2 = take(tukey ? E * 4 : 0), o_al2 = take(huber ? (size_t)Eg * 4 : 0),
+                 o_ome = take(huber ? (size_t)Eg * 4 : 0);
+    size_t sort_bytes = 0;
+    DF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned int*)nullptr, (unsigned int*)nullptr, (const unsigned int*)nullptr,
+                                              (unsigned int*)nullptr, (int)E, 0, 17, st));
+    const size_t o_sort = take(sort_bytes);
+    int rc = wf->solver_ws.reserve(off);
+    if (rc) return rc;
+    char* ws = wf->solver_ws;
+    int* idx = (int*)(ws + o_idx); float* d2 = (float*)(ws + o_d2); float* w = (float*)(ws + o_w);
+    unsigned int* keys = (unsigned int*)(ws + o_keys); unsigned int* vals = (unsigned int*)(ws + o_vals);
+    unsigned int* skeys = (unsigned int*)(ws + o_skeys); unsigned int* svals = (unsigned int*)(ws + o_svals);
+    unsigned int* spt = (unsigned int*)(ws + o_spt); float* sw = (float*)(ws + o_sw);
+    float* e0 = (float*)(ws + o_e0); float* u = (float*)(ws + o_u); unsigned int* offs = (unsigned int*)(ws + o_off);
+    float* x = (float*)(ws + o_x); float* r = (float*)(ws + o_r); float* p = (float*)(ws + o_p); float* q = (float*)(ws + o_q);
+    float* scal = (float*)(ws + o_scal); float* dq = (float*)(ws + o_dq); float* g = (float*)(ws + o_g);
+    float* omega = (float*)(ws + o_om); float* omega_e = (float*)(ws + o_ome);
+    const float* const sw_use = tukey ? (float*)(ws + o_sw2) : sw;     // what W^T reads: the scaled copy, or the list as it is
+    float* const en = scal + 12;                                        // {E_data before, after, E_reg before, after}
+    const float c2 = tukey_c * tukey_c, dd2 = huber_delta * huber_delta;
+    if (reg) { rc = df_sv_graph(wf, kg, stream); if (rc) return rc; }
+    const float* const alpha_use = huber ? (float*)(ws + o_al2) : wf->graph_alpha.p;   // the handle's cached alpha is only read
+
+    // once per call: k-NN, weights, node-major lists (and round 1's e0)
+    rc = dfusion_knn(wf, k, canonical, N, idx, d2, stream);
+    if (rc) return rc;
+    const dim3 gN((N + 255) / 256), gM((M + 255) / 256), gE((unsigned)((E + 255) / 256)), gG((Eg + 255) / 256), gW(M);
+    hipLaunchKernelGGL(df_sv_setup_kernel, gN, dim3(256), 0, st, canonical, live, N, k, idx, d2, wf->pos_sigma, wf->node_t, M, w, keys, vals, e0);
+    DF_LAUNCH_CHECK();
+    DF_HIP(hipcub::DeviceRadixSort::SortPairs(ws + o_sort, sort_bytes, keys, skeys, vals, svals, (int)E, 0, 17, st));   // stable
+    hipLaunchKernelGGL(df_sv_offsets_kernel, dim3((unsigned)((E + 1 + 255) / 256)), dim3(256), 0, st, skeys, (int)E, M, offs);
+    DF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(df_sv_sorted_kernel, gE, dim3(256), 0, st, svals, w, (int)E, k, spt, sw);
+    DF_LAUNCH_CHECK();
+    auto step = M <= 2 * SV_BLOCK ? df_sv_step_reg_kernel<2> : M <= 5 * SV_BLOCK ? df_sv_step_reg_kernel<5> : M <= 8 * SV_BLOCK ? df_sv_step_reg_kernel<8> : df_sv_step_kernel;
+    auto w_apply = k == 8 ? df_sv_w_apply_kernel<8> : k == 4 ? df_sv_w_apply_kernel<4> : df_sv_w_apply_kernel<0>;
+    auto data_energy = [&](const float* e, float* out) {
+        if (tukey) hipLaunchKernelGGL(df_sv_tukey_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, e, N, c2, out);
+        else hipLaunchKernelGGL(df_sv_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, e, N, out);
+    };
+    auto reg_energy = [&](const float* xv, float* out) {                // (the energies weigh an edge with alpha_e itself, not alpha'_e)
+        if (huber) hipLaunchKernelGGL(df_sv_huber_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, wf->graph_nbr.p, wf->graph_alpha.p, g, xv, Eg, kg, huber_delta, dd2, out);
+        else hipLaunchKernelGGL(df_sv_reg_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, wf->graph_nbr.p, wf->graph_alpha.p, g, xv, Eg, kg, out);
+    };
+    for (int round = 0; round < rounds; ++round) {
+        const bool first = round == 0, last = round == rounds - 1;
+        if (!first) {                                                   // e0 at the transforms the previous round wrote
+            hipLaunchKernelGGL(df_sv_round_e0_kernel, gN, dim3(256), 0, st, canonical, live, N, k, keys, w, wf->node_t.p, M, e0);
+            DF_LAUNCH_CHECK();
+        }
+        if (tukey) {
+            hipLaunchKernelGGL(df_sv_tukey_kernel, gN, dim3(256), 0, st, e0, N, c2, omega);
+            hipLaunchKernelGGL(df_sv_scale_list_kernel, gE, dim3(256), 0, st, spt, sw, omega, (int)E, (float*)(ws + o_sw2));
+            DF_LAUNCH_CHECK();
+        }
+        if (energy && first) { data_energy(e0, en); DF_LAUNCH_CHECK(); }
+        // r0 = W^T Omega e0 - lambda_reg * b' ; p0 = r0 ; x0 = 0
+        hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, offs, spt, sw_use, M, e0, 0.f, (const float*)nullptr, r, (const float*)nullptr);
+        DF_LAUNCH_CHECK();
+        if (reg) {
+            hipLaunchKernelGGL(df_sv_reg_edge_kernel, gG, dim3(256), 0, st, wf->graph_nbr.p, wf->pos_sigma.p, wf->rot.p, wf->dual.p, Eg, kg, g);
+            if (huber) hipLaunchKernelGGL(df_sv_huber_kernel, gG, dim3(256), 0, st, g, wf->graph_alpha.p, Eg, huber_delta, dd2, omega_e, (float*)(ws + o_al2));
+            hipLaunchKernelGGL(df_sv_reg_rhs_kernel, gM, dim3(256), 0, st, alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg, g, lambda_reg, r);
+            if (energy && first) reg_energy(nullptr, en + 2);
+            DF_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(df_sv_init_kernel, dim3(1), dim3(SV_BLOCK), 0, st, r, M, x, p, scal);
+        DF_LAUNCH_CHECK();
+        for (int it = 0; it < iters; ++it) {
+            hipLaunchKernelGGL(w_apply, gN, dim3(256), 0, st, w, keys, N, k, M, p, u, (const float*)(scal + 3));
+            hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, offs, spt, sw_use, M, u, lambda, p, q, (const float*)(scal + 3));
+            if (reg) hipLaunchKernelGGL(df_sv_reg_apply_kernel, gM, dim3(256), 0, st, wf->graph_nbr.p, alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg, p,
+                                        lambda_reg, q, (const float*)(scal + 3));
+            hipLaunchKernelGGL(step, dim3(1), dim3(SV_BLOCK), 0, st, q, M, x, r, p, scal);
+            DF_LAUNCH_CHECK();
+        }
+        if (energy && last) {
+            hipLaunchKernelGGL(w_apply, gN, dim3(256), 0, st, w, keys, N, k, M, x, u, (const float*)nullptr);
+            hipLaunchKernelGGL(df_sv_residual_kernel, dim3((unsigned)((3 * (size_t)N + 255) / 256)), dim3(256), 0, st, e0, u, 3 * N, u);
+            data_energy(u, en + 1);
+            if (reg) reg_energy(x, en + 3);
+            DF_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(df_sv_writeback_kernel, gM, dim3(256), 0, st, wf->rot.p, wf->node_t.p, x, M, dq);
+        DF_LAUNCH_CHECK();
+        rc = dfusion_warp_set_transforms(wf, dq, stream);             // (the handle's rot / dual / node_t are the new ones from here on)
+        if (rc) return rc;
+    }
+    if (energy) {
+        DF_HIP(hipMemcpyAsync(energy, en, (reg ? 4 : 2) * sizeof(float), hipMemcpyDeviceToDevice, st));
+        static const float zeros[2] = {0.f, 0.f};
+        if (!reg) DF_HIP(hipMemcpyAsync(energy + 2, zeros, sizeof(zeros), hipMemcpyHostToDevice, st));
+    }
+    if (dq_out) DF_HIP(hipMemcpyAsync(dq_out, dq, (size_t)M * 32, hipMemcpyDeviceToDevice, st));
+    if (point_weights) {
+        if (tukey) DF_HIP(hipMemcpyAsync(point_weights, omega, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+        else DF_HIP(hipMemsetD32Async((hipDeviceptr_t)point_weights, 0x3f800000, (size_t)N, st));
+    }
+    if (edge_weights) {
+        if (huber) DF_HIP(hipMemcpyAsync(edge_weights, omega_e, (size_t)Eg * 4, hipMemcpyDeviceToDevice, st));
+        else DF_HIP(hipMemsetD32Async((hipDeviceptr_t)edge_weights, 0x3f800000, (size_t)Eg, st));
+    }
+    return DF_OK;
+}
+
 extern "C" int dfusion_warp_node_graph(DfWarpField* wf, int kg, int* nbr, float* alpha, dfStream stream)
 {
     if (!wf || !nbr || kg < 1 || kg > 7 || wf->M < kg + 1) return DF_E_INVALID;

@@ -86,6 +86,10 @@ namespace kfusion
         /// nearest other nodes with weight `lambda` (dfusion_warp_solve).  Off by default (neighbours = 0 or lambda = 0): energy_data is
         /// then the data term alone, as in the reference.
         void setRegularisation(int neighbours, float lambda) { reg_neighbours_ = neighbours; reg_lambda_ = lambda; }
+        /// DynamicFusion's robust penalties in energy_data (dfusion_warp_solve_robust): `rounds` re-weighted solves with a Tukey weight
+        /// (threshold `tukey_c`, metres) on every point and a Huber weight (threshold `huber_delta`) on every graph edge; a threshold of 0
+        /// keeps that term quadratic.  Off by default (rounds <= 1 and both thresholds 0): energy_data then takes exactly the path above.
+        void setRobust(int rounds, float tukey_c, float huber_delta) { robust_rounds_ = rounds; tukey_c_ = tukey_c; huber_delta_ = huber_delta; }
         /// E_reg before / after the last regularised energy_data (with setTrackEnergy; 0 while the term is off)
         float lastRegEnergyBefore() const { return last_energy_[2]; }
         float lastRegEnergyAfter() const { return last_energy_[3]; }
@@ -140,6 +144,8 @@ namespace kfusion
         float solver_lambda_ = 0.f;
         int reg_neighbours_ = 0;
         float reg_lambda_ = 0.f;
+        int robust_rounds_ = 1;
+        float tukey_c_ = 0.f, huber_delta_ = 0.f;
         float last_energy_[4] = {0.f, 0.f, 0.f, 0.f};
         bool track_energy_ = false;
     };

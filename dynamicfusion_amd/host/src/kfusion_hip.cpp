@@ -559,7 +559,12 @@ void WarpField::energy_data(const cuda::DeviceArray<float>& canonical_vertices, 
     const size_t M = nodes_.size();
     if (!M || n <= 0) return;
     solve_dq_.create(M * 8); solve_energy_.create(4);      // no-ops after the first frame
-    if (reg_neighbours_ != 0 && reg_lambda_ != 0.f)        // with the regularisation term over the node graph
+    const bool reg = reg_neighbours_ != 0 && reg_lambda_ != 0.f;
+    if (robust_rounds_ > 1 || tukey_c_ != 0.f || huber_delta_ != 0.f)   // robust penalties by re-weighted rounds (setRobust)
+        KF_DF(dfusion_warp_solve_robust(handle_, k_, canonical_vertices.ptr(), live_vertices.ptr(), n, solver_iters_, solver_lambda_,
+                                        reg ? reg_neighbours_ : 0, reg ? reg_lambda_ : 0.f, robust_rounds_, tukey_c_, huber_delta_, solve_dq_.ptr(),
+                                        track_energy_ ? solve_energy_.ptr() : nullptr, nullptr, nullptr, nullptr));
+    else if (reg)                                          // with the regularisation term over the node graph
         KF_DF(dfusion_warp_solve(handle_, k_, canonical_vertices.ptr(), live_vertices.ptr(), n, solver_iters_, solver_lambda_, reg_neighbours_,
                                  reg_lambda_, solve_dq_.ptr(), track_energy_ ? solve_energy_.ptr() : nullptr, nullptr));
     else
@@ -567,7 +572,7 @@ void WarpField::energy_data(const cuda::DeviceArray<float>& canonical_vertices, 
                                            track_energy_ ? solve_energy_.ptr() : nullptr, nullptr));
     if (track_energy_) {
         solve_energy_.download(last_energy_);
-        if (!(reg_neighbours_ != 0 && reg_lambda_ != 0.f)) last_energy_[2] = last_energy_[3] = 0.f;   // (the data term wrote two floats)
+        if (!reg) last_energy_[2] = last_energy_[3] = 0.f;   // (the data term wrote two floats)
     }
     nodes_stale_ = true;                                   // the host node store follows (updateWarp, optimisation.hpp:211-218) -- when it is looked at
 }
@@ -960,6 +965,7 @@ void KinFu::optimiseWarp(std::vector<Vec3f>& canonical, std::vector<Vec3f>& cano
     if (params_.warp_solver_iterations <= 0) return;
     warp_->setSolverIterations(params_.warp_solver_iterations);
     warp_->setRegularisation(params_.warp_reg_neighbours, params_.warp_reg_lambda);
+    warp_->setRobust(params_.warp_robust_rounds, params_.warp_tukey_c, params_.warp_huber_delta);
     warp_->energy_data(canonical, canonical_normals, live, canonical_normals);
 }
 
@@ -1101,6 +1107,7 @@ void KinFu::dynamicfusion(cuda::Depth& depth, cuda::Cloud live_frame, cuda::Norm
                                            depth.cols(), depth.rows(), nullptr, nullptr));
             warp_->setSolverIterations(params_.warp_solver_iterations);
             warp_->setRegularisation(params_.warp_reg_neighbours, params_.warp_reg_lambda);
+            warp_->setRobust(params_.warp_robust_rounds, params_.warp_tukey_c, params_.warp_huber_delta);
             warp_->energy_data(df_points3_, df_live3_, (int)n);
         }
         warp_->warp(df_points3_, df_normals3_, (int)n);                      // :391

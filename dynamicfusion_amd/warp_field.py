@@ -189,6 +189,33 @@ class WarpField:
         self._dq = dq
         return dq, en
 
+    def solve_robust(self, canonical_dev, live_dev, iters=100, lam=0.0, reg_neighbours=0, reg_lambda=0.0, rounds=3, tukey_c=0.0,
+                     huber_delta=0.0, k=None, return_weights=False):
+        """solve with DynamicFusion's robust penalties by iteratively re-weighted least squares (include/dfusion.h
+        dfusion_warp_solve_robust): `rounds` solves, each weighting every point with the Tukey weight of its residual (threshold
+        `tukey_c`, 0 = off) and every graph edge with the Huber weight of its difference (threshold `huber_delta`, 0 = off) at the
+        transforms the round starts from.  Returns (dq [M,8] device tensor, energy device tensor [E_data before, E_data after, E_reg
+        before, E_reg after]) and, with return_weights, (point_weights [N], edge_weights [M, reg_neighbours] or None without edges): the
+        last round's weights -- 0 marks a point the solve ignored."""
+        k = self.k if k is None else k
+        n = int(canonical_dev.shape[0])
+        kg = int(reg_neighbours)
+        dq = torch.empty((self.M, 8), dtype=torch.float32, device=self.device)
+        en = torch.zeros(4, dtype=torch.float32, device=self.device)
+        pw = ew = None
+        if return_weights:
+            pw = torch.empty(n, dtype=torch.float32, device=self.device)
+            if kg > 0 and float(reg_lambda) != 0.0:
+                ew = torch.empty((self.M, kg), dtype=torch.float32, device=self.device)
+        capi.check(capi.lib().dfusion_warp_solve_robust(self.handle, k, _flat(canonical_dev), _flat(live_dev), n, int(iters), float(lam), kg,
+                                                        float(reg_lambda), int(rounds), float(tukey_c), float(huber_delta), _ptr(dq), _ptr(en),
+                                                        _ptr(pw) if pw is not None else None, _ptr(ew) if ew is not None else None,
+                                                        _stream()), "dfusion_warp_solve_robust")
+        self._dq = dq
+        if return_weights:
+            return dq, en, pw, ew
+        return dq, en
+
     def node_graph(self, kg):
         """The graph solve() regularises over: (nbr int32 [M, kg], alpha float32 [M, kg]) device tensors -- node i's kg nearest other
         nodes and the edge weights max(dg_w_i, dg_w_j)."""

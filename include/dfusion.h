@@ -417,6 +417,27 @@ int dfusion_warp_solve_data_term(DfWarpField *wf, int k, const float *canonical_
  * DF_E_INVALID: what dfusion_warp_solve_data_term refuses, kg outside 0..7, kg > 0 with M < kg + 1, lambda_reg negative or NaN.         */
 int dfusion_warp_solve(DfWarpField *wf, int k, const float *canonical_dev, const float *live_dev, int N, int iters, float lambda,
                        int kg, float lambda_reg, float *dq_out_dev, float *energy_dev, dfStream stream);
+/* The robust form of dfusion_warp_solve (DynamicFusion section 3.3: Tukey penalty on the point residuals, eq. 7; Huber penalty on the
+ * edges, eq. 8) by iteratively re-weighted least squares -- an addition to ABI 7.  The call runs `rounds` rounds; a round is one
+ * dfusion_warp_solve with weights, starting from the transforms the previous round wrote:
+ *     e0 at the handle's transforms;   omega_v = (1 - s_v / c^2)^2 for s_v = |e0_v|^2 < c^2, else 0          (c = tukey_c)
+ *     g_e at the handle's transforms;  omega_e = 1 for s_e = |g_e|^2 <= delta^2, else delta / sqrt(s_e)      (delta = huber_delta)
+ *     `iters` conjugate-gradient steps on (W^T Omega W + lambda I + lambda_reg L') delta = W^T Omega e0 - lambda_reg b',
+ *     L' and b' with alpha'_e = alpha_e * omega_e; write back; dfusion_warp_set_transforms.
+ * The k-NN, the exp weights and the node-major lists are made once per call.  Omega enters through a scaled copy of the node-major entry
+ * weights, alpha' is a copy in the call's workspace: the handle's cached graph is only read.  Nothing returns to the host between rounds.
+ *   tukey_c      0 = quadratic data term;  huber_delta  0 = quadratic regularisation (also when kg == 0 or lambda_reg == 0: no edges)
+ *   energy_dev   (nullable) 4 floats: E_data before round 1, E_data after the last round, E_reg before, E_reg after -- the robust
+ *                energies sum_v c^2/3 (1 - (1 - s/c^2)^3) (c^2/3 from c^2 on) and sum_e alpha_e (s up to delta^2, 2 delta sqrt(s) - delta^2
+ *                above), which tend to the quadratic ones as the thresholds grow; a term switched off reports dfusion_warp_solve's value
+ *   point_weights_dev (nullable) [N] the last round's omega_v (1 everywhere with tukey_c == 0)
+ *   edge_weights_dev  (nullable) [M*kg] the last round's omega_e (1 everywhere with huber_delta == 0)
+ * Both thresholds 0 and rounds == 1: the call is dfusion_warp_solve, launch for launch; with rounds == R the transforms are those of R
+ * successive dfusion_warp_solve calls.  Restated in tests/solver_robust_ref.py.
+ * DF_E_INVALID: what dfusion_warp_solve refuses, rounds < 1, tukey_c or huber_delta negative or NaN, edge_weights_dev without edges.    */
+int dfusion_warp_solve_robust(DfWarpField *wf, int k, const float *canonical_dev, const float *live_dev, int N, int iters, float lambda,
+                              int kg, float lambda_reg, int rounds, float tukey_c, float huber_delta, float *dq_out_dev,
+                              float *energy_dev, float *point_weights_dev, float *edge_weights_dev, dfStream stream);
 /* The node graph dfusion_warp_solve uses for `kg` (1..7, M >= kg + 1; built now if the handle does not hold it):
  * nbr_dev[M*kg] int32 the head node of every edge, alpha_dev[M*kg] (nullable) the edge weights.                                      */
 int dfusion_warp_node_graph(DfWarpField *wf, int kg, int *nbr_dev, float *alpha_dev, dfStream stream);
