@@ -118,7 +118,7 @@ struct __attribute__((visibility("hidden"))) DfWarpField {     // (opaque in dfu
     DfDevBuf<unsigned long long> plan_mask2[2]; DfDevBuf<unsigned int> plan_list2[2]; int pphase = 0; unsigned hphase = 0;
     DfDevBuf<unsigned long long> plan_code2[2];      // per strip item: which of its (patch, layer) cells read 4-bit codes
     DfDevBuf<uint16_t> pyr_mem;             // max-pyramid of the frame's dists image (warped sweep's depth cull), entries
-    // scratch of dfusion_warp_solve_data_term (grown on demand)
+    // scratch of the warp solver (dfusion_solver.hip: one carve-up for its three entry points; grown on demand)
     DfDevBuf<char> solver_ws;
     // node graph of the regularised solve (dfusion_solver.hip): node i's graph_kg nearest other nodes nbr[M * kg], the edge weights
     // alpha[M * kg], the incoming edges of every node (CSR: in_off[M + 1] into in_edge, ascending edge ids) and the build's scratch.

@@ -15,9 +15,12 @@
 //                                       a fixed tree -- no float atomics, so the result is reproducible (and bit-comparable
 //                                       with the restatement in oracle/dfusion_frontend_oracle.c);
 //   dot products / vector updates     : one 1024-thread workgroup (M <= 65535), fixed tree.
-// dfusion_warp_solve adds DynamicFusion's regularisation term over a node graph to the same solve (second half of this file).
-// Nothing returns to the host between iterations: once every component has converged (scal[3] == 0) the kernels of the remaining
-// steps return at once.
+// dfusion_warp_solve adds DynamicFusion's regularisation term over a node graph, dfusion_warp_solve_robust a Tukey
+// penalty on the data term and a Huber penalty on the edges by re-weighted rounds.  The three entry points share one
+// host pipeline at the end of this file: one workspace (SvWorkspace), one preparation (df_sv_prepare: what depends only on the
+// canonical points and the node positions) and one round loop (df_sv_rounds), in which a term that is switched off launches nothing.
+// Nothing returns to the host between iterations: once every component has converged (scal[SV_ACTIVE] == 0) the kernels of the
+// remaining steps return at once.
 #include <hipcub/hipcub.hpp>
 #include "dfusion_internal.h"
 
@@ -75,7 +78,7 @@ __global__ __launch_bounds__(256) void df_sv_w_apply_kernel(const float* __restr
                                                             int M, const float* __restrict__ p, float* __restrict__ u,
                                                             const float* __restrict__ active)
 {
-    // `active` (nullable): scal[3], the number of CG components still iterating.  Once it is 0 every further step is an exact no-op
+    // `active` (nullable): scal + SV_ACTIVE, the number of CG components still iterating.  Once it is 0 every further step is an exact no-op
     // (alpha = beta = 0), so the kernels of the remaining steps return at once -- the host enqueues all steps without looking.
     if (active && *active == 0.f) return;
     const int v = blockIdx.x * 256 + threadIdx.x;
@@ -187,9 +190,14 @@ __device__ __forceinline__ void sv_block_sum3(float (&s)[3], float* lds /* [3][1
     __syncthreads();
 }
 
-// scal: [0..2] rr (0 = component converged / frozen), [3] number of components still iterating, [4] initial energy,
-// [5] final energy, [6..8] rr of the first residual (the convergence test is relative to it); the regularised solve reports through
-// [12..15] instead of [4], [5]: E_data before, after, E_reg before, after
+// scal, the solve's device scalars: the slots, per x / y / z component where there are three (4, 5 and 9 .. 11 are free)
+enum {
+    SV_RR = 0,          // [3] rr of the current residual (0 = component converged / frozen)
+    SV_ACTIVE = 3,      //     number of components still iterating
+    SV_RR0 = 6,         // [3] rr of the first residual (the convergence test is relative to it)
+    SV_ENERGY = 12,     // [4] E_data before, after, E_reg before, after (a data-only solve writes the first two)
+    SV_SCAL_N = 16
+};
 #define SV_REL_TOL2 1.0e-10f        // stop a component once |r|^2 <= 1e-10 |r0|^2
 __global__ __launch_bounds__(SV_BLOCK) void df_sv_init_kernel(const float* __restrict__ r, int M, float* __restrict__ x, float* __restrict__ p,
                                                               float* __restrict__ scal)
@@ -199,24 +207,46 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_init_kernel(const float* __res
     for (int n = threadIdx.x; n < M; n += SV_BLOCK)
         for (int c = 0; c < 3; ++c) { const float rv = r[3 * n + c]; x[3 * n + c] = 0.f; p[3 * n + c] = rv; s[c] = s[c] + rv * rv; }
     sv_block_sum3(s, lds);
-    if (threadIdx.x == 0) { scal[0] = s[0]; scal[1] = s[1]; scal[2] = s[2]; scal[6] = s[0]; scal[7] = s[1]; scal[8] = s[2];
-                            scal[3] = (float)((s[0] > 0.f) + (s[1] > 0.f) + (s[2] > 0.f)); }
+    if (threadIdx.x == 0) {
+        for (int c = 0; c < 3; ++c) { scal[SV_RR + c] = s[c]; scal[SV_RR0 + c] = s[c]; }
+        scal[SV_ACTIVE] = (float)((s[0] > 0.f) + (s[1] > 0.f) + (s[2] > 0.f));
+    }
+}
+
+// The scalar recurrence of a CG step, per component, for both step kernels below.
+__device__ __forceinline__ float sv_cg_alpha(float pq, float rr_old)
+{
+    return (pq > 0.f && rr_old > 0.f) ? rr_old / pq : 0.f;              // converged / degenerate component: frozen
+}
+
+__device__ __forceinline__ float sv_cg_beta(float alpha, float rr, float rr_old)
+{
+    return (alpha != 0.f && rr_old > 0.f) ? rr / rr_old : 0.f;
+}
+
+// one thread, once every thread has read scal's rr: the new rr (0 = frozen from here on) and the number of components left
+__device__ __forceinline__ void sv_cg_freeze(const float (&alpha)[3], const float (&rr)[3], float* scal)
+{
+    float active = 0.f;
+    for (int c = 0; c < 3; ++c) {
+        const float keep = (alpha[c] != 0.f && rr[c] > SV_REL_TOL2 * scal[SV_RR0 + c]) ? rr[c] : 0.f;
+        scal[SV_RR + c] = keep;
+        active += keep > 0.f ? 1.f : 0.f;
+    }
+    scal[SV_ACTIVE] = active;
 }
 
 __global__ __launch_bounds__(SV_BLOCK) void df_sv_step_kernel(const float* __restrict__ q, int M, float* __restrict__ x, float* __restrict__ r,
                                                               float* __restrict__ p, float* __restrict__ scal)
 {
     __shared__ float lds[3 * SV_BLOCK];
-    if (scal[3] == 0.f) return;                                         // all components frozen: the step would change nothing
+    if (scal[SV_ACTIVE] == 0.f) return;                                 // all components frozen: the step would change nothing
     float pq[3] = {0.f, 0.f, 0.f};
     for (int n = threadIdx.x; n < M; n += SV_BLOCK)
         for (int c = 0; c < 3; ++c) pq[c] = pq[c] + p[3 * n + c] * q[3 * n + c];
     sv_block_sum3(pq, lds);
     float alpha[3], rr_old[3];
-    for (int c = 0; c < 3; ++c) {
-        rr_old[c] = scal[c];
-        alpha[c] = (pq[c] > 0.f && rr_old[c] > 0.f) ? rr_old[c] / pq[c] : 0.f;        // converged / degenerate component: frozen
-    }
+    for (int c = 0; c < 3; ++c) { rr_old[c] = scal[SV_RR + c]; alpha[c] = sv_cg_alpha(pq[c], rr_old[c]); }
     float rr[3] = {0.f, 0.f, 0.f};
     for (int n = threadIdx.x; n < M; n += SV_BLOCK)
         for (int c = 0; c < 3; ++c) {
@@ -227,19 +257,11 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_step_kernel(const float* __res
         }
     sv_block_sum3(rr, lds);
     float beta[3];
-    for (int c = 0; c < 3; ++c) beta[c] = (alpha[c] != 0.f && rr_old[c] > 0.f) ? rr[c] / rr_old[c] : 0.f;
+    for (int c = 0; c < 3; ++c) beta[c] = sv_cg_beta(alpha[c], rr[c], rr_old[c]);
     for (int n = threadIdx.x; n < M; n += SV_BLOCK)
         for (int c = 0; c < 3; ++c) p[3 * n + c] = r[3 * n + c] + beta[c] * p[3 * n + c];
     __syncthreads();
-    if (threadIdx.x == 0) {
-        float active = 0.f;
-        for (int c = 0; c < 3; ++c) {
-            const float keep = (alpha[c] != 0.f && rr[c] > SV_REL_TOL2 * scal[6 + c]) ? rr[c] : 0.f;
-            scal[c] = keep;
-            active += keep > 0.f ? 1.f : 0.f;
-        }
-        scal[3] = active;
-    }
+    if (threadIdx.x == 0) sv_cg_freeze(alpha, rr, scal);
 }
 
 // df_sv_step_kernel for M <= EPT * SV_BLOCK: x, r, p, q are read once and stay in registers between the three passes (the passes of
@@ -249,7 +271,7 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_step_reg_kernel(const float* _
                                                                   float* __restrict__ p, float* __restrict__ scal)
 {
     __shared__ float lds[3 * SV_BLOCK];
-    if (scal[3] == 0.f) return;                                         // all components frozen: the step would change nothing
+    if (scal[SV_ACTIVE] == 0.f) return;                                 // all components frozen: the step would change nothing
     float pv[EPT][3], qv[EPT][3], rv[EPT][3], xv[EPT][3];
 #pragma unroll
     for (int j = 0; j < EPT; ++j) {
@@ -269,10 +291,7 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_step_reg_kernel(const float* _
             for (int c = 0; c < 3; ++c) pq[c] = pq[c] + pv[j][c] * qv[j][c];
     sv_block_sum3(pq, lds);
     float alpha[3], rr_old[3];
-    for (int c = 0; c < 3; ++c) {
-        rr_old[c] = scal[c];
-        alpha[c] = (pq[c] > 0.f && rr_old[c] > 0.f) ? rr_old[c] / pq[c] : 0.f;
-    }
+    for (int c = 0; c < 3; ++c) { rr_old[c] = scal[SV_RR + c]; alpha[c] = sv_cg_alpha(pq[c], rr_old[c]); }
     float rr[3] = {0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < EPT; ++j)
@@ -285,7 +304,7 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_step_reg_kernel(const float* _
             }
     sv_block_sum3(rr, lds);
     float beta[3];
-    for (int c = 0; c < 3; ++c) beta[c] = (alpha[c] != 0.f && rr_old[c] > 0.f) ? rr[c] / rr_old[c] : 0.f;
+    for (int c = 0; c < 3; ++c) beta[c] = sv_cg_beta(alpha[c], rr[c], rr_old[c]);
 #pragma unroll
     for (int j = 0; j < EPT; ++j) {
         const int n = threadIdx.x + j * SV_BLOCK;
@@ -293,15 +312,7 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_step_reg_kernel(const float* _
 #pragma unroll
             for (int c = 0; c < 3; ++c) { x[3 * n + c] = xv[j][c]; r[3 * n + c] = rv[j][c]; p[3 * n + c] = rv[j][c] + beta[c] * pv[j][c]; }
     }
-    if (threadIdx.x == 0) {
-        float active = 0.f;
-        for (int c = 0; c < 3; ++c) {
-            const float keep = (alpha[c] != 0.f && rr[c] > SV_REL_TOL2 * scal[6 + c]) ? rr[c] : 0.f;
-            scal[c] = keep;
-            active += keep > 0.f ? 1.f : 0.f;
-        }
-        scal[3] = active;
-    }
+    if (threadIdx.x == 0) sv_cg_freeze(alpha, rr, scal);
 }
 
 // ---- energy = sum_v |e_v|^2 (single workgroup, same tree)
@@ -448,149 +459,9 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_reg_energy_kernel(const int* _
     if (threadIdx.x == 0) *out = (s[0] + s[1]) + s[2];
 }
 
-// The node graph of the handle for `kg` neighbours, made on first use and kept until the node set changes (graph_kg = 0).
-static int df_sv_graph(DfWarpField* wf, int kg, dfStream stream)
-{
-    if (wf->graph_kg == kg) return DF_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int M = wf->M, kq = kg + 1;
-    const size_t E = (size_t)M * kg;
-    wf->graph_kg = 0;
-    int rc;
-    if ((rc = wf->graph_nbr.reserve(E)) || (rc = wf->graph_alpha.reserve(E)) || (rc = wf->graph_in_off.reserve((size_t)M + 2)) ||
-        (rc = wf->graph_in_edge.reserve(E))) return rc;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_pos = take((size_t)M * 12), o_idx = take((size_t)M * kq * 4), o_d2 = take((size_t)M * kq * 4), o_keys = take(E * 4),
-                 o_vals = take(E * 4), o_skeys = take(E * 4);
-    size_t sort_bytes = 0;
-    DF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned int*)nullptr, (unsigned int*)nullptr, (const unsigned int*)nullptr,
-                                              (unsigned int*)nullptr, (int)E, 0, 16, st));
-    const size_t o_sort = take(sort_bytes);
-    if ((rc = wf->graph_ws.reserve(off))) return rc;
-    char* ws = wf->graph_ws;
-    float* pos3 = (float*)(ws + o_pos); int* idx = (int*)(ws + o_idx); float* d2 = (float*)(ws + o_d2);
-    unsigned int* keys = (unsigned int*)(ws + o_keys); unsigned int* vals = (unsigned int*)(ws + o_vals);
-    unsigned int* skeys = (unsigned int*)(ws + o_skeys);
-    const dim3 gM((M + 255) / 256);
-    hipLaunchKernelGGL(df_sv_graph_pos_kernel, gM, dim3(256), 0, st, wf->pos_sigma, M, pos3);
-    DF_LAUNCH_CHECK();
-    if ((rc = dfusion_knn(wf, kq, pos3, M, idx, d2, stream))) return rc;
-    hipLaunchKernelGGL(df_sv_graph_kernel, gM, dim3(256), 0, st, idx, wf->pos_sigma, M, kg, wf->graph_nbr.p, wf->graph_alpha.p, keys, vals);
-    DF_LAUNCH_CHECK();
-    DF_HIP(hipcub::DeviceRadixSort::SortPairs(ws + o_sort, sort_bytes, keys, skeys, vals, wf->graph_in_edge.p, (int)E, 0, 16, st));   // stable
-    hipLaunchKernelGGL(df_sv_offsets_kernel, dim3((unsigned)((E + 1 + 255) / 256)), dim3(256), 0, st, skeys, (int)E, M, wf->graph_in_off);
-    DF_LAUNCH_CHECK();
-    wf->graph_kg = kg;
-    return DF_OK;
-}
-
-// The solve behind both entry points.  kg = 0: the data term alone -- exactly the launches dfusion_warp_solve_data_term always made,
-// energy = 2 floats.  kg > 0: with lambda_reg * E_reg, energy = 4 floats {E_data before, after, E_reg before, after}.
-static int df_sv_solve(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int kg,
-                       float lambda_reg, float* dq_out, float* energy, dfStream stream)
-{
-    if (!wf || !canonical || !live || N <= 0 || iters < 0 || !(lambda >= 0.f) || wf->M <= 0 || k < 1 || k > 8 || wf->M < k) return DF_E_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    const int M = wf->M;
-    const size_t E = (size_t)N * k;
-    if (E > 0x7fffffffu) return DF_E_INVALID;
-    // workspace carve-up (256-byte aligned pieces)
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_idx = take(E * 4), o_d2 = take(E * 4), o_w = take(E * 4), o_keys = take(E * 4), o_vals = take(E * 4), o_skeys = take(E * 4),
-                 o_svals = take(E * 4), o_spt = take(E * 4), o_sw = take(E * 4), o_e0 = take((size_t)N * 12), o_u = take((size_t)N * 12), o_off = take(((size_t)M + 2) * 4),
-                 o_x = take((size_t)M * 12), o_r = take((size_t)M * 12), o_p = take((size_t)M * 12), o_q = take((size_t)M * 12),
-                 o_scal = take(64), o_dq = take((size_t)M * 32);
-    const int Eg = M * kg;                                              // graph edges (0: no regularisation)
-    const size_t o_g = take((size_t)Eg * 12);
-    size_t sort_bytes = 0;
-    DF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned int*)nullptr, (unsigned int*)nullptr, (const unsigned int*)nullptr,
-                                              (unsigned int*)nullptr, (int)E, 0, 17, st));
-    const size_t o_sort = take(sort_bytes);
-    int rc = wf->solver_ws.reserve(off);
-    if (rc) return rc;
-    char* ws = wf->solver_ws;
-    int* idx = (int*)(ws + o_idx); float* d2 = (float*)(ws + o_d2); float* w = (float*)(ws + o_w);
-    unsigned int* keys = (unsigned int*)(ws + o_keys); unsigned int* vals = (unsigned int*)(ws + o_vals);
-    unsigned int* skeys = (unsigned int*)(ws + o_skeys); unsigned int* svals = (unsigned int*)(ws + o_svals);
-    unsigned int* spt = (unsigned int*)(ws + o_spt); float* sw = (float*)(ws + o_sw);
-    float* e0 = (float*)(ws + o_e0); float* u = (float*)(ws + o_u); unsigned int* offs = (unsigned int*)(ws + o_off);
-    float* x = (float*)(ws + o_x); float* r = (float*)(ws + o_r); float* p = (float*)(ws + o_p); float* q = (float*)(ws + o_q);
-    float* scal = (float*)(ws + o_scal); float* dq = (float*)(ws + o_dq); float* g = (float*)(ws + o_g);
-    float* const en = kg ? scal + 12 : scal + 4;                        // {E_data before, after} and, regularised, {E_reg before, after}
-    if (kg) { rc = df_sv_graph(wf, kg, stream); if (rc) return rc; }
-
-    rc = dfusion_knn(wf, k, canonical, N, idx, d2, stream);           // getWeightsAndUpdateKNN's k-NN (NaN queries are masked below)
-    if (rc) return rc;
-    const dim3 gN((N + 255) / 256), gM((M + 255) / 256);
-    hipLaunchKernelGGL(df_sv_setup_kernel, gN, dim3(256), 0, st, canonical, live, N, k, idx, d2, wf->pos_sigma, wf->node_t, M, w, keys, vals, e0);
-    DF_LAUNCH_CHECK();
-    DF_HIP(hipcub::DeviceRadixSort::SortPairs(ws + o_sort, sort_bytes, keys, skeys, vals, svals, (int)E, 0, 17, st));   // stable
-    hipLaunchKernelGGL(df_sv_offsets_kernel, dim3((unsigned)((E + 1 + 255) / 256)), dim3(256), 0, st, skeys, (int)E, M, offs);
-    DF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(df_sv_sorted_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, svals, w, (int)E, k, spt, sw);
-    DF_LAUNCH_CHECK();
-    if (energy) { hipLaunchKernelGGL(df_sv_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, e0, N, en); DF_LAUNCH_CHECK(); }
-    auto step = M <= 2 * SV_BLOCK ? df_sv_step_reg_kernel<2> : M <= 5 * SV_BLOCK ? df_sv_step_reg_kernel<5> : M <= 8 * SV_BLOCK ? df_sv_step_reg_kernel<8> : df_sv_step_kernel;
-    auto w_apply = k == 8 ? df_sv_w_apply_kernel<8> : k == 4 ? df_sv_w_apply_kernel<4> : df_sv_w_apply_kernel<0>;
-    // r0 = W^T e0 ; p0 = r0 ; x0 = 0
-    const dim3 gW(M);
-    hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, offs, spt, sw, M, e0, 0.f, (const float*)nullptr, r, (const float*)nullptr);
-    DF_LAUNCH_CHECK();
-    if (kg) {                                                           // r0 = W^T e0 - lambda_reg * b
-        hipLaunchKernelGGL(df_sv_reg_edge_kernel, dim3((Eg + 255) / 256), dim3(256), 0, st, wf->graph_nbr, wf->pos_sigma, wf->rot, wf->dual, Eg, kg, g);
-        hipLaunchKernelGGL(df_sv_reg_rhs_kernel, gM, dim3(256), 0, st, wf->graph_alpha, wf->graph_in_off, wf->graph_in_edge, M, kg, g, lambda_reg, r);
-        if (energy) hipLaunchKernelGGL(df_sv_reg_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, wf->graph_nbr, wf->graph_alpha, g, (const float*)nullptr, Eg, kg, en + 2);
-        DF_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(df_sv_init_kernel, dim3(1), dim3(SV_BLOCK), 0, st, r, M, x, p, scal);
-    DF_LAUNCH_CHECK();
-    for (int it = 0; it < iters; ++it) {
-        hipLaunchKernelGGL(w_apply, gN, dim3(256), 0, st, w, keys, N, k, M, p, u, (const float*)(scal + 3));
-        hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, offs, spt, sw, M, u, lambda, p, q, (const float*)(scal + 3));
-        if (kg) hipLaunchKernelGGL(df_sv_reg_apply_kernel, gM, dim3(256), 0, st, wf->graph_nbr, wf->graph_alpha, wf->graph_in_off, wf->graph_in_edge, M, kg, p,
-                                   lambda_reg, q, (const float*)(scal + 3));
-        hipLaunchKernelGGL(step, dim3(1), dim3(SV_BLOCK), 0, st, q, M, x, r, p, scal);
-        DF_LAUNCH_CHECK();
-    }
-    if (energy) {
-        hipLaunchKernelGGL(w_apply, gN, dim3(256), 0, st, w, keys, N, k, M, x, u, (const float*)nullptr);
-        hipLaunchKernelGGL(df_sv_residual_kernel, dim3((unsigned)((3 * (size_t)N + 255) / 256)), dim3(256), 0, st, e0, u, 3 * N, u);
-        hipLaunchKernelGGL(df_sv_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, u, N, en + 1);
-        if (kg) hipLaunchKernelGGL(df_sv_reg_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, wf->graph_nbr, wf->graph_alpha, g, (const float*)x, Eg, kg, en + 3);
-        DF_LAUNCH_CHECK();
-        DF_HIP(hipMemcpyAsync(energy, en, (kg ? 4 : 2) * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
-    hipLaunchKernelGGL(df_sv_writeback_kernel, gM, dim3(256), 0, st, wf->rot, wf->node_t, x, M, dq);
-    DF_LAUNCH_CHECK();
-    if (dq_out) DF_HIP(hipMemcpyAsync(dq_out, dq, (size_t)M * 32, hipMemcpyDeviceToDevice, st));
-    return dfusion_warp_set_transforms(wf, dq, stream);
-}
-
-extern "C" int dfusion_warp_solve_data_term(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda,
-                                            float* dq_out, float* energy, dfStream stream)
-{
-    return df_sv_solve(wf, k, canonical, live, N, iters, lambda, 0, 0.f, dq_out, energy, stream);
-}
-
-extern "C" int dfusion_warp_solve(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int kg,
-                                  float lambda_reg, float* dq_out, float* energy, dfStream stream)
-{
-    if (!wf || kg < 0 || kg > 7 || (kg > 0 && wf->M < kg + 1) || !(lambda_reg >= 0.f)) return DF_E_INVALID;
-    if (kg == 0 || lambda_reg == 0.f) {                                 // off: the data-term call, bit for bit and launch for launch
-        const int rc = df_sv_solve(wf, k, canonical, live, N, iters, lambda, 0, 0.f, dq_out, energy, stream);
-        static const float zeros[2] = {0.f, 0.f};                       // (a copy from the host, not a fill: no kernel of any kind is added)
-        if (rc == DF_OK && energy) DF_HIP(hipMemcpyAsync(energy + 2, zeros, sizeof(zeros), hipMemcpyHostToDevice, (hipStream_t)stream));
-        return rc;
-    }
-    return df_sv_solve(wf, k, canonical, live, N, iters, lambda, kg, lambda_reg, dq_out, energy, stream);
-}
-
 // ---------------------------------------------------------------- robust solve: Tukey data term, Huber regularisation, IRLS
 // A round is one solve of above with weights: omega_v (Tukey, from the residual the round starts at) multiplied into the node-major copy
-// of the entry weights, omega_e (Huber, from the round's g_e) into a copy of alpha.  Everything that depends only on the canonical points and
-// the node positions (k-NN, exp weights, sort, lists, graph) is made once per call; the kernels of the plain solve are launched unchanged.
+// of the entry weights, omega_e (Huber, from the round's g_e) into a copy of alpha; the kernels above are launched unchanged.
 
 // e0 at the transforms the handle holds now, from the stored entries: df_sv_setup_kernel's sums in its order (keys[e] = M: invalid point)
 __global__ __launch_bounds__(256) void df_sv_round_e0_kernel(const float* __restrict__ canonical, const float* __restrict__ live, int N, int k,
@@ -685,139 +556,250 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_huber_energy_kernel(const int*
     if (threadIdx.x == 0) *out = acc[0];
 }
 
-extern "C" int dfusion_warp_solve_robust(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int kg,
-                                         float lambda_reg, int rounds, float tukey_c, float huber_delta, float* dq_out, float* energy,
-                                         float* point_weights, float* edge_weights, dfStream stream)
-{
-    if (!wf || !canonical || !live || N <= 0 || iters < 0 || !(lambda >= 0.f) || wf->M <= 0 || k < 1 || k > 8 || wf->M < k) return DF_E_INVALID;
-    if (kg < 0 || kg > 7 || (kg > 0 && wf->M < kg + 1) || !(lambda_reg >= 0.f)) return DF_E_INVALID;
-    if (rounds < 1 || !(tukey_c >= 0.f) || !(huber_delta >= 0.f)) return DF_E_INVALID;
-    const bool reg = kg > 0 && lambda_reg != 0.f;
-    if (!reg) kg = 0;
-    if (edge_weights && !reg) return DF_E_INVALID;
-    const bool tukey = tukey_c != 0.f, huber = reg && huber_delta != 0.f;
-    hipStream_t st = (hipStream_t)stream;
-    const int M = wf->M;
-    const size_t E = (size_t)N * k;
-    if (E > 0x7fffffffu) return DF_E_INVALID;
-    const int Eg = M * kg;                                              // graph edges (0: no regularisation)
-    if (!tukey && !huber && rounds == 1) {                              // all off: the plain solve, launch for launch
-        const int rc = dfusion_warp_solve(wf, k, canonical, live, N, iters, lambda, kg, lambda_reg, dq_out, energy, stream);
-        if (rc) return rc;
-        if (point_weights) DF_HIP(hipMemsetD32Async((hipDeviceptr_t)point_weights, 0x3f800000, (size_t)N, st));
-        if (edge_weights) DF_HIP(hipMemsetD32Async((hipDeviceptr_t)edge_weights, 0x3f800000, (size_t)Eg, st));
-        return DF_OK;
+// ---------------------------------------------------------------- host side
+// 256-byte aligned pieces of one buffer.  A carve-up is written once and run twice: from base 0, where `at` ends as the size to
+// reserve, and from the reserved buffer's address.
+struct SvBump {
+    uintptr_t at;
+    template <typename T> T* take(size_t count)
+    {
+        T* const p = (T*)at;
+        at += (count * sizeof(T) + 255) & ~(uintptr_t)255;
+        return p;
     }
-    // workspace carve-up (256-byte aligned pieces): df_sv_solve's, then omega, sorted_w', alpha', omega_e
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_idx = take(E * 4), o_d2 = take(E * 4), o_w = take(E * 4), o_keys = take(E * 4), o_vals = take(E * 4), o_skeys = take(E * 4),
-                 o_svals = take(E * 4), o_spt = take(E * 4), o_sw = take(E * 4), o_e0 = take((size_t)N * 12), o_u = take((size_t)N * 12), o_off = take(((size_t)M + 2) * 4),
-                 o_x = take((size_t)M * 12), o_r = take((size_t)M * 12), o_p = take((size_t)M * 12), o_q = take((size_t)M * 12),
-                 o_scal = take(64), o_dq = take((size_t)M * 32), o_g = take((size_t)Eg * 12),
-                 o_om = take(tukey ? (size_t)N * 4 : 0), o_sw2 = take(tukey ? E * 4 : 0), o_al2 = take(huber ? (size_t)Eg * 4 : 0),
-                 o_ome = take(huber ? (size_t)Eg * 4 : 0);
-    size_t sort_bytes = 0;
-    DF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned int*)nullptr, (unsigned int*)nullptr, (const unsigned int*)nullptr,
-                                              (unsigned int*)nullptr, (int)E, 0, 17, st));
-    const size_t o_sort = take(sort_bytes);
-    int rc = wf->solver_ws.reserve(off);
-    if (rc) return rc;
-    char* ws = wf->solver_ws;
-    int* idx = (int*)(ws + o_idx); float* d2 = (float*)(ws + o_d2); float* w = (float*)(ws + o_w);
-    unsigned int* keys = (unsigned int*)(ws + o_keys); unsigned int* vals = (unsigned int*)(ws + o_vals);
-    unsigned int* skeys = (unsigned int*)(ws + o_skeys); unsigned int* svals = (unsigned int*)(ws + o_svals);
-    unsigned int* spt = (unsigned int*)(ws + o_spt); float* sw = (float*)(ws + o_sw);
-    float* e0 = (float*)(ws + o_e0); float* u = (float*)(ws + o_u); unsigned int* offs = (unsigned int*)(ws + o_off);
-    float* x = (float*)(ws + o_x); float* r = (float*)(ws + o_r); float* p = (float*)(ws + o_p); float* q = (float*)(ws + o_q);
-    float* scal = (float*)(ws + o_scal); float* dq = (float*)(ws + o_dq); float* g = (float*)(ws + o_g);
-    float* omega = (float*)(ws + o_om); float* omega_e = (float*)(ws + o_ome);
-    const float* const sw_use = tukey ? (float*)(ws + o_sw2) : sw;     // what W^T reads: the scaled copy, or the list as it is
-    float* const en = scal + 12;                                        // {E_data before, after, E_reg before, after}
-    const float c2 = tukey_c * tukey_c, dd2 = huber_delta * huber_delta;
-    if (reg) { rc = df_sv_graph(wf, kg, stream); if (rc) return rc; }
-    const float* const alpha_use = huber ? (float*)(ws + o_al2) : wf->graph_alpha.p;   // the handle's cached alpha is only read
+};
 
-    // once per call: k-NN, weights, node-major lists (and round 1's e0)
-    rc = dfusion_knn(wf, k, canonical, N, idx, d2, stream);
-    if (rc) return rc;
-    const dim3 gN((N + 255) / 256), gM((M + 255) / 256), gE((unsigned)((E + 255) / 256)), gG((Eg + 255) / 256), gW(M);
-    hipLaunchKernelGGL(df_sv_setup_kernel, gN, dim3(256), 0, st, canonical, live, N, k, idx, d2, wf->pos_sigma, wf->node_t, M, w, keys, vals, e0);
+// scratch bytes of the stable radix sort of E (key, value) pairs of unsigned int on key bits [0, end_bit)
+static int df_sv_sort_bytes(size_t E, int end_bit, hipStream_t st, size_t* bytes)
+{
+    *bytes = 0;
+    DF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, *bytes, (const unsigned int*)nullptr, (unsigned int*)nullptr, (const unsigned int*)nullptr,
+                                              (unsigned int*)nullptr, (int)E, 0, end_bit, st));
+    return DF_OK;
+}
+
+// The node graph of the handle for `kg` neighbours, made on first use and kept until the node set changes (graph_kg = 0).
+static int df_sv_graph(DfWarpField* wf, int kg, dfStream stream)
+{
+    if (wf->graph_kg == kg) return DF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int M = wf->M, kq = kg + 1;
+    const size_t E = (size_t)M * kg;
+    wf->graph_kg = 0;
+    int rc;
+    if ((rc = wf->graph_nbr.reserve(E)) || (rc = wf->graph_alpha.reserve(E)) || (rc = wf->graph_in_off.reserve((size_t)M + 2)) ||
+        (rc = wf->graph_in_edge.reserve(E))) return rc;
+    size_t sort_bytes;
+    if ((rc = df_sv_sort_bytes(E, 16, st, &sort_bytes))) return rc;
+    float *pos3, *d2; int* idx; unsigned int *keys, *vals, *skeys; char* sort;
+    auto carve = [&](char* base) {
+        SvBump b{(uintptr_t)base};
+        pos3 = b.take<float>((size_t)M * 3); idx = b.take<int>((size_t)M * kq); d2 = b.take<float>((size_t)M * kq);
+        keys = b.take<unsigned int>(E); vals = b.take<unsigned int>(E); skeys = b.take<unsigned int>(E); sort = b.take<char>(sort_bytes);
+        return (size_t)(b.at - (uintptr_t)base);
+    };
+    if ((rc = wf->graph_ws.reserve(carve(nullptr)))) return rc;
+    carve(wf->graph_ws);
+    const dim3 gM((M + 255) / 256);
+    hipLaunchKernelGGL(df_sv_graph_pos_kernel, gM, dim3(256), 0, st, wf->pos_sigma, M, pos3);
     DF_LAUNCH_CHECK();
-    DF_HIP(hipcub::DeviceRadixSort::SortPairs(ws + o_sort, sort_bytes, keys, skeys, vals, svals, (int)E, 0, 17, st));   // stable
-    hipLaunchKernelGGL(df_sv_offsets_kernel, dim3((unsigned)((E + 1 + 255) / 256)), dim3(256), 0, st, skeys, (int)E, M, offs);
+    if ((rc = dfusion_knn(wf, kq, pos3, M, idx, d2, stream))) return rc;
+    hipLaunchKernelGGL(df_sv_graph_kernel, gM, dim3(256), 0, st, idx, wf->pos_sigma, M, kg, wf->graph_nbr.p, wf->graph_alpha.p, keys, vals);
     DF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(df_sv_sorted_kernel, gE, dim3(256), 0, st, svals, w, (int)E, k, spt, sw);
+    DF_HIP(hipcub::DeviceRadixSort::SortPairs(sort, sort_bytes, keys, skeys, vals, wf->graph_in_edge.p, (int)E, 0, 16, st));   // stable
+    hipLaunchKernelGGL(df_sv_offsets_kernel, dim3((unsigned)((E + 1 + 255) / 256)), dim3(256), 0, st, skeys, (int)E, M, wf->graph_in_off);
     DF_LAUNCH_CHECK();
+    wf->graph_kg = kg;
+    return DF_OK;
+}
+
+// The solve's scratch, carved from wf->solver_ws.  E = N * k entries, Eg = M * kg graph edges.
+struct SvWorkspace {
+    int* idx; float* d2;                                    // [E] the k-NN's output
+    float* w; unsigned int *keys, *vals;                    // [E] point-major entries: weight, node id (M: invalid point), entry id
+    unsigned int *skeys, *svals;                            // [E] the sort's output
+    unsigned int* spt; float* sw;                           // [E] node-major entries: point id, weight
+    float *e0, *u;                                          // [3N] residual the round starts at ; W p, then the final residual
+    unsigned int* off;                                      // [M + 2] node offsets into the node-major entries
+    float *x, *r, *p, *q;                                   // [3M] conjugate gradients
+    float* scal;                                            // [SV_SCAL_N]
+    float* dq;                                              // [8M] the transforms a round writes
+    float* g;                                               // [3Eg] edge values
+    float *omega, *sw_scaled;                               // [N], [E] Tukey: point weights, sorted_w' (no Tukey: empty)
+    float *alpha_scaled, *omega_e;                          // [Eg] Huber: alpha', edge weights (no Huber: empty)
+    char* sort; size_t sort_bytes;
+};
+
+static int df_sv_workspace(DfWarpField* wf, int N, int k, int M, int Eg, bool tukey, bool huber, hipStream_t st, SvWorkspace* ws)
+{
+    const size_t E = (size_t)N * k, n = N, m = M, eg = Eg;
+    int rc;
+    if ((rc = df_sv_sort_bytes(E, 17, st, &ws->sort_bytes))) return rc;
+    auto carve = [&](char* base) {
+        SvBump b{(uintptr_t)base};
+        ws->idx = b.take<int>(E); ws->d2 = b.take<float>(E); ws->w = b.take<float>(E);
+        ws->keys = b.take<unsigned int>(E); ws->vals = b.take<unsigned int>(E);
+        ws->skeys = b.take<unsigned int>(E); ws->svals = b.take<unsigned int>(E);
+        ws->spt = b.take<unsigned int>(E); ws->sw = b.take<float>(E);
+        ws->e0 = b.take<float>(3 * n); ws->u = b.take<float>(3 * n); ws->off = b.take<unsigned int>(m + 2);
+        ws->x = b.take<float>(3 * m); ws->r = b.take<float>(3 * m); ws->p = b.take<float>(3 * m); ws->q = b.take<float>(3 * m);
+        ws->scal = b.take<float>(SV_SCAL_N); ws->dq = b.take<float>(8 * m); ws->g = b.take<float>(3 * eg);
+        ws->omega = b.take<float>(tukey ? n : 0); ws->sw_scaled = b.take<float>(tukey ? E : 0);
+        ws->alpha_scaled = b.take<float>(huber ? eg : 0); ws->omega_e = b.take<float>(huber ? eg : 0);
+        ws->sort = b.take<char>(ws->sort_bytes);
+        return (size_t)(b.at - (uintptr_t)base);
+    };
+    if ((rc = wf->solver_ws.reserve(carve(nullptr)))) return rc;
+    carve(wf->solver_ws);
+    return DF_OK;
+}
+
+// Once per call, what depends only on the canonical points and the node positions: the graph (kg > 0), the k-NN, the entries' weights
+// and node ids (with e0 at the transforms the handle holds now), the node offsets and the node-major lists.
+static int df_sv_prepare(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int kg, const SvWorkspace& ws, dfStream stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const int M = wf->M, E = N * k;
+    size_t sort_bytes = ws.sort_bytes;
+    int rc;
+    if (kg && (rc = df_sv_graph(wf, kg, stream))) return rc;
+    if ((rc = dfusion_knn(wf, k, canonical, N, ws.idx, ws.d2, stream))) return rc;   // getWeightsAndUpdateKNN's k-NN (NaN queries are masked below)
+    hipLaunchKernelGGL(df_sv_setup_kernel, dim3((N + 255) / 256), dim3(256), 0, st, canonical, live, N, k, ws.idx, ws.d2, wf->pos_sigma, wf->node_t, M,
+                       ws.w, ws.keys, ws.vals, ws.e0);
+    DF_LAUNCH_CHECK();
+    DF_HIP(hipcub::DeviceRadixSort::SortPairs(ws.sort, sort_bytes, ws.keys, ws.skeys, ws.vals, ws.svals, E, 0, 17, st));   // stable
+    hipLaunchKernelGGL(df_sv_offsets_kernel, dim3((unsigned)(((size_t)E + 1 + 255) / 256)), dim3(256), 0, st, ws.skeys, E, M, ws.off);
+    DF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(df_sv_sorted_kernel, dim3((unsigned)(((size_t)E + 255) / 256)), dim3(256), 0, st, ws.svals, ws.w, E, k, ws.spt, ws.sw);
+    DF_LAUNCH_CHECK();
+    return DF_OK;
+}
+
+// The solve behind the three entry points (arguments checked and normalised by df_sv_check: kg = 0 means no regularisation).
+// `rounds` solves, each from the transforms the one before wrote; tukey_c / huber_delta = 0: that penalty is quadratic and its kernels
+// are not launched, so rounds = 1 with both 0 is the plain solve, launch for launch.  `energy` (nullable) holds n_energy floats:
+// 2 = {E_data before, after}, 4 = with {E_reg before, after}, which are 0 without the term.
+static int df_sv_rounds(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int kg, float lambda_reg,
+                        int rounds, float tukey_c, float huber_delta, float* dq_out, float* energy, int n_energy, float* point_weights,
+                        float* edge_weights, dfStream stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const bool reg = kg > 0, tukey = tukey_c != 0.f, huber = reg && huber_delta != 0.f;
+    const int M = wf->M, E = N * k, Eg = M * kg;
+    const float c2 = tukey_c * tukey_c, dd2 = huber_delta * huber_delta;
+    SvWorkspace ws;
+    int rc;
+    if ((rc = df_sv_workspace(wf, N, k, M, Eg, tukey, huber, st, &ws))) return rc;
+    if ((rc = df_sv_prepare(wf, k, canonical, live, N, kg, ws, stream))) return rc;
+    const float* const sw_use = tukey ? ws.sw_scaled : ws.sw;           // what W^T reads: the scaled copy, or the list as it is
+    const float* const alpha_use = huber ? ws.alpha_scaled : wf->graph_alpha.p;   // the handle's cached alpha is only read
+    const float* const active = ws.scal + SV_ACTIVE; float* const en = ws.scal + SV_ENERGY;
+    const dim3 gN((N + 255) / 256), gM((M + 255) / 256), gE((unsigned)(((size_t)E + 255) / 256)), gG((Eg + 255) / 256), gW(M), one(1);
     auto step = M <= 2 * SV_BLOCK ? df_sv_step_reg_kernel<2> : M <= 5 * SV_BLOCK ? df_sv_step_reg_kernel<5> : M <= 8 * SV_BLOCK ? df_sv_step_reg_kernel<8> : df_sv_step_kernel;
     auto w_apply = k == 8 ? df_sv_w_apply_kernel<8> : k == 4 ? df_sv_w_apply_kernel<4> : df_sv_w_apply_kernel<0>;
     auto data_energy = [&](const float* e, float* out) {
-        if (tukey) hipLaunchKernelGGL(df_sv_tukey_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, e, N, c2, out);
-        else hipLaunchKernelGGL(df_sv_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, e, N, out);
+        if (tukey) hipLaunchKernelGGL(df_sv_tukey_energy_kernel, one, dim3(SV_BLOCK), 0, st, e, N, c2, out);
+        else hipLaunchKernelGGL(df_sv_energy_kernel, one, dim3(SV_BLOCK), 0, st, e, N, out);
     };
     auto reg_energy = [&](const float* xv, float* out) {                // (the energies weigh an edge with alpha_e itself, not alpha'_e)
-        if (huber) hipLaunchKernelGGL(df_sv_huber_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, wf->graph_nbr.p, wf->graph_alpha.p, g, xv, Eg, kg, huber_delta, dd2, out);
-        else hipLaunchKernelGGL(df_sv_reg_energy_kernel, dim3(1), dim3(SV_BLOCK), 0, st, wf->graph_nbr.p, wf->graph_alpha.p, g, xv, Eg, kg, out);
+        if (huber) hipLaunchKernelGGL(df_sv_huber_energy_kernel, one, dim3(SV_BLOCK), 0, st, wf->graph_nbr.p, wf->graph_alpha.p, ws.g, xv, Eg, kg, huber_delta, dd2, out);
+        else hipLaunchKernelGGL(df_sv_reg_energy_kernel, one, dim3(SV_BLOCK), 0, st, wf->graph_nbr.p, wf->graph_alpha.p, ws.g, xv, Eg, kg, out);
     };
     for (int round = 0; round < rounds; ++round) {
         const bool first = round == 0, last = round == rounds - 1;
         if (!first) {                                                   // e0 at the transforms the previous round wrote
-            hipLaunchKernelGGL(df_sv_round_e0_kernel, gN, dim3(256), 0, st, canonical, live, N, k, keys, w, wf->node_t.p, M, e0);
+            hipLaunchKernelGGL(df_sv_round_e0_kernel, gN, dim3(256), 0, st, canonical, live, N, k, ws.keys, ws.w, wf->node_t.p, M, ws.e0);
             DF_LAUNCH_CHECK();
         }
         if (tukey) {
-            hipLaunchKernelGGL(df_sv_tukey_kernel, gN, dim3(256), 0, st, e0, N, c2, omega);
-            hipLaunchKernelGGL(df_sv_scale_list_kernel, gE, dim3(256), 0, st, spt, sw, omega, (int)E, (float*)(ws + o_sw2));
+            hipLaunchKernelGGL(df_sv_tukey_kernel, gN, dim3(256), 0, st, ws.e0, N, c2, ws.omega);
+            hipLaunchKernelGGL(df_sv_scale_list_kernel, gE, dim3(256), 0, st, ws.spt, ws.sw, ws.omega, E, ws.sw_scaled);
             DF_LAUNCH_CHECK();
         }
-        if (energy && first) { data_energy(e0, en); DF_LAUNCH_CHECK(); }
+        if (energy && first) { data_energy(ws.e0, en); DF_LAUNCH_CHECK(); }
         // r0 = W^T Omega e0 - lambda_reg * b' ; p0 = r0 ; x0 = 0
-        hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, offs, spt, sw_use, M, e0, 0.f, (const float*)nullptr, r, (const float*)nullptr);
+        hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, sw_use, M, ws.e0, 0.f, (const float*)nullptr, ws.r, (const float*)nullptr);
         DF_LAUNCH_CHECK();
         if (reg) {
-            hipLaunchKernelGGL(df_sv_reg_edge_kernel, gG, dim3(256), 0, st, wf->graph_nbr.p, wf->pos_sigma.p, wf->rot.p, wf->dual.p, Eg, kg, g);
-            if (huber) hipLaunchKernelGGL(df_sv_huber_kernel, gG, dim3(256), 0, st, g, wf->graph_alpha.p, Eg, huber_delta, dd2, omega_e, (float*)(ws + o_al2));
-            hipLaunchKernelGGL(df_sv_reg_rhs_kernel, gM, dim3(256), 0, st, alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg, g, lambda_reg, r);
+            hipLaunchKernelGGL(df_sv_reg_edge_kernel, gG, dim3(256), 0, st, wf->graph_nbr.p, wf->pos_sigma.p, wf->rot.p, wf->dual.p, Eg, kg, ws.g);
+            if (huber) hipLaunchKernelGGL(df_sv_huber_kernel, gG, dim3(256), 0, st, ws.g, wf->graph_alpha.p, Eg, huber_delta, dd2, ws.omega_e, ws.alpha_scaled);
+            hipLaunchKernelGGL(df_sv_reg_rhs_kernel, gM, dim3(256), 0, st, alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg, ws.g, lambda_reg, ws.r);
             if (energy && first) reg_energy(nullptr, en + 2);
             DF_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(df_sv_init_kernel, dim3(1), dim3(SV_BLOCK), 0, st, r, M, x, p, scal);
+        hipLaunchKernelGGL(df_sv_init_kernel, one, dim3(SV_BLOCK), 0, st, ws.r, M, ws.x, ws.p, ws.scal);
         DF_LAUNCH_CHECK();
         for (int it = 0; it < iters; ++it) {
-            hipLaunchKernelGGL(w_apply, gN, dim3(256), 0, st, w, keys, N, k, M, p, u, (const float*)(scal + 3));
-            hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, offs, spt, sw_use, M, u, lambda, p, q, (const float*)(scal + 3));
-            if (reg) hipLaunchKernelGGL(df_sv_reg_apply_kernel, gM, dim3(256), 0, st, wf->graph_nbr.p, alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg, p,
-                                        lambda_reg, q, (const float*)(scal + 3));
-            hipLaunchKernelGGL(step, dim3(1), dim3(SV_BLOCK), 0, st, q, M, x, r, p, scal);
+            hipLaunchKernelGGL(w_apply, gN, dim3(256), 0, st, ws.w, ws.keys, N, k, M, ws.p, ws.u, active);
+            hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, sw_use, M, ws.u, lambda, ws.p, ws.q, active);
+            if (reg) hipLaunchKernelGGL(df_sv_reg_apply_kernel, gM, dim3(256), 0, st, wf->graph_nbr.p, alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg, ws.p,
+                                        lambda_reg, ws.q, active);
+            hipLaunchKernelGGL(step, one, dim3(SV_BLOCK), 0, st, ws.q, M, ws.x, ws.r, ws.p, ws.scal);
             DF_LAUNCH_CHECK();
         }
         if (energy && last) {
-            hipLaunchKernelGGL(w_apply, gN, dim3(256), 0, st, w, keys, N, k, M, x, u, (const float*)nullptr);
-            hipLaunchKernelGGL(df_sv_residual_kernel, dim3((unsigned)((3 * (size_t)N + 255) / 256)), dim3(256), 0, st, e0, u, 3 * N, u);
-            data_energy(u, en + 1);
-            if (reg) reg_energy(x, en + 3);
+            hipLaunchKernelGGL(w_apply, gN, dim3(256), 0, st, ws.w, ws.keys, N, k, M, ws.x, ws.u, (const float*)nullptr);
+            hipLaunchKernelGGL(df_sv_residual_kernel, dim3((unsigned)((3 * (size_t)N + 255) / 256)), dim3(256), 0, st, ws.e0, ws.u, 3 * N, ws.u);
+            data_energy(ws.u, en + 1);
+            if (reg) reg_energy(ws.x, en + 3);
             DF_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(df_sv_writeback_kernel, gM, dim3(256), 0, st, wf->rot.p, wf->node_t.p, x, M, dq);
+        hipLaunchKernelGGL(df_sv_writeback_kernel, gM, dim3(256), 0, st, wf->rot.p, wf->node_t.p, ws.x, M, ws.dq);
         DF_LAUNCH_CHECK();
-        rc = dfusion_warp_set_transforms(wf, dq, stream);             // (the handle's rot / dual / node_t are the new ones from here on)
-        if (rc) return rc;
+        if ((rc = dfusion_warp_set_transforms(wf, ws.dq, stream))) return rc;   // (the handle's rot / dual / node_t are the new ones from here on)
     }
     if (energy) {
-        DF_HIP(hipMemcpyAsync(energy, en, (reg ? 4 : 2) * sizeof(float), hipMemcpyDeviceToDevice, st));
-        static const float zeros[2] = {0.f, 0.f};
-        if (!reg) DF_HIP(hipMemcpyAsync(energy + 2, zeros, sizeof(zeros), hipMemcpyHostToDevice, st));
+        DF_HIP(hipMemcpyAsync(energy, en, (reg ? n_energy : 2) * sizeof(float), hipMemcpyDeviceToDevice, st));
+        static const float zeros[2] = {0.f, 0.f};                       // (a copy from the host, not a fill: no kernel of any kind is added)
+        if (!reg && n_energy == 4) DF_HIP(hipMemcpyAsync(energy + 2, zeros, sizeof(zeros), hipMemcpyHostToDevice, st));
     }
-    if (dq_out) DF_HIP(hipMemcpyAsync(dq_out, dq, (size_t)M * 32, hipMemcpyDeviceToDevice, st));
+    if (dq_out) DF_HIP(hipMemcpyAsync(dq_out, ws.dq, (size_t)M * 32, hipMemcpyDeviceToDevice, st));
     if (point_weights) {
-        if (tukey) DF_HIP(hipMemcpyAsync(point_weights, omega, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+        if (tukey) DF_HIP(hipMemcpyAsync(point_weights, ws.omega, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
         else DF_HIP(hipMemsetD32Async((hipDeviceptr_t)point_weights, 0x3f800000, (size_t)N, st));
     }
     if (edge_weights) {
-        if (huber) DF_HIP(hipMemcpyAsync(edge_weights, omega_e, (size_t)Eg * 4, hipMemcpyDeviceToDevice, st));
+        if (huber) DF_HIP(hipMemcpyAsync(edge_weights, ws.omega_e, (size_t)Eg * 4, hipMemcpyDeviceToDevice, st));
         else DF_HIP(hipMemsetD32Async((hipDeviceptr_t)edge_weights, 0x3f800000, (size_t)Eg, st));
     }
     return DF_OK;
+}
+
+// The arguments the three entry points share.  DF_OK, with *kg = 0 where the regularisation is switched off (kg == 0 or
+// lambda_reg == 0: checked first, so an out-of-range kg is refused whatever lambda_reg is), or DF_E_INVALID.
+static int df_sv_check(const DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int* kg,
+                       float lambda_reg)
+{
+    if (!wf || !canonical || !live || N <= 0 || iters < 0 || !(lambda >= 0.f) || wf->M <= 0 || k < 1 || k > 8 || wf->M < k) return DF_E_INVALID;
+    if ((size_t)N * k > 0x7fffffffu) return DF_E_INVALID;
+    if (*kg < 0 || *kg > 7 || (*kg > 0 && wf->M < *kg + 1) || !(lambda_reg >= 0.f)) return DF_E_INVALID;
+    if (lambda_reg == 0.f) *kg = 0;
+    return DF_OK;
+}
+
+extern "C" int dfusion_warp_solve_data_term(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda,
+                                            float* dq_out, float* energy, dfStream stream)
+{
+    int kg = 0;
+    if (df_sv_check(wf, k, canonical, live, N, iters, lambda, &kg, 0.f)) return DF_E_INVALID;
+    return df_sv_rounds(wf, k, canonical, live, N, iters, lambda, kg, 0.f, 1, 0.f, 0.f, dq_out, energy, 2, nullptr, nullptr, stream);
+}
+
+extern "C" int dfusion_warp_solve(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int kg,
+                                  float lambda_reg, float* dq_out, float* energy, dfStream stream)
+{
+    if (df_sv_check(wf, k, canonical, live, N, iters, lambda, &kg, lambda_reg)) return DF_E_INVALID;
+    return df_sv_rounds(wf, k, canonical, live, N, iters, lambda, kg, lambda_reg, 1, 0.f, 0.f, dq_out, energy, 4, nullptr, nullptr, stream);
+}
+
+extern "C" int dfusion_warp_solve_robust(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int kg,
+                                         float lambda_reg, int rounds, float tukey_c, float huber_delta, float* dq_out, float* energy,
+                                         float* point_weights, float* edge_weights, dfStream stream)
+{
+    if (df_sv_check(wf, k, canonical, live, N, iters, lambda, &kg, lambda_reg)) return DF_E_INVALID;
+    if (rounds < 1 || !(tukey_c >= 0.f) || !(huber_delta >= 0.f) || (edge_weights && kg == 0)) return DF_E_INVALID;
+    return df_sv_rounds(wf, k, canonical, live, N, iters, lambda, kg, lambda_reg, rounds, tukey_c, huber_delta, dq_out, energy, 4, point_weights,
+                        edge_weights, stream);
 }
 
 extern "C" int dfusion_warp_node_graph(DfWarpField* wf, int kg, int* nbr, float* alpha, dfStream stream)

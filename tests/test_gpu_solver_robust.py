@@ -1,7 +1,8 @@
 """GPU parity of the robust warp solve (dfusion_warp_solve_robust) against the numpy restatement
 tests/solver_robust_ref.py, which tests/test_solver_robust_rule.py checks on the CPU: the transforms, the four energies and the last
 round's point and edge weights bit for bit across the node-count, neighbour-count, graph, round and penalty settings that change a
-dispatch; the off switches; huge thresholds; all outliers; the graph cache; NaN points; argument checks; the C++ mirror.
+dispatch; the off switches; huge thresholds; all outliers; the graph cache; NaN points; argument checks; one handle through all three
+entry points at changing sizes; how many energies the data-term entry point writes; the C++ mirror.
 
 The grid is a covering design, not the full product (108 solves, the M = 8193 ones seconds each on the CPU side): every M meets every
 penalty setting, every M meets every k, and kg = 0 / 4 and rounds = 1 / 3 each occur with every M, every k and every penalty setting
@@ -208,6 +209,58 @@ def test_invalid_arguments():
     assert call() == 0 and call(kg=4, edge=ew.data_ptr()) == 0 and call(kg=0, lreg=0.0, c=0.0, delta=0.0, rounds=1) == 0
     assert L.dfusion_warp_solve_robust(wf.handle, 4, pts.data_ptr(), pts.data_ptr(), 64, 3, 0.0, 2, 1.0, 2, 0.05, 0.01, None, None, None, None, None) == 0
     torch.cuda.synchronize()
+
+
+def test_one_handle_serves_every_entry_point_while_its_workspace_grows_and_shrinks():
+    """The three entry points carve one workspace on the handle.  Calls of different shapes in a row (N = 300 / 3001, with and without
+    the graph's and the penalties' pieces) must each give the bits of the same call on a fresh handle: nothing a differently shaped call
+    left behind is read."""
+    pos = random_nodes(40)
+    sigma, dq, src, dst = outlier_problem(pos)
+    small, large = (dev(src[:300]), dev(dst[:300])), (dev(src), dev(dst))
+    kw = dict(iters=ITERS, lam=LAM, k=4)
+    graph = dict(reg_neighbours=2, reg_lambda=LREG)
+    steps = [
+        lambda wf: wf.energy_data(*small, **kw),
+        lambda wf: wf.solve_robust(*large, rounds=2, tukey_c=TUKEY_C, huber_delta=HUBER_DELTA, return_weights=True, **graph, **kw),
+        lambda wf: wf.solve(*small, **graph, **kw),
+        lambda wf: wf.solve_robust(*small, rounds=1, tukey_c=0.0, huber_delta=0.0, return_weights=True, **graph, **kw),
+        lambda wf: wf.energy_data(*large, **kw),
+    ]
+
+    def run(wf, step):
+        wf.set_transforms(dev(dq))
+        out = step(wf)
+        torch.cuda.synchronize()
+        return [bits(t.cpu().numpy()) for t in out]
+    one = field(pos, sigma, dq, 4)
+    got = [run(one, step) for step in steps]
+    for i, step in enumerate(steps):
+        want = run(field(pos, sigma, dq, 4), step)
+        assert len(got[i]) == len(want)
+        for j, (g, w) in enumerate(zip(got[i], want)):
+            assert np.array_equal(g, w), "call %d, output %d: the shared handle against a fresh one" % (i + 1, j)
+    assert [len(g) for g in got] == [2, 4, 2, 4, 2]
+    assert (got[1][2] == 0).any() and (got[1][3] != bits(F32(1))).any()        # both penalties were live in call 2
+    assert np.array_equal(got[3][0], got[2][0]) and np.array_equal(got[3][1], got[2][1])   # all off, one round: the plain solve
+    assert (got[3][2] == bits(F32(1))).all() and (got[3][3] == bits(F32(1))).all()
+
+
+def test_the_data_term_entry_point_writes_two_energies():
+    L = capi.lib()
+    pos = random_nodes(5)
+    wf = field(pos, np.full(5, 0.4, F32), k=4)
+    src = np.random.default_rng(1).uniform(-1, 1, (64, 3)).astype(F32)
+    pts, live = dev(src), dev(src + F32(0.01))
+    dq = torch.empty((5, 8), dtype=torch.float32, device="cuda"); en = torch.full((4,), -7.0, dtype=torch.float32, device="cuda")
+    assert L.dfusion_warp_solve_data_term(wf.handle, 4, pts.data_ptr(), live.data_ptr(), 64, 3, 0.0, dq.data_ptr(), en.data_ptr(), None) == 0
+    torch.cuda.synchronize()
+    e = en.cpu().numpy()
+    assert e[0] > 0 and 0 <= e[1] < e[0] and (e[2:] == -7).all(), e
+    assert L.dfusion_warp_solve(wf.handle, 4, pts.data_ptr(), live.data_ptr(), 64, 3, 0.0, 0, 1.0, dq.data_ptr(), en.data_ptr(), None) == 0
+    torch.cuda.synchronize()
+    e = en.cpu().numpy()
+    assert e[0] > 0 and (bits(e[2:]) == 0).all(), e
 
 
 # ------------------------------------------------------------------------------------------------ the C++ mirror

@@ -7,7 +7,8 @@ Wall times around a device synchronise, medians of REPEATS after two warm-up rou
   the robust solve with 0 steps at 2 and 3 rounds: what a round costs beyond its conjugate-gradient steps (e0, Tukey, list scale, edge
   values, Huber, right-hand side, write-back).
 Every measurement runs in a child process of its own (one library per process); this tree and the parent library alternate, SESSIONS
-times each.  Writes one JSON line to --out (default profiles/solver_robust_probe.json).
+times each; every row the parent library has is timed there too, and the summary sets the two side by side
+(rows_against_parent).  Writes one JSON line to --out (default profiles/solver_robust_probe.json).
 Usage: tools/solver_robust_probe.py [REPEATS] [--parent-lib FILE] [--out FILE] [--sessions N]"""
 import json
 import os
@@ -107,6 +108,17 @@ def main():
         "round_beyond_cg_ms": m["robust_0_steps_3"] - m["robust_0_steps_2"],
         "round_beyond_cg_over_parent_solve": (m["robust_0_steps_3"] - m["robust_0_steps_2"]) / base,
     }
+    if parent:
+        # every row on both libraries: the session medians, and whether this tree's lies within the parent's own session-to-session
+        # spread, widened by that spread once more on either side (two sessions are a small sample of it)
+        rows = {}
+        for name in res["parent"][0]["median_ms"]:
+            p = [s["median_ms"][name] for s in res["parent"]]
+            t = [s["median_ms"][name] for s in res["tree"]]
+            spread = max(p) - min(p)
+            rows[name] = {"parent_ms": p, "tree_ms": t, "tree_median_ms": med(t), "allowed_ms": [min(p) - spread, max(p) + spread],
+                          "within": bool(min(p) - spread <= med(t) <= max(p) + spread)}
+        res["summary"]["rows_against_parent"] = rows
     line = json.dumps(res)
     print(json.dumps(res["summary"]))
     with open(out, "w") as f:
