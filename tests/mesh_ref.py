@@ -107,8 +107,8 @@ class Mesh:
 
 def extract_mesh(vol_u32, dims, vs, aff12, slab=None):
     """vol_u32 [z_store_n, Y, X] (the stored planes); slab = (z_store0, z_store_n, z_own0, z_own_n) or None.
-    -> Mesh: vertices f32 [n, 4], triangles uint32 [m, 3]; owner [n, 4] (z, y, x, slot; z global) of every vertex; meshed [nz-1.., ..] and
-    z0 (the first owner plane) for the property tests."""
+    -> Mesh: vertices f32 [n, 4], triangles uint32 [m, 3]; owner [n, 4] (z, y, x, slot; z global) of every vertex; meshed [nz-1.., ..],
+    cell_patterns (the 8-bit corner pattern of every meshed cell) and z0 (the first owner plane) for the property tests."""
     X, Y, Z = dims
     z_store0, z_store_n, z_own0, z_own_n = slab if slab is not None else (0, Z, 0, Z)
     z_end = min(z_own0 + z_own_n, Z - 1)
@@ -119,6 +119,7 @@ def extract_mesh(vol_u32, dims, vs, aff12, slab=None):
     if z_end < z_own0:
         out.vertices, out.triangles = np.zeros((0, 4), F32), np.zeros((0, 3), np.uint32)
         out.owner, out.meshed = np.zeros((0, 4), np.int64), np.zeros((0, Y - 1, X - 1), bool)
+        out.cell_patterns = np.zeros(0, np.int64)
         return out
     P = np.ascontiguousarray(vol_u32[z_own0 - z_store0:z_end - z_store0 + 1])
     nz = P.shape[0]
@@ -155,6 +156,7 @@ def extract_mesh(vol_u32, dims, vs, aff12, slab=None):
     out.meshed = meshed
     cz, cy, cx = np.nonzero(meshed)                                     # ascending linear cell index
     cin = in8[cz, cy, cx]
+    out.cell_patterns = cin                                            # the inside / outside corner pattern of every meshed cell
     N, CORNER, SLOT, _ = case_table()
     tri = np.full((cz.size, 6, 2, 3), -1, np.int64)
     for t, (a, b, _c) in enumerate(PERMS):
@@ -303,3 +305,79 @@ def rotated_pose():
     T[:3, :3] = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
     T[:3, 3] = [-0.4, 0.3, 0.9]
     return T.astype(F32)
+
+
+# ------------------------------------------------------------------------------------------------ volumes that reach every lane state
+ANISO_VS = (F32(3.0) / F32(256), F32(5.0) / F32(256), F32(7.0) / F32(512))
+FUZZ_DIMS = [(4, 1, 1), (4, 2, 2), (4, 7, 3), (8, 1, 5), (12, 5, 1), (20, 3, 9), (36, 7, 5), (260, 3, 2), (16, 16, 16), (24, 11, 13)]
+FUZZ_P_INVALID = (0.0, 0.1)
+
+
+def noise_volume(dims, seed, p_invalid):
+    """Every voxel on its own: half tsdf uniform in [-1, 1] (a draw that rounds to +1.0, which would not be valid, is the half below
+    it), about 5 % of the voxels +0 or -0 (outside both), 2 % -1.0 (valid, inside), p_invalid / 2 of them +1.0 (not valid); weights
+    1 .. 127, p_invalid of them 0.  No NaN, no |tsdf| > 1: the pipeline stores neither.  -> uint32 [Z, Y, X]."""
+    X, Y, Z = dims
+    rng = np.random.default_rng(seed)
+    half = rng.uniform(-1.0, 1.0, (Z, Y, X)).astype(np.float16).view(np.uint16)
+    half[half == 0x3c00] = 0x3bff
+    u = rng.random((Z, Y, X))
+    half[u < 0.025] = 0x0000
+    half[(u >= 0.025) & (u < 0.05)] = 0x8000
+    half[(u >= 0.05) & (u < 0.07)] = 0xbc00
+    half[(u >= 0.07) & (u < 0.07 + p_invalid / 2)] = 0x3c00
+    weight = rng.integers(1, 128, (Z, Y, X)).astype(np.uint32)
+    weight[rng.random((Z, Y, X)) < p_invalid] = 0
+    return half.astype(np.uint32) | (weight << np.uint32(16))
+
+
+@functools.lru_cache(None)
+def fuzz_case(index, p_invalid):
+    """(volume, its mesh at POSE) of FUZZ_DIMS[index], seed 10 + index; shared, read-only."""
+    vol = noise_volume(FUZZ_DIMS[index], 10 + index, p_invalid)
+    return vol, extract_mesh(vol, FUZZ_DIMS[index], VS, POSE)
+
+
+def checker_volume(dims):
+    """Inside iff x + y + z is odd, |tsdf| = 0.5, weight 1: every axis edge and every body diagonal carries a vertex, so every lane has one."""
+    X, Y, Z = dims
+    z, y, x = np.meshgrid(np.arange(Z), np.arange(Y), np.arange(X), indexing="ij")
+    half = np.where((x + y + z) & 1, 0xb800, 0x3800).astype(np.uint32)
+    return half | np.uint32(1 << 16)
+
+
+def one_vertex_per_lane_volume(dims):
+    """On even y and even z only: voxels x = 0 (mod 4) outside, x = 1 (mod 4) inside; everything else has weight 0.  A lane of such a
+    row has exactly one vertex (its first x edge), every other lane none, and no cell is meshed."""
+    X, Y, Z = dims
+    vol = np.zeros((Z, Y, X), np.uint32)
+    vol[::2, ::2, 0::4] = (1 << 16) | 0x3800
+    vol[::2, ::2, 1::4] = (1 << 16) | 0xb800
+    return vol
+
+
+def lanes_with_a_vertex(mesh):
+    """The number of lanes (4 x-adjacent voxels, x0 = 0 mod 4) that own at least one vertex."""
+    z, y, x, _ = mesh.owner.T
+    return len(np.unique(np.stack([z, y, x >> 2], 1), axis=0))
+
+
+def banded_mesh(vol, dims, vs, aff, bands):
+    """The mesh of a volume that is valid only inside the z-bands (z0, n), ascending, with at least one all-invalid plane between two
+    of them: the meshes of the bands, each extracted as a slab of its own (plus the invalid plane above it, which the slab rule wants
+    stored), concatenated with the vertex indices offset.  vol: the whole volume [Z, Y, X].  -> Mesh with vertices and triangles only."""
+    Z = dims[2]
+    vertices, triangles, nv, top = [], [], 0, 0
+    for z0, n in bands:
+        store_n = min(n + 1, Z - z0)
+        assert z0 >= top and z0 + n <= Z
+        assert not decode(vol[top:z0])[1].any() and not decode(vol[z0 + n:z0 + store_n])[1].any()
+        m = extract_mesh(vol[z0:z0 + store_n], dims, vs, aff, slab=(z0, store_n, z0, n))
+        vertices.append(m.vertices)
+        triangles.append((m.triangles.astype(np.int64) + nv).astype(np.uint32))
+        nv += len(m.vertices)
+        top = z0 + n
+    assert not decode(vol[top:])[1].any()
+    out = Mesh()
+    out.vertices, out.triangles = np.concatenate(vertices), np.concatenate(triangles)
+    return out

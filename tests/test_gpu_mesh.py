@@ -23,11 +23,11 @@ def pose44(aff12):
     return T
 
 
-def gpu_volume(vol_u32, dims, aff12=R.IDENT, slab=None):
-    """A TsdfVolume whose voxel size is mesh_ref.VS exactly (3 / 256 per voxel), holding vol_u32's stored planes."""
+def gpu_volume(vol_u32, dims, aff12=R.IDENT, slab=None, vs=R.VS):
+    """A TsdfVolume whose voxel size is vs exactly (mesh_ref.VS: 3 / 256 per voxel), holding vol_u32's stored planes."""
     v = TsdfVolume(dims, slab=slab)
-    v.setSize([float(F32(d) * R.VS[i]) for i, d in enumerate(dims)])
-    assert np.array_equal(v.getVoxelSize().view(np.uint32), np.array(R.VS, F32).view(np.uint32))
+    v.setSize([float(F32(d) * vs[i]) for i, d in enumerate(dims)])
+    assert np.array_equal(v.getVoxelSize().view(np.uint32), np.array(vs, F32).view(np.uint32))
     v.setPose(pose44(aff12))
     v.upload(vol_u32[v.z_store0:v.z_store0 + v.z_store_n])
     return v

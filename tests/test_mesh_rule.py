@@ -128,3 +128,79 @@ def test_write_ply_round_trip(tmp_path):
         faces = np.frombuffer(body[vb:], dtype=np.uint8).reshape(nf, 13)
         assert (faces[:, 0] == 3).all()
         assert np.ascontiguousarray(faces[:, 1:]).tobytes() == m.triangles.astype("<u4").tobytes()
+
+
+# ---- the volumes that tests/test_gpu_mesh_edges.py meshes on the GPU: what they reach, shown here without the kernel
+def fuzz_set():
+    return [(R.FUZZ_DIMS[i], p) + R.fuzz_case(i, p) for i in range(len(R.FUZZ_DIMS)) for p in R.FUZZ_P_INVALID]
+
+
+def test_noise_volume_holds_what_it_says():
+    vol = R.noise_volume((16, 16, 16), 18, 0.1)
+    half, weight = vol & 0xffff, vol >> 16
+    tsdf = half.astype(np.uint16).view(np.float16).astype(np.float32)
+    assert np.isfinite(tsdf).all() and np.abs(tsdf).max() <= 1 and weight.max() <= 127
+    frac = lambda m: float(m.mean())
+    assert 0.03 < frac((half == 0) | (half == 0x8000)) < 0.07 and (half == 0).any() and (half == 0x8000).any()
+    assert 0.01 < frac(half == 0xbc00) < 0.03 and 0.03 < frac(half == 0x3c00) < 0.07 and 0.07 < frac(weight == 0) < 0.13
+    clean = R.noise_volume((16, 16, 16), 18, 0.0)
+    assert R.decode(clean)[1].all()
+
+
+def test_fuzz_set_reaches_every_corner_pattern_and_every_edge_mask():
+    patterns, masks = set(), set()
+    for dims, p, vol, m in fuzz_set():
+        assert np.isfinite(m.vertices).all()
+        assert m.vertices.shape[0] > 0, (dims, p)
+        patterns |= set(int(c) for c in np.unique(m.cell_patterns))
+        X, Y, Z = dims
+        z, y, x, s = m.owner.T
+        per_voxel = np.zeros(X * Y * Z, np.int64)
+        np.bitwise_or.at(per_voxel, (z * Y + y) * X + x, 1 << s)
+        masks |= set(int(c) for c in np.unique(per_voxel))
+    assert patterns == set(range(256))
+    assert masks == set(range(128))
+
+
+def test_fuzz_volumes_without_cells_have_vertices_and_no_triangles():
+    for dims, p, vol, m in fuzz_set():
+        if dims in ((4, 1, 1), (8, 1, 5), (12, 5, 1)):
+            assert len(m.vertices) > 0 and len(m.triangles) == 0, (dims, p)
+    assert max(len(m.triangles) for _, _, _, m in fuzz_set()) > 5000
+
+
+def test_checker_fills_the_lane_table_with_every_lane():
+    dims = (16, 6, 5)
+    m = R.extract_mesh(R.checker_volume(dims), dims, R.VS, R.IDENT)
+    n4 = 16 * 6 * 5 // 4
+    assert R.lanes_with_a_vertex(m) == n4 == 120 and len(m.vertices) > n4 and len(m.triangles) > 0
+
+
+def test_one_vertex_per_lane_fills_the_lane_table_with_every_vertex():
+    dims = (16, 6, 5)
+    m = R.extract_mesh(R.one_vertex_per_lane_volume(dims), dims, R.VS, R.IDENT)
+    assert R.lanes_with_a_vertex(m) == len(m.vertices) == 36 and len(m.triangles) == 0
+
+
+def test_banded_mesh_is_the_mesh_of_the_whole_volume():
+    dims, bands = (16, 8, 40), [(0, 5), (17, 6), (33, 7)]
+    noise = R.noise_volume(dims, 7, 0.1)
+    vol = np.zeros_like(noise)
+    for z0, n in bands:
+        vol[z0:z0 + n] = noise[z0:z0 + n]
+    whole = R.extract_mesh(vol, dims, R.VS, R.POSE)
+    banded = R.banded_mesh(vol, dims, R.VS, R.POSE, bands)
+    assert len(whole.triangles) > 1000 and len(np.unique(whole.owner[:, 0] // 16)) == 3         # every band has vertices
+    assert np.array_equal(banded.vertices.view(np.uint32), whole.vertices.view(np.uint32))
+    assert np.array_equal(banded.triangles, whole.triangles)
+
+
+def test_anisotropic_voxel_sizes_cannot_be_permuted_unseen():
+    import itertools
+    base = R.extract_mesh(R.torus_volume(), R.TORUS_DIMS, R.ANISO_VS, R.IDENT).vertices.view(np.uint32)
+    assert len(set(float(v) for v in R.ANISO_VS)) == 3
+    for perm in itertools.permutations(range(3)):
+        if perm == (0, 1, 2):
+            continue
+        other = R.extract_mesh(R.torus_volume(), R.TORUS_DIMS, [R.ANISO_VS[i] for i in perm], R.IDENT).vertices.view(np.uint32)
+        assert other.shape == base.shape and not np.array_equal(other, base), perm
