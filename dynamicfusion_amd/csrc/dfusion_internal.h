@@ -202,6 +202,20 @@ DF_LOCAL int df_tables_complete(DfWarpField* wf, hipStream_t st);
 DF_LOCAL int df_build_voxel_table(DfWarpField* wf, const DfVolume& v, const DfSlab& s, const float vol2world[12], int k, bool weights,
                                   bool on_demand, hipStream_t st);
 
+// The scratch buffer the library keeps per (device, stream) until dfusion_release_scratch() (dfusion_volume.hip; the rigid integrate's
+// plan and the mesh extraction's workspace: calls on one stream are ordered, so they can share it).  df_scratch_acquire returns the
+// entry of (current device, st), LOCKED, and at least `bytes` of device memory in *mem_out, or nullptr when that cannot be allocated;
+// df_scratch_release unlocks it, once the call's last launch that uses the memory is enqueued.  DfScratchHold does both.
+struct DfScratchEntry;
+DF_LOCAL DfScratchEntry* df_scratch_acquire(hipStream_t st, size_t bytes, char** mem_out);
+DF_LOCAL void df_scratch_release(DfScratchEntry* entry);
+struct DfScratchHold {
+    char* mem = nullptr; DfScratchEntry* entry;                 // entry == nullptr: out of memory
+    DfScratchHold(hipStream_t st, size_t bytes) : entry(df_scratch_acquire(st, bytes, &mem)) {}
+    ~DfScratchHold() { if (entry) df_scratch_release(entry); }
+    DfScratchHold(const DfScratchHold&) = delete; DfScratchHold& operator=(const DfScratchHold&) = delete;
+};
+
 // Appends to the node set without dropping what still holds (dfusion_warp_index.hip; used by dfusion_warp_extend): the handle takes the grown
 // set pos/dq/sigma[Mn] (layout of dfusion_warp_set_nodes; the first M entries are the current nodes), and an index is brought up to date
 // for it in place -- the brick lists are re-made, and only the table blocks whose brick list changed or whose build met an exact

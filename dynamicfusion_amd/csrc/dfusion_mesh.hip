@@ -19,11 +19,6 @@
 #include <hipcub/hipcub.hpp>
 #include "dfusion_internal.h"
 
-// dfusion_volume.hip: the scratch buffer the library keeps per (device, stream) until dfusion_release_scratch().  Returns the locked
-// entry (nullptr: out of memory) and at least `bytes` of device memory; df_scratch_release() once the call's last launch is enqueued.
-DF_LOCAL void* df_scratch_acquire(hipStream_t st, size_t bytes, char** mem_out);
-DF_LOCAL void df_scratch_release(void* entry);
-
 // ---- the case table, derived by geometry at compile time
 // Tetrahedron t of a cell belongs to the axis permutation (a, b, c) = DF_MT_PERM[t] (lexicographic: xyz, xzy, yxz, yzx, zxy, zyx); its
 // corners are the cell corners (bit 0 = +x, bit 1 = +y, bit 2 = +z) v0 = 0, v1 = e_a, v2 = e_a + e_b, v3 = 7.  The edge between local
@@ -374,10 +369,9 @@ extern "C" int dfusion_extract_mesh(DfVolume v, const DfSlab* slab, const float 
     const size_t o_v = 0, o_t = o_v + (a.n_items + 1) * 8, o_q = (o_t + (a.n_items + 1) * 8 + 15) / 16 * 16;
     const size_t o_cnt = o_q + (emit ? a.n_items * sizeof(DfMeshItemQ) : 0), zero_bytes = o_cnt + 16;
     const size_t o_tab = zero_bytes, o_scan = (o_tab + (size_t)a.qcap * sizeof(uint2) + 255) / 256 * 256;
-    char* ws = nullptr;
-    void* hold = df_scratch_acquire(st, o_scan + scan_bytes, &ws);                              // held until the last launch is enqueued
-    if (!hold) return (int)hipErrorOutOfMemory;
-    struct Hold { void* e; ~Hold() { df_scratch_release(e); } } holder{hold};
+    DfScratchHold hold(st, o_scan + scan_bytes);                                                // held until the last launch is enqueued
+    if (!hold.entry) return (int)hipErrorOutOfMemory;
+    char* const ws = hold.mem;
     a.vbase = (unsigned long long*)(ws + o_v); a.tbase = (unsigned long long*)(ws + o_t);
     a.itemq = (DfMeshItemQ*)(ws + o_q); a.qcount = (unsigned int*)(ws + o_cnt); a.qtab = (uint2*)(ws + o_tab);
     DF_HIP(hipMemsetAsync(ws, 0, zero_bytes, st));

@@ -15,10 +15,8 @@
 //     the traffic the algorithmic-bytes figure 8*N_upd counts.
 #include "dfusion_internal.h"
 #include "dfusion_pyramid.h"
-#include <atomic>
 #include <list>
 #include <mutex>
-#include <vector>
 #include <math.h>
 #include <stdlib.h>
 #include <stdio.h>
@@ -26,10 +24,10 @@
 // ------------------------------------------------------------------------------------------ clear
 // (a workgroup zeroes CONTIGUOUS 16 KiB runs with non-temporal stores -- the copy probe's lesson below: a grid-stride loop of single
 // 16-byte stores wrote 4.3 TB/s)
-typedef unsigned int df_fill_u4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void df_fill_zero_kernel(df_fill_u4* __restrict__ p, size_t n16)
+typedef unsigned int df_u4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void df_fill_zero_kernel(df_u4* __restrict__ p, size_t n16)
 {
-    const df_fill_u4 z = {0u, 0u, 0u, 0u};             // pack_tsdf(0.f, 0) == 0 (device.hpp:53-54)
+    const df_u4 z = {0u, 0u, 0u, 0u};                  // pack_tsdf(0.f, 0) == 0 (device.hpp:53-54)
     for (size_t c0 = (size_t)blockIdx.x * 1024; c0 < n16; c0 += (size_t)gridDim.x * 1024) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -47,7 +45,7 @@ extern "C" int dfusion_clear(DfVolume v, const DfSlab* slab, dfStream stream)
     size_t n16 = (size_t)v.dims[0] * v.dims[1] * s.z_store_n / 4;
     size_t blocks = (n16 + 1023) / 1024;
     if (blocks > 256 * 16) blocks = 256 * 16;         // 16 blocks per CU, each walking 16 KiB runs
-    hipLaunchKernelGGL(df_fill_zero_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (df_fill_u4*)v.data, n16);
+    hipLaunchKernelGGL(df_fill_zero_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (df_u4*)v.data, n16);
     DF_LAUNCH_CHECK();
     return DF_OK;
 }
@@ -57,13 +55,12 @@ extern "C" int dfusion_clear(DfVolume v, const DfSlab* slab, dfStream stream)
 // grid-stride loop of single 16-byte accesses -- the usual form, and round 2's probe -- reaches 4.4-4.9 TB/s, because the lines a
 // workgroup touches at one time are scattered over the whole buffer; a workgroup that copies ONE CONTIGUOUS 16 KiB run, four
 // non-temporal 16-byte loads in flight per lane and non-temporal stores, reaches 5.7-6.3 TB/s (the guide's 6.29 TB/s float4 copy).
-typedef unsigned int df_probe_u4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void df_copy_kernel(df_probe_u4* __restrict__ d, const df_probe_u4* __restrict__ s, size_t n16)
+__global__ __launch_bounds__(256) void df_copy_kernel(df_u4* __restrict__ d, const df_u4* __restrict__ s, size_t n16)
 {
     const size_t b = (size_t)blockIdx.x * 1024, e = b + 1024 < n16 ? b + 1024 : n16;
     size_t i = b + threadIdx.x;
     if (i + 768 < e) {
-        df_probe_u4 v[4];
+        df_u4 v[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) v[u] = __builtin_nontemporal_load(s + i + u * 256);
 #pragma unroll
@@ -80,25 +77,25 @@ extern "C" int dfusion_copy_bandwidth_probe(void* dst, const void* src, size_t b
     const size_t blocks = (n16 + 1023) / 1024;
     if (blocks == 0) return DF_OK;
     if (blocks > 0x7fffffffull) return DF_E_INVALID;
-    hipLaunchKernelGGL(df_copy_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (df_probe_u4*)dst, (const df_probe_u4*)src, n16);
+    hipLaunchKernelGGL(df_copy_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (df_u4*)dst, (const df_u4*)src, n16);
     DF_LAUNCH_CHECK();
     return DF_OK;
 }
 
 // read-only stream probe: the measured roofline denominator for scan kernels (extract); four non-temporal loads in flight per lane
-__global__ __launch_bounds__(256) void df_read_kernel(const df_probe_u4* __restrict__ s, size_t n16, unsigned int* __restrict__ sink)
+__global__ __launch_bounds__(256) void df_read_kernel(const df_u4* __restrict__ s, size_t n16, unsigned int* __restrict__ sink)
 {
     const size_t stride = (size_t)gridDim.x * 256;
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     unsigned int acc = 0;
     for (; i + 3 * stride < n16; i += 4 * stride) {
-        df_probe_u4 v[4];
+        df_u4 v[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) v[u] = __builtin_nontemporal_load(s + i + u * stride);
 #pragma unroll
         for (int u = 0; u < 4; ++u) acc ^= v[u].x ^ v[u].y ^ v[u].z ^ v[u].w;
     }
-    for (; i < n16; i += stride) { const df_probe_u4 v = s[i]; acc ^= v.x ^ v.y ^ v.z ^ v.w; }
+    for (; i < n16; i += stride) { const df_u4 v = s[i]; acc ^= v.x ^ v.y ^ v.z ^ v.w; }
     if (acc == 0x9e3779b9u) *sink = acc;              // practically never true: keeps the loads alive without a store stream
 }
 
@@ -109,7 +106,7 @@ extern "C" int dfusion_read_bandwidth_probe(const void* src, size_t bytes, void*
     size_t blocks = (n16 + 255) / 256;
     if (blocks > 256 * 64) blocks = 256 * 64;
     if (blocks == 0) return DF_OK;
-    hipLaunchKernelGGL(df_read_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const df_probe_u4*)src, n16, (unsigned int*)sink4);
+    hipLaunchKernelGGL(df_read_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const df_u4*)src, n16, (unsigned int*)sink4);
     DF_LAUNCH_CHECK();
     return DF_OK;
 }
@@ -279,11 +276,10 @@ struct DfRigidArgs {
     DfIntegrateParams P;
     unsigned long long* n_upd;
     unsigned long long* n_swept;   // nullable: += voxels that went through the sample chain (alive sub-chunks x columns inside the volume)
-    // launch plan (df_rigid_plan_kernel).  A patch = DF_RIGID_PX x DF_RIGID_PY columns (one wave), tile = ty * tiles_x + tx with
-    // tiles_x a multiple of 4; a STRIP = 4 patches side by side in x (one workgroup: the four waves touch 4 * PX * 4 contiguous bytes
-    // of every voxel row together); item = chunk * strips + strip, its mask = 4 x 8 bits (bit 8 k + s: sub-chunk s of patch k may
-    // update, planes [zb + SUB s, zb + SUB s + SUB)); items with w > 0 bits are listed in bin w (plan_bins[w * plan_items ...],
-    // plan_cnt[w] entries), their masks in plan_mask[item]
+    // launch plan (df_rigid_plan_kernel).  A patch = DF_RIGID_PX x DF_RIGID_PY columns (one wave), tile = ty * tiles_x + tx;
+    // item = chunk * tiles + tile: one patch over one chunk, its mask one byte (bit s: sub-chunk s may update, planes
+    // [zb + SUB s, zb + SUB s + SUB)); items with w > 0 bits are listed in bin w (plan_bins[w * plan_items ...], plan_cnt[w] entries),
+    // their masks in plan_mask[item]
     const unsigned int* plan_bins; const unsigned int* plan_cnt; const unsigned int* plan_mask; unsigned int plan_items; int tiles, tiles_x;
     const float4* plan_starts;     // [item][lane]: the running position of lane's column at the item's first plane
 #ifdef DF_TRACE_WG
@@ -319,39 +315,82 @@ __device__ __forceinline__ unsigned df_outside_mask(const DfFrustum& F, f3 p, fl
 // box), the sweep's waves take the alive items most-work-first and carry no tests: full from start to end, 0.135 ms.
 // A chunk starting at plane zb replays the zb additions of :75 in registers, so every chunk -- and every Z-slab shard on another
 // GPU -- produces the bits of the unsharded sweep.
+// One batch of U voxels of a column, decided without the exact square root wherever that is possible (stage 1's second half, see
+// tsdf_sample_pre in dfusion_device.h): the approximate |vc| decides wherever the voxel is not within trunc of the surface -- the tsdf
+// is then exactly 1.f or the voxel does not update.  pre[u].ok already carries "inside the run and inside the volume".  Returns the
+// wave-uniform `sat` (every sample of the wave's batch was decided that way) and leaves the verdicts in up[], the tsdf values in ts[].
+template <int U>
+__device__ __forceinline__ bool df_rigid_decide(const DfIntegrateParams& P, const DfSamplePre (&pre)[U], float sat_t, bool (&up)[U], float (&ts)[U])
+{
+    bool undecided = false;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        ts[u] = pre[u].Dp - pre[u].s;                                       // approximate sdf
+        undecided = undecided | (pre[u].ok & (fabsf(ts[u]) < sat_t));
+    }
+    const bool sat = __builtin_amdgcn_ballot_w64(undecided) == 0ull;
+    if (sat) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) { up[u] = pre[u].ok & (ts[u] >= sat_t); ts[u] = 1.f; }
+    } else {                                                                // within trunc of the surface: the exact root and :89-93 as written
+#pragma unroll
+        for (int u = 0; u < U; ++u) up[u] = tsdf_sample_finish(P, pre[u], &ts[u]);
+    }
+    return sat;
+}
+// Stage 3 of a batch: fuse (:97-103) the samples up[] / ts[] into the voxel words v[] (loaded wherever up[u]) and store.  A wave decides
+// together which form of the fuse it takes: `sat` samples onto stored 1.0 / cleared voxels are a weight increment; finite stored values
+// take the fuse division's short form; the generic tsdf_fuse otherwise, and always without FAST (DF_RIGID_NO_SHORT_FORMS).
+template <int U, bool FAST, bool COUNT>
+__device__ __forceinline__ void df_rigid_fuse_store(const DfRigidArgs& a, uint32_t* p, size_t plane, const bool (&up)[U], const float (&ts)[U],
+                                                    const uint32_t (&v)[U], bool sat, unsigned int& my_upd)
+{
+    bool one = sat;
+    if (sat) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) one = one & (!up[u] | tsdf_fuse_one_ok(v[u]));
+        one = df_wave_all(one);
+    }
+    if (one) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (up[u]) { p[(size_t)u * plane] = tsdf_fuse_one(v[u], a.P.max_weight); if (COUNT) ++my_upd; }
+    } else {
+        bool fin = FAST;
+        if (FAST) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) fin = fin & (!up[u] | tsdf_fuse_short_ok(v[u]));
+            fin = df_wave_all(fin);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (up[u]) { p[(size_t)u * plane] = fin ? tsdf_fuse_short(v[u], ts[u], a.P.max_weight) : tsdf_fuse(v[u], ts[u], a.P.max_weight); if (COUNT) ++my_upd; }
+    }
+}
+
 // the voxels of one column on planes [zs, zse), U at a time
 template <int U, bool FAST, bool SAT, bool FULL, bool COUNT>
 __device__ __forceinline__ void df_rigid_batches(const DfRigidArgs& a, f3& vc, f3 zstep, uint32_t*& p, size_t plane, int zs, int zse,
                                                  bool active, unsigned int& my_upd)
 {
-    // FULL: the run is a whole number of batches (every sub-chunk but a slab's last): no per-plane range tests
+    // FULL: the run is a whole number of batches (every sub-chunk but a slab's last): no per-plane range tests.  Only without SAT: a
+    // whole run with the saturated-sample shortcuts is df_rigid_run_pipe's
+    static_assert(!(FULL && SAT) && (FAST || !SAT), "SAT needs FAST; a FULL run with SAT is df_rigid_run_pipe's");
     const float sat_t = df_sat_threshold(a.P.trunc);
     for (int z = zs; z < zse; z += U) {
         float ts[U];
         bool up[U];
-        bool sat = false;                               // every sample of the batch is decided without the exact square root
-        if constexpr (FAST && SAT) {
-            // stage 1 in two halves (dfusion_device.h, tsdf_sample_pre): the approximate |vc| decides wherever the voxel is not
-            // within trunc of the surface -- the tsdf is then exactly 1.f or the voxel does not update
+        bool sat = false;
+        if constexpr (SAT) {
             DfSamplePre pre[U];
-            bool undecided = false;
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
+            for (int u = 0; u < U; ++u) {               // stage 1, first half: U projections and dists gathers
                 const bool inr = FULL || z + u < zse;
                 pre[u] = tsdf_sample_pre(a.P, vc);
-                ts[u] = pre[u].Dp - pre[u].s;           // approximate sdf
-                up[u] = pre[u].ok && inr && active;
-                undecided = undecided | (up[u] & (fabsf(ts[u]) < sat_t));
+                pre[u].ok = pre[u].ok && inr && active;
                 if (inr) vc = add3(vc, zstep);          // :75
             }
-            sat = __builtin_amdgcn_ballot_w64(undecided) == 0ull;
-            if (sat) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) { up[u] = up[u] & (ts[u] >= sat_t); ts[u] = 1.f; }
-            } else {                                    // within trunc of the surface: the exact root and :89-93 as written
-#pragma unroll
-                for (int u = 0; u < U; ++u) up[u] = tsdf_sample_finish(a.P, pre[u], &ts[u]) & up[u];
-            }
+            sat = df_rigid_decide<U>(a.P, pre, sat_t, up, ts);
         } else {
 #pragma unroll
             for (int u = 0; u < U; ++u) {               // stage 1: U branch-free sample chains
@@ -364,28 +403,7 @@ __device__ __forceinline__ void df_rigid_batches(const DfRigidArgs& a, f3& vc, f
 #pragma unroll
         for (int u = 0; u < U; ++u)                     // stage 2: the voxel loads of the batch in flight together
             if (up[u]) v[u] = p[(size_t)u * plane];
-        bool one = false;                               // saturated samples onto stored 1.0 / cleared voxels: the fuse is a weight increment
-        if (FAST && SAT && sat) {
-            one = true;
-#pragma unroll
-            for (int u = 0; u < U; ++u) one = one & (!up[u] | tsdf_fuse_one_ok(v[u]));
-            one = df_wave_all(one);
-        }
-        if (one) {
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-                if (up[u]) { p[(size_t)u * plane] = tsdf_fuse_one(v[u], a.P.max_weight); if (COUNT) ++my_upd; }
-        } else {
-            bool fin = FAST;                            // the fuse division's short form: finite stored values (a wave decides together)
-            if (FAST) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) fin = fin & (!up[u] | tsdf_fuse_short_ok(v[u]));
-                fin = df_wave_all(fin);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)                 // stage 3: fuse (:97-103) and store
-                if (up[u]) { p[(size_t)u * plane] = fin ? tsdf_fuse_short(v[u], ts[u], a.P.max_weight) : tsdf_fuse(v[u], ts[u], a.P.max_weight); if (COUNT) ++my_upd; }
-        }
+        df_rigid_fuse_store<U, FAST, COUNT>(a, p, plane, up, ts, v, sat, my_upd);
         p += (size_t)(FULL ? U : min(U, zse - z)) * plane;
     }
 }
@@ -398,14 +416,14 @@ __device__ __forceinline__ void df_rigid_batches(const DfRigidArgs& a, f3& vc, f
 // wave instead of U, and one wait per batch instead of two dependent ones.
 // (Chunk starts are made once per column by the plan kernel -- every chunk replaying the additions from plane 0 was the first form --
 // and the run is software-pipelined one batch ahead; both used to be compile-time switches.)
-template <int U> struct DfRigidPend { float Dp[U], d2[U], s[U]; uint32_t v[U]; bool ok[U]; };
+template <int U> struct DfRigidPend { DfSamplePre pre[U]; uint32_t v[U]; };
 template <int U>
 __device__ __forceinline__ void df_rigid_issue(const DfRigidArgs& a, f3& vc, f3 zstep, const uint32_t* p, size_t plane, bool active, DfRigidPend<U>& P)
 {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        const DfSamplePre pre = tsdf_sample_pre(a.P, vc);                   // (issues the dists gather)
-        P.Dp[u] = pre.Dp; P.d2[u] = pre.d2; P.s[u] = pre.s; P.ok[u] = pre.ok && active;
+        P.pre[u] = tsdf_sample_pre(a.P, vc);                                // (issues the dists gather)
+        P.pre[u].ok = P.pre[u].ok && active;
         P.v[u] = 0u;
         // the voxel word, unconditionally.  (Round 4 measured the obvious refinement -- only for voxels that project into the image, a
         // test on the geometry alone, so the load still goes out with the dists gather: 0.1123 against 0.1122 ms, same box,
@@ -418,42 +436,8 @@ template <int U, bool COUNT>
 __device__ __forceinline__ void df_rigid_finish(const DfRigidArgs& a, uint32_t* p, size_t plane, const DfRigidPend<U>& P, float sat_t, unsigned int& my_upd)
 {
     float ts[U]; bool up[U];
-    bool undecided = false;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        ts[u] = P.Dp[u] - P.s[u];                                           // approximate sdf (see tsdf_sample_pre)
-        undecided = undecided | (P.ok[u] & (fabsf(ts[u]) < sat_t));
-    }
-    const bool sat = __builtin_amdgcn_ballot_w64(undecided) == 0ull;
-    if (sat) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) { up[u] = P.ok[u] & (ts[u] >= sat_t); ts[u] = 1.f; }
-    } else {                                                                // within trunc of the surface: the exact root, :89-93 as written
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            DfSamplePre pre; pre.Dp = P.Dp[u]; pre.d2 = P.d2[u]; pre.s = P.s[u]; pre.ok = P.ok[u];
-            up[u] = tsdf_sample_finish(a.P, pre, &ts[u]);
-        }
-    }
-    bool one = sat;                                                         // saturated samples onto stored 1.0 / cleared voxels: a weight increment
-    if (sat) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) one = one & (!up[u] | tsdf_fuse_one_ok(P.v[u]));
-        one = df_wave_all(one);
-    }
-    if (one) {
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (up[u]) { p[(size_t)u * plane] = tsdf_fuse_one(P.v[u], a.P.max_weight); if (COUNT) ++my_upd; }
-    } else {
-        bool fin = true;
-#pragma unroll
-        for (int u = 0; u < U; ++u) fin = fin & (!up[u] | tsdf_fuse_short_ok(P.v[u]));
-        fin = df_wave_all(fin);
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (up[u]) { p[(size_t)u * plane] = fin ? tsdf_fuse_short(P.v[u], ts[u], a.P.max_weight) : tsdf_fuse(P.v[u], ts[u], a.P.max_weight); if (COUNT) ++my_upd; }
-    }
+    const bool sat = df_rigid_decide<U>(a.P, P.pre, sat_t, up, ts);
+    df_rigid_fuse_store<U, true, COUNT>(a, p, plane, up, ts, P.v, sat, my_upd);
 }
 // planes [zs, zs + n), n a multiple of U
 template <int U, bool COUNT>
@@ -480,19 +464,18 @@ __device__ __forceinline__ void df_rigid_run_pipe(const DfRigidArgs& a, f3& vc, 
 #define DF_RIGID_PY (64 / DF_RIGID_PX)
 #define DF_RIGID_SUB 8
 #define DF_RIGID_U 2
-#define DF_RIGID_U_GENERIC 2
 #define DF_RIGID_WAVES 8
 #define DF_RIGID_MAX_SUBS 8      // sub-chunks per chunk (the plan's masks are bytes)
-#define DF_RIGID_STRIP 1         // patches (waves) side by side in x per plan item: 1, 2 or 4 (a sweep workgroup = 4 waves = 4 / STRIP items)
 #define DF_RIGID_ZC 32           // planes per chunk wanted (a multiple of DF_RIGID_SUB, <= DF_RIGID_SUB * DF_RIGID_MAX_SUBS)
-#define DF_RIGID_BINS (DF_RIGID_STRIP * DF_RIGID_MAX_SUBS + 1)
+#define DF_RIGID_BINS (DF_RIGID_MAX_SUBS + 1)  // an item is listed by its number of alive sub-chunks, 1 .. MAX_SUBS
+static_assert(DF_RIGID_SUB % DF_RIGID_U == 0, "a whole sub-chunk is a whole number of batches (the sweep's dispatch, df_rigid_batches' FULL)");
 // (Round 5 built PAIRS -- two x-adjacent 32 x 2 patches whose alive sub-chunks coincide walked as two 64 x 1 rows, one 256-byte run per
 // plane instead of two of 128: 0.1123 ms against 0.1121 without, same box, volumes identical, profiles/r05_ab_rigid_pairs.txt.  The sweep
 // is not bound by how wide its row runs are; the variant is gone from the source.)
-// Conservative, result-identical rejection of ALL the voxels of a 32 x 2 column patch on planes [zs, zs + n): the same two tests as
-// df_rigid_culled, on the box the patch's voxels span (its 8 corners; positions by multiplication, within the tests' margin of the
-// running sums the sweep carries): (a) all corners outside the same frustum side plane, (b) the box's least distance from the camera
-// centre exceeds, by more than trunc, the largest dists value over the pixel rectangle that bounds the corners' projections.
+// Conservative, result-identical rejection of ALL the voxels of a 32 x 2 column patch on planes [zs, zs + n): two tests on the box
+// the patch's voxels span (its 8 corners; positions by multiplication, within the tests' margin of the running sums the sweep
+// carries): (a) all corners outside the same frustum side plane, (b) the box's least distance from the camera centre exceeds, by
+// more than trunc, the largest dists value over the pixel rectangle that bounds the corners' projections.
 template <bool DEPTH>
 __device__ __forceinline__ bool df_rigid_box_culled(const DfRigidArgs& a, const DfFrustum& F, const DfDistsPyramid& Py, int x0, int y0, int zs, int n)
 {
@@ -528,14 +511,14 @@ __device__ __forceinline__ bool df_rigid_box_culled(const DfRigidArgs& a, const 
 }
 
 // The launch plan.  One wave per patch and group of 8 chunks: lane 8 c + s tests sub-chunk s of the group's c-th chunk (the box of
-// the whole patch over the sub-chunk's planes), the ballot gives the patch's masks.  Four neighbouring waves are the four patches of a
-// STRIP; their masks meet in LDS and make the strip items' 32-bit masks.  Alive items are binned by their number of alive
-// (patch, sub-chunk) cells (slots taken per workgroup, one atomic per bin); the sweep takes the bins from the fullest down, so its
-// workgroups are the long ones first and the launch does not end on a few of them.
-// Why strips (round 3): what bounded the sweep was neither its instructions nor the voxels it had in flight but the WAY it touched
-// HBM -- independent waves, each read-modify-writing 64 (16 x 4 patch) or 128 (32 x 2) contiguous bytes per voxel row at places
-// unrelated to what every other wave was touching: tools/rmw_probe.hip measures 2.6 / 4.4 TB/s for exactly that traffic, and
-// 6.3-6.6 TB/s as soon as >= 256 contiguous bytes of a row are touched together.
+// the whole patch over the sub-chunk's planes), the ballot gives the patch's masks, one byte per chunk: the plan's items.  The
+// workgroup's masks meet in LDS; alive items are binned by their number of alive sub-chunks (slots taken per workgroup, one atomic
+// per bin); the sweep takes the bins from the fullest down, so its waves are the long ones first and the launch does not end on a
+// few of them.
+// (Round 3 built STRIP items -- 2 or 4 patches side by side in x as one item and one sweep workgroup, so that >= 256 contiguous bytes
+// of a voxel row are touched together, for which tools/rmw_probe.hip measures 6.3-6.6 TB/s against the 4.4 TB/s of independent
+// 128-byte read-modify-writes: bit-identical and not faster, 103.8 against 104.6 us, the coarser items pack the wave slots worse.
+// profiles/NOTES.md, "Rigid integrate", has the numbers; the variant is gone from the source.)
 // The same wave then makes the CHUNK STARTS of its patch: a chunk at plane zb needs the running position after zb
 // additions `vc += zstep` (tsdf_volume.cu:75) -- the sequence cannot be shortcut, its roundings are the result.  Lane l walks column l
 // of the patch ONCE, up to the last alive chunk, and leaves the position at every alive chunk's first plane in `starts`.
@@ -551,7 +534,7 @@ __global__ __launch_bounds__(1024) void df_rigid_plan_kernel(const DfRigidArgs a
     // a wave = one patch and a group of cpw = 64 / subs chunks (subs = sub-chunks per chunk, a power of two <= 8): lane = cl * subs + sb
     const int subs = a.zc / DF_RIGID_SUB, sshift = __ffs(subs) - 1, cpw = 64 >> sshift;
     const int groups = (chunks + cpw - 1) / cpw;
-    const unsigned wg = blockIdx.x * 16u + (threadIdx.x >> 6);            // (chunk group, tile): tile fastest, a.tiles a multiple of 4
+    const unsigned wg = blockIdx.x * 16u + (threadIdx.x >> 6);            // (chunk group, tile): tile fastest
     const int cg = (int)(wg / (unsigned)a.tiles), tile = (int)(wg % (unsigned)a.tiles);
     const int lane = threadIdx.x & 63, sb = lane & (subs - 1), chunk = cg * cpw + (lane >> sshift);
     const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
@@ -564,17 +547,16 @@ __global__ __launch_bounds__(1024) void df_rigid_plan_kernel(const DfRigidArgs a
     const unsigned long long alive = __ballot(keep);                      // bits [cl * subs, (cl + 1) * subs): the patch's mask in chunk cg * cpw + cl
     if (lane == 0) s_alive[threadIdx.x >> 6] = alive;
     __syncthreads();
-    // the workgroup's 16 waves are 16 / STRIP strips x cpw chunks of plan items: one thread per item
+    // the workgroup's 16 waves are 16 patches x cpw chunks of plan items: one thread per item
     const unsigned smask = (1u << subs) - 1u;
     unsigned m = 0, w = 0, slot = 0, item = 0;
-    const int n_local = (16 / DF_RIGID_STRIP) * cpw;
+    const int n_local = 16 * cpw;
     if ((int)threadIdx.x < n_local) {
-        const int q = threadIdx.x / cpw, c = threadIdx.x % cpw;
-#pragma unroll
-        for (int k = 0; k < DF_RIGID_STRIP; ++k) m |= ((unsigned)(s_alive[DF_RIGID_STRIP * q + k] >> (c * subs)) & smask) << (8 * k);
-        const unsigned wg0 = blockIdx.x * 16u + (unsigned)(DF_RIGID_STRIP * q);      // the strip's first wave
-        const int scg = (int)(wg0 / (unsigned)a.tiles), strip = (int)(wg0 % (unsigned)a.tiles) / DF_RIGID_STRIP;
-        item = (unsigned)(scg * cpw + c) * (unsigned)(a.tiles / DF_RIGID_STRIP) + (unsigned)strip;
+        const int q = threadIdx.x / cpw, c = threadIdx.x % cpw;                 // wave q's patch, its c-th chunk
+        m = (unsigned)(s_alive[q] >> (c * subs)) & smask;
+        const unsigned wq = blockIdx.x * 16u + (unsigned)q;
+        const int qcg = (int)(wq / (unsigned)a.tiles), qtile = (int)(wq % (unsigned)a.tiles);
+        item = (unsigned)(qcg * cpw + c) * (unsigned)a.tiles + (unsigned)qtile;
         w = (unsigned)__popc(m);
         if (m) slot = atomicAdd(&s_cnt[w], 1u);
     }
@@ -608,25 +590,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DF_RIGID_WA
 {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    // plan entry -> strip item: lane j < DF_RIGID_BINS - 1 holds the count of bin DF_RIGID_BINS - 1 - j and the running total
+    // plan entry -> item: lane j < DF_RIGID_BINS - 1 holds the count of bin DF_RIGID_BINS - 1 - j and the running total
     const unsigned bin_cnt = lane < DF_RIGID_BINS - 1 ? a.plan_cnt[DF_RIGID_BINS - 1 - lane] : 0u;
     unsigned bin_end = bin_cnt;
 #pragma unroll
     for (int o = 1; o < DF_RIGID_BINS; o <<= 1) { const unsigned t = __shfl_up(bin_end, o, 64); if (lane >= o) bin_end += t; }
     const unsigned n_alive = (unsigned)__builtin_amdgcn_readlane((int)bin_end, DF_RIGID_BINS - 2);
-    const unsigned e = blockIdx.x * (4 / DF_RIGID_STRIP) + (unsigned)(wave / DF_RIGID_STRIP);      // plan entry: a strip of STRIP waves
+    const unsigned e = blockIdx.x * 4 + (unsigned)wave;                     // plan entry
     if (e >= n_alive) return;                                              // wave-uniform (no barrier below)
 #ifdef DF_TRACE_WG
     const unsigned long long t_start = wall_clock64(); unsigned n_sub = 0;
 #endif
     const int j = __ffsll((unsigned long long)__ballot(lane < DF_RIGID_BINS - 1 && e < bin_end)) - 1;
     const unsigned r = e - ((unsigned)__builtin_amdgcn_readlane((int)bin_end, j) - (unsigned)__builtin_amdgcn_readlane((int)bin_cnt, j));
-    const unsigned sitem = (unsigned)__builtin_amdgcn_readfirstlane((int)a.plan_bins[(size_t)(DF_RIGID_BINS - 1 - j) * a.plan_items + r]);
-    const unsigned mask = ((unsigned)__builtin_amdgcn_readfirstlane((int)a.plan_mask[sitem]) >> (8 * (wave % DF_RIGID_STRIP))) & 0xffu;
-    if (mask == 0u) return;                                                // nothing alive in this wave's patch
-    const int strips = a.tiles / DF_RIGID_STRIP;
-    const int chunk = (int)(sitem / (unsigned)strips), tile = (int)(sitem % (unsigned)strips) * DF_RIGID_STRIP + (wave % DF_RIGID_STRIP);
-    const unsigned item = (unsigned)chunk * (unsigned)a.tiles + (unsigned)tile;     // (patch item: indexes plan_starts)
+    const unsigned item = (unsigned)__builtin_amdgcn_readfirstlane((int)a.plan_bins[(size_t)(DF_RIGID_BINS - 1 - j) * a.plan_items + r]);
+    const unsigned mask = (unsigned)__builtin_amdgcn_readfirstlane((int)a.plan_mask[item]) & 0xffu;
+    if (mask == 0u) return;                                                // (no listed item: the plan lists what has an alive sub-chunk)
+    const int chunk = (int)(item / (unsigned)a.tiles), tile = (int)(item % (unsigned)a.tiles);
     const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
     const int x = tx * DF_RIGID_PX + (lane & (DF_RIGID_PX - 1)), y = ty * DF_RIGID_PY + (lane / DF_RIGID_PX);
     const bool active = x < a.X && y < a.Y;
@@ -657,10 +637,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DF_RIGID_WA
         // (SAT: the saturated-sample shortcuts also want every coordinate within 32 m; the generic forms otherwise)
         const bool fast = FASTOK && df_wave_all(!active || (tsdf_sample_domain_ok(vc, vc_end) && (!SAT || tsdf_sat_domain_ok(vc, vc_end))));
         my_swept += (unsigned)(zse - zs);               // (wave-uniform; times the wave's columns inside the volume at the end)
-        if (fast && SAT && (zse - zs) % U == 0) df_rigid_run_pipe<U, COUNT>(a, vc, zstep, p, plane, zse - zs, active, my_upd);
-        else if (fast && zse - zs == DF_RIGID_SUB) df_rigid_batches<DF_RIGID_U_GENERIC, true, SAT, true, COUNT>(a, vc, zstep, p, plane, zs, zse, active, my_upd);
-        else if (fast) df_rigid_batches<DF_RIGID_U_GENERIC, true, SAT, false, COUNT>(a, vc, zstep, p, plane, zs, zse, active, my_upd);
-        else df_rigid_batches<DF_RIGID_U_GENERIC, false, false, false, COUNT>(a, vc, zstep, p, plane, zs, zse, active, my_upd);   // (rare: fewer chains in flight, fewer registers)
+        const int n = zse - zs;
+        if (fast && SAT && n % U == 0) {                // whole batches with the shortcuts: the pipelined run
+            df_rigid_run_pipe<U, COUNT>(a, vc, zstep, p, plane, n, active, my_upd);
+        } else if (fast) {                              // batches with the short forms: a slab's last, odd run with SAT; every run without
+            if constexpr (SAT) df_rigid_batches<U, true, true, false, COUNT>(a, vc, zstep, p, plane, zs, zse, active, my_upd);
+            else if (n == DF_RIGID_SUB) df_rigid_batches<U, true, false, true, COUNT>(a, vc, zstep, p, plane, zs, zse, active, my_upd);
+            else df_rigid_batches<U, true, false, false, COUNT>(a, vc, zstep, p, plane, zs, zse, active, my_upd);
+        } else {                                        // batches with the generic forms (DF_RIGID_NO_SHORT_FORMS; a run outside the short forms' domain: rare)
+            df_rigid_batches<U, false, false, false, COUNT>(a, vc, zstep, p, plane, zs, zse, active, my_upd);
+        }
     }
 #ifdef DF_TRACE_WG
     if (lane == 0) {
@@ -743,8 +729,8 @@ static void df_scratch_free_entry(DfScratchEntry& c)                       // ca
     if (have_cur) (void)hipSetDevice(cur);
     c.mem = nullptr; c.cap = 0;
 }
-// the entry of (current device, st), locked; nullptr on failure.  *mem_out = at least `bytes` of device memory.
-static DfScratchEntry* df_rigid_scratch_acquire(hipStream_t st, size_t bytes, char** mem_out)
+// the entry of (current device, st), locked; nullptr on failure.  *mem_out = at least `bytes` of device memory.  (dfusion_internal.h)
+DF_LOCAL DfScratchEntry* df_scratch_acquire(hipStream_t st, size_t bytes, char** mem_out)
 {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
@@ -784,9 +770,7 @@ static DfScratchEntry* df_rigid_scratch_acquire(hipStream_t st, size_t bytes, ch
     *mem_out = e->mem;
     return e;
 }
-// the same buffer for dfusion_mesh.hip (which declares these two): calls on one stream are ordered, so they can share it
-DF_LOCAL void* df_scratch_acquire(hipStream_t st, size_t bytes, char** mem_out) { return df_rigid_scratch_acquire(st, bytes, mem_out); }
-DF_LOCAL void df_scratch_release(void* entry) { ((DfScratchEntry*)entry)->busy.unlock(); }
+DF_LOCAL void df_scratch_release(DfScratchEntry* entry) { entry->busy.unlock(); }
 extern "C" int dfusion_release_scratch(void)
 {
     std::lock_guard<std::mutex> lock(g_df_scratch_mutex);
@@ -836,9 +820,8 @@ extern "C" int dfusion_integrate_ex(const uint16_t* dists, size_t pitch, int col
             F.nlx = F.nrx = F.nty = F.nby = 0.f; F.nlz = F.nrz = F.ntz = F.nbz = 0.f;
         }
     }
-    // column patches (one per wave), 4 side by side per strip (one per workgroup): the patch grid's x extent is padded to whole strips
-    constexpr int tx_pad = DF_RIGID_STRIP;
-    const int tiles_x = ((a.X + DF_RIGID_PX - 1) / DF_RIGID_PX + tx_pad - 1) / tx_pad * tx_pad;
+    // column patches, one per wave of the sweep
+    const int tiles_x = (a.X + DF_RIGID_PX - 1) / DF_RIGID_PX;
     const int tiles = tiles_x * ((a.Y + DF_RIGID_PY - 1) / DF_RIGID_PY);
     // Z chunking: chunks of DF_RIGID_ZC planes -- 1, 2, 4 or 8 sub-chunks.  Short enough that the longest wave is a fraction of the
     // launch: a per-wave timeline (tools/trace_sweep.py, round 3) showed 64-plane items taking up to 93 us of a 115 us launch whose
@@ -848,37 +831,34 @@ extern "C" int dfusion_integrate_ex(const uint16_t* dists, size_t pitch, int col
     while ((s.z_own_n + zc - 1) / zc > 4096 && zc < DF_RIGID_SUB * DF_RIGID_MAX_SUBS) zc *= 2;      // (very deep slabs)
     a.zc = zc;
     const int chunks = (s.z_own_n + zc - 1) / zc;
-    const unsigned n_pitems = (unsigned)tiles * (unsigned)chunks;        // patch items (chunk starts)
-    const unsigned n_items = n_pitems / DF_RIGID_STRIP;                  // strip items (the plan's entries)
+    const unsigned n_items = (unsigned)tiles * (unsigned)chunks;         // the plan's items: a patch over a chunk (mask, chunk starts)
     a.tiles = tiles; a.tiles_x = tiles_x; a.plan_items = n_items;
     hipStream_t st = (hipStream_t)stream;
     // scratch: the launch plan, and for the behind-the-surface test a max-pyramid of this frame's dists
     const size_t pyr_elems = no_depth_cull ? 0 : df_pyramid_elems(cols, rows);
-    if (n_pitems >= (1u << 30)) return DF_E_INVALID;
+    if (n_items >= (1u << 30)) return DF_E_INVALID;
     const size_t off_cnt = 0, off_bins = 256, off_mask = off_bins + (size_t)DF_RIGID_BINS * n_items * 4;
     const size_t off_pyr = (off_mask + (size_t)n_items * 4 + 15) / 16 * 16;
     const size_t off_starts = (off_pyr + pyr_elems * sizeof(uint16_t) + 255) / 256 * 256;
-    const size_t bytes = off_starts + (size_t)n_pitems * 64 * sizeof(float4);
+    const size_t bytes = off_starts + (size_t)n_items * 64 * sizeof(float4);
     // One scratch buffer per (device, stream), grown on demand and kept: calls on a stream are ordered, so the next call's kernels
     // cannot start before this call's have finished with it.  (Round 3 tried the runtime's stream-ordered allocator here,
     // hipMallocAsync / hipFreeAsync per call: in a process that also allocates and frees with hipMalloc / hipFree between the calls --
     // the host mirror's reference-shaped flow -- one integrate in ~30 then updated a different set of voxels from identical inputs;
     // with a plain or a kept allocation never, 200 runs each.)
-    char* scratch = nullptr;
-    DfScratchEntry* scratch_entry = df_rigid_scratch_acquire(st, bytes, &scratch);       // held until the last launch below is enqueued
-    if (!scratch_entry) return (int)hipErrorOutOfMemory;
-    struct ScratchHold { DfScratchEntry* e; ~ScratchHold() { e->busy.unlock(); } } scratch_hold{scratch_entry};
+    DfScratchHold hold(st, bytes);                                         // held until the last launch below is enqueued: every return path
+    if (!hold.entry) return (int)hipErrorOutOfMemory;
+    char* const scratch = hold.mem;
     // validation: the kept buffer still holds the previous call's plan -- exactly what would hide a read of plan data this call did
     // not write.  Poisoned (every byte 0xFF: NaN starts, out-of-range items, full masks), such a read cannot go unnoticed.
     if (flags & DF_RIGID_POISON_SCRATCH) DF_HIP(hipMemsetAsync(scratch, 0xFF, bytes, st));
-    auto release_scratch = [&]() {};                                       // (scratch_hold's destructor: every return path)
     DfDistsPyramid Py;
     memset(&Py, 0, sizeof(Py));
     int rc = DF_OK;
     // (levels 1..5 only: the plan reads none above; the pyramid's first workgroup zeroes the plan's counters)
     if (pyr_elems) rc = df_build_dists_pyramid(dists, pitch, cols, rows, (uint16_t*)(scratch + off_pyr), pyr_elems, &Py, st, true, (unsigned int*)(scratch + off_cnt));
     if (rc == DF_OK && Py.top == 0 && hipMemsetAsync(scratch + off_cnt, 0, 256, st) != hipSuccess) rc = (int)hipGetLastError();
-    if (rc != DF_OK) { release_scratch(); return rc; }
+    if (rc != DF_OK) return rc;
     unsigned int* cnt = (unsigned int*)(scratch + off_cnt);
     unsigned int* bins = (unsigned int*)(scratch + off_bins);
     unsigned int* pmask = (unsigned int*)(scratch + off_mask);
@@ -891,7 +871,7 @@ extern "C" int dfusion_integrate_ex(const uint16_t* dists, size_t pitch, int col
     // short arithmetic forms (tsdf_sample_fast): 32-bit dists offsets, sane intrinsics; the value domain is tested per run in the kernel
     const bool fast_ok = (unsigned long long)rows * pitch < (1ull << 31) && proj[0] == proj[0] && proj[1] == proj[1] && proj[2] > 0.f && proj[3] > 0.f &&
                          !no_fast_forms;          // (cx, cy > 0: the one-compare pixel range test of tsdf_sample_fast)
-    const dim3 grid((n_items * DF_RIGID_STRIP + 3) / 4);             // 4 waves per workgroup; those past the plan's end return at once
+    const dim3 grid((n_items + 3) / 4);            // 4 waves per workgroup; those past the plan's end return at once
 #ifdef DF_TRACE_WG
     static unsigned long long* trace_dev = nullptr; static size_t trace_cap = 0;
     const size_t trace_n = (size_t)grid.x * 4 * 4;
@@ -916,7 +896,6 @@ extern "C" int dfusion_integrate_ex(const uint16_t* dists, size_t pitch, int col
         free(h);
     }
 #endif
-    release_scratch();
     return rc;
 }
 

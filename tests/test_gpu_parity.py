@@ -8,6 +8,7 @@ Bar (BASELINE.json north_star / SURVEY.md 8d):
   * k-NN: identical index lists and distances; exact distance ties in nanoflann's tree order (tests/test_gpu_ties.py)
   * ray-cast: identical hit mask, vertex |delta| <= 1e-4 m, normal |delta| <= 1e-3
 """
+import functools
 import os
 
 import numpy as np
@@ -100,7 +101,7 @@ def test_integrate_rigid_bit_exact(cfg):
 
 @pytest.mark.parametrize("cfg", [SMALL, MID], ids=["64", "128"])
 def test_integrate_rigid_depth_cull_is_result_identical(cfg):
-    """The behind-the-surface skip of the rigid sweep (max-pyramid of dists, conservative per 16-plane sub-chunk) must not change
+    """The behind-the-surface skip of the rigid sweep (max-pyramid of dists, conservative per 8-plane sub-chunk) must not change
     a single bit: 3 frames with it, 3 frames without, plus an all-invalid and a one-pixel depth image."""
     sc = Scene(cfg, n_frames=3, with_nodes=False)
     intr = Intr(*cfg.intr)
@@ -135,6 +136,59 @@ def test_integrate_rigid_slabs_equal_full():
         v.integrate(upload_u16(sc.dists[0]), sc.cam_poses[0], intr)
         parts.append(v.download())
     assert np.array_equal(np.concatenate(parts, 0), full.download())
+
+
+@functools.lru_cache(maxsize=None)
+def _odd_depth_scene():
+    """Three frames into a (36, 20, 45) volume and the oracle's result (read-only).  45 planes: the second chunk is planes 32-44 and
+    its last sub-chunk the five planes 40-44 -- with two planes per batch the only kind of run that the sweep's pipelined form does
+    not take.  The volume is pulled towards the camera so that these planes cut the sphere: voxels beside it saturate against the back
+    plane, voxels on its rim do not.  The x / y offsets keep every column's camera-frame x and y off zero (the short forms' domain)."""
+    cfg = synth.Config((36, 20, 45), 1.0, cols=67, rows=45, nodes=0)
+    sc = Scene(cfg, n_frames=3, with_nodes=False)
+    sc.pose = synth.translation(-0.49, -0.51, 0.06)
+    ref = sc.new_volume()
+    n_ref = 0
+    for f in range(3):
+        n_ref += O.integrate(sc.dists[f], ref, sc.ovol(ref), synth.aff12(sc.vol2cam(f)), sc.intr)
+    ref.setflags(write=False)
+    return sc, ref, n_ref
+
+
+def _assert_last_subchunk_is_exercised(ref, z0, z1):
+    t, w = decode(ref[z0:z1])
+    assert ((w > 0) & (t == 1)).any() and ((w > 0) & (t != 1)).any(), "planes %d-%d: no saturated or no unsaturated update" % (z0, z1 - 1)
+
+
+@pytest.mark.parametrize("flags", [0, capi.DF_RIGID_NO_SAT, capi.DF_RIGID_NO_SHORT_FORMS, capi.DF_RIGID_NO_DEPTH_CULL | capi.DF_RIGID_KEEP_ALL],
+                         ids=["default", "no-sat", "no-short-forms", "keep-all"])
+def test_integrate_rigid_odd_depth_bit_exact(flags):
+    """A Z extent that is no multiple of the 8-plane sub-chunk: the five-plane run 40-44 goes batch by batch, the last batch half
+    outside the run.  Bit for bit against the oracle, update count included."""
+    sc, ref, n_ref = _odd_depth_scene()
+    _assert_last_subchunk_is_exercised(ref, 40, 45)
+    intr = Intr(*sc.cfg.intr)
+    vol = make_gpu_volume(sc)
+    n_upd = torch.zeros(1, dtype=torch.int64, device="cuda")
+    for f in range(3):
+        vol.integrate(upload_u16(sc.dists[f]), sc.cam_poses[f], intr, n_updated=n_upd, flags=flags)
+    assert_volume_parity(vol.download(), ref)
+    assert int(n_upd.item()) == n_ref
+
+
+@pytest.mark.parametrize("z0, zn", [(3, 21), (24, 21)])
+def test_integrate_rigid_odd_slabs_equal_full(z0, zn):
+    """Slabs whose owned ranges are odd: chunks start at plane 3 (24) and end on a five-plane sub-chunk, 19-23 (40-44)."""
+    sc, ref, _ = _odd_depth_scene()
+    _assert_last_subchunk_is_exercised(ref, 40, 45)
+    intr = Intr(*sc.cfg.intr)
+    full = make_gpu_volume(sc)
+    part = make_gpu_volume(sc, slab=(z0, zn, 0))
+    for f in range(3):
+        full.integrate(upload_u16(sc.dists[f]), sc.cam_poses[f], intr)
+        part.integrate(upload_u16(sc.dists[f]), sc.cam_poses[f], intr)
+    assert np.array_equal(part.download(), full.download()[z0:z0 + zn])
+    assert np.array_equal(part.download(), ref[z0:z0 + zn])
 
 
 @pytest.mark.parametrize("k", [4, 8])
