@@ -14,7 +14,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libdfusion_hip.so")
 
 SOURCES = ["dfusion_volume.hip", "dfusion_warp.hip", "dfusion_warp_nodes.hip", "dfusion_warp_points.hip", "dfusion_warp_index.hip",
-           "dfusion_raycast.hip", "dfusion_frontend.hip", "dfusion_solver.hip", "dfusion_selftest.hip", "dfusion_warp_extend.hip", "dfusion_mesh.hip"]
+           "dfusion_raycast.hip", "dfusion_frontend.hip", "dfusion_solver.hip", "dfusion_selftest.hip", "dfusion_warp_extend.hip", "dfusion_mesh.hip", "dfusion_associate.hip"]
 HEADERS = ["dfusion_device.h", "dfusion_internal.h", "dfusion_nanoflann.h", "dfusion_pyramid.h", "dfusion_warp_topk.h", "dfusion_warp_sweep.h",
            "dfusion_warp_blocks.h", "dfusion_warp_pipe.h", os.path.join(REPO_DIR, "include", "dfusion.h")]
 
@@ -62,6 +62,7 @@ def kernel_source_sha(kernel):
          else "dfusion_raycast.hip" if k.startswith(("df_raycast", "df_extract"))
          else "dfusion_solver.hip" if k.startswith("df_sv")
          else "dfusion_mesh.hip" if k.startswith("df_mesh")
+         else "dfusion_associate.hip" if k.startswith("df_assoc")
          else "dfusion_volume.hip")
     h = hashlib.sha256()
     for name in _csrc_includes(f, []):
@@ -90,6 +91,7 @@ HOST_WARP_TESTS = os.path.join(HOST_DIR, "warp_tests")
 HOST_DEMO_CALLS = os.path.join(HOST_DIR, "demo_calls")
 HOST_REG_SOLVE = os.path.join(HOST_DIR, "reg_solve")
 HOST_ROBUST_SOLVE = os.path.join(HOST_DIR, "robust_solve")
+HOST_ASSOCIATE = os.path.join(HOST_DIR, "associate")
 HOST_ZSLAB_LIB = os.path.join(HOST_DIR, "libkfusion_zslab.so")       # kfusion::cuda::ZSlabComm: the RCCL side of the Z-slab sharding
 HOST_ZSLAB_APP = os.path.join(HOST_DIR, "zslab_frame")
 
@@ -106,8 +108,9 @@ def build_host(force=False, verbose=False):
     app5 = os.path.join(HOST_DIR, "apps", "zslab_frame.cpp")
     app6 = os.path.join(HOST_DIR, "apps", "reg_solve.cpp")
     app7 = os.path.join(HOST_DIR, "apps", "robust_solve.cpp")
-    deps = [src, app, app2, app3, app4, zsrc, app5, app6, app7, LIB_PATH] + [os.path.join(r, f) for r, _, fs in os.walk(os.path.join(HOST_DIR, "include")) for f in fs]
-    outs = (HOST_LIB, HOST_APP, HOST_KINFU_APP, HOST_WARP_TESTS, HOST_DEMO_CALLS, HOST_ZSLAB_LIB, HOST_ZSLAB_APP, HOST_REG_SOLVE, HOST_ROBUST_SOLVE)
+    app8 = os.path.join(HOST_DIR, "apps", "associate.cpp")
+    deps = [src, app, app2, app3, app4, zsrc, app5, app6, app7, app8, LIB_PATH] + [os.path.join(r, f) for r, _, fs in os.walk(os.path.join(HOST_DIR, "include")) for f in fs]
+    outs = (HOST_LIB, HOST_APP, HOST_KINFU_APP, HOST_WARP_TESTS, HOST_DEMO_CALLS, HOST_ZSLAB_LIB, HOST_ZSLAB_APP, HOST_REG_SOLVE, HOST_ROBUST_SOLVE, HOST_ASSOCIATE)
     if not force and all(os.path.exists(f) for f in outs) and min(os.path.getmtime(f) for f in outs) >= max(os.path.getmtime(d) for d in deps):
         return HOST_LIB, HOST_APP
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
@@ -121,6 +124,7 @@ def build_host(force=False, verbose=False):
             common + [app4, "-o", HOST_DEMO_CALLS, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + [app6, "-o", HOST_REG_SOLVE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + [app7, "-o", HOST_ROBUST_SOLVE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
+            common + [app8, "-o", HOST_ASSOCIATE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + ["-fPIC", "-shared", zsrc, "-o", HOST_ZSLAB_LIB, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-lrccl", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + [app5, "-o", HOST_ZSLAB_APP, "-L", HOST_DIR, "-lkfusion_zslab", "-lkfusion_hip"] + link + ["-lrccl", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."]]
     for c in cmds:

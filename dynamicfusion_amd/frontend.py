@@ -11,7 +11,7 @@ import torch
 
 from . import capi
 from .synth import aff12
-from .tsdf_volume import BGRA, F4, F32, U16, Intr, _image, _stream
+from .tsdf_volume import BGRA, F4, F32, U16, Intr, _flat, _image, _ptr, _stream
 
 
 def intr_level(intr, level):
@@ -148,6 +148,37 @@ def renderTangentColors(normals, image=None):
     capi.check(capi.lib().dfusion_render_tangent_colors(np_, npitch, cols, rows, ip, ipitch, _stream()),
                "dfusion_render_tangent_colors")
     return image
+
+
+def associateProjective(intr, points, normals, live_points, live_normals, dist_thres, min_cosine, occlusion_margin=-1.0,
+                        return_status=False, return_counts=False):
+    """Projective data association for the warp solve (include/dfusion.h dfusion_associate_projective): every predicted point
+    (device [N, 3], camera frame of the live image; `normals` [N, 3] or None together with `live_normals`) is paired with the sample
+    of `live_points` (float32 [rows, cols, 4]) at the pixel it projects to.  Returns live [N, 3] -- rejected points are all-NaN
+    (0x7fffffff), which the solvers skip -- then, if asked for, status (uint8 [N]: 0 paired, 1 invalid, 2 behind, 3 outside,
+    4 occluded, 5 hole, 6 far, 7 normal) and counts (int64 [8], points per status), all device tensors.  occlusion_margin < 0
+    switches the occlusion test off."""
+    if (normals is None) != (live_normals is None):
+        raise ValueError("normals and live_normals go together")
+    lp, lpitch, rows, cols = _image(live_points, F4)
+    lnp, lnpitch = _sized(live_normals, F4, rows, cols) if live_normals is not None else (None, 0)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points %s %s, expected float32 [N, 3]" % (points.dtype, tuple(points.shape)))
+    n = int(points.shape[0])
+    if normals is not None and (normals.dtype != torch.float32 or tuple(normals.shape) != (n, 3)):
+        raise ValueError("normals %s %s, expected float32 [%d, 3]" % (normals.dtype, tuple(normals.shape), n))
+    if n == 0:
+        normals, lnp = None, None                       # (an empty tensor has no address: nothing is read either way)
+    dev = live_points.device
+    live = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev) if return_status else None
+    counts = torch.empty(8, dtype=torch.int64, device=dev) if return_counts else None
+    capi.check(capi.lib().dfusion_associate_projective(
+        _flat(points), _flat(normals) if normals is not None else None, n, lp, lpitch, lnp, lnpitch, cols, rows, intr.as_proj(),
+        float(dist_thres), float(min_cosine), float(occlusion_margin), _ptr(live), _ptr(status) if return_status else None,
+        _ptr(counts) if return_counts else None, _stream()), "dfusion_associate_projective")
+    out = (live,) + ((status,) if return_status else ()) + ((counts,) if return_counts else ())
+    return out[0] if len(out) == 1 else out
 
 
 def unpack_icp_sums(sums):

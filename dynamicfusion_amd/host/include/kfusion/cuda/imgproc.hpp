@@ -39,6 +39,16 @@ void computePointNormals(const Intr& intr, const Depth& depth, Cloud& points, No
 void resizeDepthNormals(const Depth& depth, const Normals& normals, Depth& depth_out, Normals& normals_out);
 void resizePointsNormals(const Cloud& points, const Normals& normals, Cloud& points_out, Normals& normals_out);
 
+// ---- projective data association for the warp solve (no reference counterpart; include/dfusion.h dfusion_associate_projective)
+// Pairs each of the n predicted points (packed float3, camera frame of the live image; `normals` likewise, or an EMPTY array: then the
+// normal test is off and live_normals is not read) with the live sample at the pixel it projects to.  live_out (grown to 3 n floats if
+// smaller) receives the paired sample or three NaN words (0x7fffffff), which WarpField::energy_data skips; status (n bytes: 0 paired,
+// 1 invalid, 2 behind, 3 outside, 4 occluded, 5 hole, 6 far, 7 normal) and counts (8 numbers, points per status) are device arrays too,
+// created if too small, nullptr = not wanted.  occlusion_margin < 0 switches the occlusion test off.
+void associateProjective(const Intr& intr, const DeviceArray<float>& points, const DeviceArray<float>& normals, int n, const Cloud& live_points,
+                         const Normals& live_normals, float dist_thres, float min_cosine, float occlusion_margin, DeviceArray<float>& live_out,
+                         DeviceArray<unsigned char>* status = nullptr, DeviceArray<unsigned long long>* counts = nullptr);
+
 // ---- the views KinFu::renderImage returns (BGRA, `image` is created rows x cols)                              imgproc.cpp:152-201
 // Phong shading of a depth image / a points image with its normals, light at light_pose (metres, camera frame)
 void renderImage(const Depth& depth, const Normals& normals, const Intr& intr, const Vec3f& light_pose, Image& image);

@@ -5,6 +5,7 @@
 // device_resident (default on: same results as the reference's host staging, bit for bit, without the ~50 MB/frame of PCIe traffic;
 // switch off when optimiseWarp is overridden, which needs the host vectors).
 #pragma once
+#include <array>
 #include <memory>
 #include <vector>
 #include <kfusion/types.hpp>
@@ -53,6 +54,12 @@ namespace kfusion
         int warp_robust_rounds = 1;          // robust warp solve (WarpField::setRobust): re-weighted rounds per frame,
         float warp_tukey_c = 0.f;            // the Tukey threshold of the point residuals (metres; 0 = quadratic data term)
         float warp_huber_delta = 0.f;        // and the Huber threshold of the graph edges (0 = quadratic regularisation); default: off
+        bool warp_projective_association = false;   // device-resident dynamicfusion(): pair every warped point with the live sample at the
+                                             // pixel it projects to (cuda::associateProjective) instead of by pixel index; default off =
+                                             // the reference's pairing
+        float warp_assoc_dist_thres = 0.05f; // its distance gate (metres),
+        float warp_assoc_angle_thres = 0.52359878f;   // its normal gate (radians: 30 degrees, used as its cosine)
+        float warp_assoc_occlusion_margin = 0.02f;    // and how far behind the nearest warped point of its pixel a point may lie (< 0: off)
     };
 
     class KinFu
@@ -84,6 +91,9 @@ namespace kfusion
         /// kinfu.cpp:408-436: the same views of a fresh ray-cast from `pose`
         void renderImage(cuda::Image& image, const Affine3f& pose, int flags = 0);
         Affine3f getCameraPose(int time = -1) const;
+        /// the last frame's association: points per status (0 paired, 1 invalid, 2 behind, 3 outside, 4 occluded, 5 hole, 6 far,
+        /// 7 normal); all zero until a frame ran with warp_projective_association.  Waits for the device.
+        std::array<unsigned long long, 8> associationCounts() const;
 
     protected:
         /// optimiser_->optimiseWarpData(canonical, canonical_normals, live, canonical_normals) (kinfu.cpp:389) on the host-staged data
@@ -102,7 +112,8 @@ namespace kfusion
         std::unique_ptr<WarpField> warp_;
         // scratch of the device-resident dynamicfusion()
         cuda::Cloud df_cloud_; cuda::Normals df_normals_;
-        cuda::DeviceArray<float> df_points3_, df_normals3_, df_live3_;
+        cuda::DeviceArray<float> df_points3_, df_normals3_, df_live3_, df_assoc3_;
+        cuda::DeviceArray<unsigned long long> df_assoc_counts_; bool df_assoc_valid_ = false;
         cuda::DeviceArray<Point> df_warped4_;
         cuda::Normals df_live_normals_;
     };

@@ -730,6 +730,24 @@ void kfusion::cuda::resizePointsNormals(const Cloud& points, const Normals& norm
                                         points.rows(), (float*)points_out.ptr(), points_out.step(), (float*)normals_out.ptr(),
                                         normals_out.step(), nullptr));
 }
+void kfusion::cuda::associateProjective(const Intr& intr, const DeviceArray<float>& points, const DeviceArray<float>& normals, int n,
+                                        const Cloud& live_points, const Normals& live_normals, float dist_thres, float min_cosine,
+                                        float occlusion_margin, DeviceArray<float>& live_out, DeviceArray<unsigned char>* status,
+                                        DeviceArray<unsigned long long>* counts)
+{
+    const size_t n3 = 3 * (size_t)(n > 0 ? n : 0);
+    if (points.size() < n3 || (normals.size() != 0 && normals.size() < n3))
+        kfusion::cuda::error("points / normals hold fewer than n points", __FILE__, __LINE__, "associateProjective");
+    if (live_out.size() < n3) live_out.create(n3);
+    if (status && status->size() < n3 / 3) status->create(n3 / 3);
+    if (counts && counts->size() < 8) counts->create(8);
+    const bool with_normals = normals.size() != 0;
+    const float iv[4] = {intr.fx, intr.fy, intr.cx, intr.cy};
+    KF_DF(dfusion_associate_projective(points.ptr(), with_normals ? normals.ptr() : nullptr, n, (const float*)live_points.ptr(), live_points.step(),
+                                       with_normals ? (const float*)live_normals.ptr() : nullptr, with_normals ? live_normals.step() : 0,
+                                       live_points.cols(), live_points.rows(), iv, dist_thres, min_cosine, occlusion_margin, live_out.ptr(),
+                                       status ? status->ptr() : nullptr, counts ? counts->ptr() : nullptr, nullptr));
+}
 
 // ------------------------------------------------------------------------------------------ views (imgproc.cpp:152-201)
 void kfusion::cuda::renderImage(const Depth& depth, const Normals& normals, const Intr& intr, const Vec3f& light_pose, Image& image)
@@ -1077,7 +1095,14 @@ bool KinFu::operator()(const cuda::Depth& depth, const cuda::Image& /*image*/)  
     return ++frame_counter_, true;
 }
 
-void KinFu::dynamicfusion(cuda::Depth& depth, cuda::Cloud live_frame, cuda::Normals /*current_normals*/)   // kinfu.cpp:344-400
+std::array<unsigned long long, 8> KinFu::associationCounts() const
+{
+    std::array<unsigned long long, 8> c = {};
+    if (df_assoc_valid_) df_assoc_counts_.download(c.data());
+    return c;
+}
+
+void KinFu::dynamicfusion(cuda::Depth& depth, cuda::Cloud live_frame, cuda::Normals current_normals)   // kinfu.cpp:344-400
 {
     const Affine3f camera_pose = poses_.back();
     if (warp_->nodeCount() < (size_t)warp_->k()) {                      // no usable warp field (empty first frame): plain KinFu fusion
@@ -1103,8 +1128,24 @@ void KinFu::dynamicfusion(cuda::Depth& depth, cuda::Cloud live_frame, cuda::Norm
         warp_->warp(df_points3_, df_normals3_, (int)n);                      // :387
         if (params_.warp_solver_iterations > 0) {                           // :389 optimiser_->optimiseWarpData(canonical, normals, live, normals)
             if (df_live3_.size() < 3 * n) df_live3_.create(3 * n);
-            KF_DF(dfusion_transform_points((const float*)live_frame.ptr(), live_frame.step(), 4, df_live3_.ptr(), (size_t)depth.cols() * 12, 3,
-                                           depth.cols(), depth.rows(), nullptr, nullptr));
+            if (params_.warp_projective_association) {
+                // DynamicFusion's data association instead of the reference's pairing by pixel index: the warped points go into the
+                // camera frame (df_live3_ holds them for a moment), each is paired with the live sample at the pixel it projects to
+                // (visible surface only, the warped normals against the live ones), and the pairs come back into the frame the
+                // solver's points are in -- rejected points as NaN, which the solve skips
+                if (df_assoc3_.size() < 3 * n) df_assoc3_.create(3 * n);
+                float pose12[12]; affine_to_aff12(camera_pose, pose12);
+                KF_DF(dfusion_transform_points(df_points3_.ptr(), 3 * n * sizeof(float), 3, df_live3_.ptr(), 3 * n * sizeof(float), 3, (int)n, 1,
+                                               pose12, nullptr));
+                cuda::associateProjective(params_.intr, df_live3_, df_normals3_, (int)n, live_frame, current_normals, params_.warp_assoc_dist_thres,
+                                          std::cos(params_.warp_assoc_angle_thres), params_.warp_assoc_occlusion_margin, df_assoc3_, nullptr,
+                                          &df_assoc_counts_);
+                df_assoc_valid_ = true;
+                KF_DF(dfusion_transform_points(df_assoc3_.ptr(), 3 * n * sizeof(float), 3, df_live3_.ptr(), 3 * n * sizeof(float), 3, (int)n, 1,
+                                               inv12, nullptr));
+            } else
+                KF_DF(dfusion_transform_points((const float*)live_frame.ptr(), live_frame.step(), 4, df_live3_.ptr(), (size_t)depth.cols() * 12, 3,
+                                               depth.cols(), depth.rows(), nullptr, nullptr));
             warp_->setSolverIterations(params_.warp_solver_iterations);
             warp_->setRegularisation(params_.warp_reg_neighbours, params_.warp_reg_lambda);
             warp_->setRobust(params_.warp_robust_rounds, params_.warp_tukey_c, params_.warp_huber_delta);

@@ -520,6 +520,36 @@ int dfusion_render_tangent_colors(const float *normals_dev, size_t normals_pitch
 int dfusion_transform_points(const float *in_dev, size_t in_pitch, int in_stride, float *out_dev, size_t out_pitch, int out_stride,
                              int cols, int rows, const float aff[12], dfStream stream);
 
+/* Projective data association for the warp solve (no reference counterpart: KinFu::dynamicfusion pairs ray-cast point i with live
+ * point i; additive, ABI 7).  Every predicted point p (packed float3 [N], in the camera frame of the live image, e.g. the warped
+ * ray-cast points) with its normal n (nullable, together with live_normals_dev) is paired with the sample of the live points image
+ * (float4, byte pitch) at the pixel it projects to, visible surface only.  intr = {fx, fy, cx, cy} of that image.  Arithmetic is f32
+ * without contraction; the FIRST failing test names the point's status:
+ *   1 invalid   a component of p (with normals: or of n) is not finite
+ *   2 behind    !(p.z > 0)
+ *   3 outside   u = fmaf(fx, p.x / p.z, cx), v = fmaf(fy, p.y / p.z, cy) (the ICP's projection, dfusion_icp_sums_points); rejected unless
+ *               u >= 0 && v >= 0 && u < (float)cols && v < (float)rows.  The pixel is (ui, vi) = ((int)u, (int)v)
+ *   4 occluded  zmin = the smallest p.z over ALL points that passed tests 1-3 and fall on the same pixel; rejected iff
+ *               occlusion_margin >= 0 and p.z - zmin > occlusion_margin (margin 0 keeps exact ties; a negative -- or NaN -- margin
+ *               switches the test off)
+ *   5 hole      q = live_points(vi, ui); rejected iff isnan(q.x) (the ICP's rule)
+ *   6 far       d = p - q; rejected iff dot(d, d) > dist_thres * dist_thres, dot(a, b) = fmaf(a.x, b.x, fmaf(a.y, b.y, a.z * b.z))
+ *               (equality is kept)
+ *   7 normal    with normals only: rejected unless fabsf(dot(n, live_normals(vi, ui))) >= min_cosine (a NaN live normal rejects,
+ *               equality is kept)
+ *   0 paired    live_out[i] = (q.x, q.y, q.z)
+ * On any rejection all three words of live_out[i] are 0x7fffffff: dfusion_warp_solve* skip such pairs.  status_dev (nullable) [N]
+ * receives the statuses, counts_dev (nullable) [8] is OVERWRITTEN with the number of points per status (they sum to N).
+ * DF_E_INVALID: N < 0, cols <= 0, rows <= 0, exactly one of the two normal pointers NULL, a pitch < 16 * cols, dist_thres negative or
+ * NaN, min_cosine NaN, intr NULL, and -- for N > 0 -- points_dev, live_points_dev or live_out_dev NULL.  N == 0 enqueues nothing but
+ * the zeroing of counts_dev.  Three short launches (depth-buffer fill, integer atomic-min splat, resolve; the resolve alone when the
+ * occlusion test is off); the depth buffer (4 bytes per pixel) lives in the per-(device, stream) scratch dfusion_integrate uses, so
+ * dfusion_release_scratch() frees it.  No float atomics: the output does not depend on scheduling.                                   */
+int dfusion_associate_projective(const float *points_dev, const float *normals_dev, int N, const float *live_points_dev,
+                                 size_t live_points_pitch, const float *live_normals_dev, size_t live_normals_pitch, int cols, int rows,
+                                 const float intr[4], float dist_thres, float min_cosine, float occlusion_margin, float *live_out_dev,
+                                 unsigned char *status_dev, unsigned long long *counts_dev, dfStream stream);
+
 /* device::ComputeIcpHelper::operator() (internal.hpp:91-92; kfusion/src/cuda/proj_icp.cu:30-441): one Gauss-Newton
  * accumulation of point-to-plane ICP.  aff = current estimate curr -> prev; dist2_thres = dist_thres^2 and
  * min_cosine = cos(angle_thres) (projective_icp.cpp:11-15).  sums_dev[27] = the upper triangle of A (6x6) interleaved
