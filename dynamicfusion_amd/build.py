@@ -92,6 +92,7 @@ HOST_DEMO_CALLS = os.path.join(HOST_DIR, "demo_calls")
 HOST_REG_SOLVE = os.path.join(HOST_DIR, "reg_solve")
 HOST_ROBUST_SOLVE = os.path.join(HOST_DIR, "robust_solve")
 HOST_ASSOCIATE = os.path.join(HOST_DIR, "associate")
+HOST_PLANE_SOLVE = os.path.join(HOST_DIR, "plane_solve")
 HOST_ZSLAB_LIB = os.path.join(HOST_DIR, "libkfusion_zslab.so")       # kfusion::cuda::ZSlabComm: the RCCL side of the Z-slab sharding
 HOST_ZSLAB_APP = os.path.join(HOST_DIR, "zslab_frame")
 
@@ -109,8 +110,9 @@ def build_host(force=False, verbose=False):
     app6 = os.path.join(HOST_DIR, "apps", "reg_solve.cpp")
     app7 = os.path.join(HOST_DIR, "apps", "robust_solve.cpp")
     app8 = os.path.join(HOST_DIR, "apps", "associate.cpp")
-    deps = [src, app, app2, app3, app4, zsrc, app5, app6, app7, app8, LIB_PATH] + [os.path.join(r, f) for r, _, fs in os.walk(os.path.join(HOST_DIR, "include")) for f in fs]
-    outs = (HOST_LIB, HOST_APP, HOST_KINFU_APP, HOST_WARP_TESTS, HOST_DEMO_CALLS, HOST_ZSLAB_LIB, HOST_ZSLAB_APP, HOST_REG_SOLVE, HOST_ROBUST_SOLVE, HOST_ASSOCIATE)
+    app9 = os.path.join(HOST_DIR, "apps", "plane_solve.cpp")
+    deps = [src, app, app2, app3, app4, zsrc, app5, app6, app7, app8, app9, LIB_PATH] + [os.path.join(r, f) for r, _, fs in os.walk(os.path.join(HOST_DIR, "include")) for f in fs]
+    outs = (HOST_LIB, HOST_APP, HOST_KINFU_APP, HOST_WARP_TESTS, HOST_DEMO_CALLS, HOST_ZSLAB_LIB, HOST_ZSLAB_APP, HOST_REG_SOLVE, HOST_ROBUST_SOLVE, HOST_ASSOCIATE, HOST_PLANE_SOLVE)
     if not force and all(os.path.exists(f) for f in outs) and min(os.path.getmtime(f) for f in outs) >= max(os.path.getmtime(d) for d in deps):
         return HOST_LIB, HOST_APP
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
@@ -125,6 +127,7 @@ def build_host(force=False, verbose=False):
             common + [app6, "-o", HOST_REG_SOLVE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + [app7, "-o", HOST_ROBUST_SOLVE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + [app8, "-o", HOST_ASSOCIATE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
+            common + [app9, "-o", HOST_PLANE_SOLVE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + ["-fPIC", "-shared", zsrc, "-o", HOST_ZSLAB_LIB, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-lrccl", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + [app5, "-o", HOST_ZSLAB_APP, "-L", HOST_DIR, "-lkfusion_zslab", "-lkfusion_hip"] + link + ["-lrccl", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."]]
     for c in cmds:

@@ -61,7 +61,7 @@ SYMBOLS = [
     "dfusion_selftest_exact_forms", "dfusion_warp_set_point_tiling", "dfusion_integrate_ex", "dfusion_warp_debug_counters", "dfusion_warp_alive_blocks", "dfusion_warp_coded_blocks", "dfusion_raycast_points_of_keys_rows", "dfusion_raycast_sum_pieces", "dfusion_raycast_min_pieces", "dfusion_integrate_warped_prepare", "dfusion_integrate_warped_sweep",
     "dfusion_render_image_points", "dfusion_render_image_depth", "dfusion_render_tangent_colors", "dfusion_cloud_to_depth",
     "dfusion_warp_extend", "dfusion_warp_solve", "dfusion_warp_node_graph", "dfusion_extract_mesh",
-    "dfusion_warp_solve_robust", "dfusion_associate_projective",
+    "dfusion_warp_solve_robust", "dfusion_associate_projective", "dfusion_warp_solve_plane",
 ]
 
 
@@ -147,6 +147,8 @@ def load(path, strict=True):
     L.dfusion_warp_node_graph.argtypes = [vp, C.c_int, vp, vp, vp]
     L.dfusion_warp_solve_robust.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float,
                                             vp, vp, vp, vp, vp]
+    L.dfusion_warp_solve_plane.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float,
+                                           vp, vp, vp, vp, vp]
     L.dfusion_associate_projective.argtypes = [vp, vp, C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, fp, C.c_float, C.c_float, C.c_float,
                                                vp, vp, vp, vp]
     L.dfusion_warp_extend.argtypes = [vp, C.c_int, vp, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp, C.POINTER(C.c_int),

@@ -16,7 +16,8 @@
 //                                       with the restatement in oracle/dfusion_frontend_oracle.c);
 //   dot products / vector updates     : one 1024-thread workgroup (M <= 65535), fixed tree.
 // dfusion_warp_solve adds DynamicFusion's regularisation term over a node graph, dfusion_warp_solve_robust a Tukey
-// penalty on the data term and a Huber penalty on the edges by re-weighted rounds.  The three entry points share one
+// penalty on the data term and a Huber penalty on the edges by re-weighted rounds, dfusion_warp_solve_plane takes the
+// data term along the model normals (point-to-plane).  The four entry points share one
 // host pipeline at the end of this file: one workspace (SvWorkspace), one preparation (df_sv_prepare: what depends only on the
 // canonical points and the node positions) and one round loop (df_sv_rounds), in which a term that is switched off launches nothing.
 // Nothing returns to the host between iterations: once every component has converged (scal[SV_ACTIVE] == 0) the kernels of the
@@ -29,7 +30,10 @@
 #define SV_BLOCK 1024
 
 // ---- per point: validity, weights, node ids (sort keys), residual at the current translations
-__global__ __launch_bounds__(256) void df_sv_setup_kernel(const float* __restrict__ canonical, const float* __restrict__ live, int N, int k,
+// PLANE: a normal with a NaN or infinite component makes the point invalid too (normals is not read otherwise)
+template <bool PLANE>
+__global__ __launch_bounds__(256) void df_sv_setup_kernel(const float* __restrict__ canonical, const float* __restrict__ live,
+                                                          const float* __restrict__ normals, int N, int k,
                                                           const int* __restrict__ idx, const float* __restrict__ d2,
                                                           const float4* __restrict__ pos_sigma, const float4* __restrict__ node_t, int M,
                                                           float* __restrict__ w, unsigned int* __restrict__ keys,
@@ -39,7 +43,8 @@ __global__ __launch_bounds__(256) void df_sv_setup_kernel(const float* __restric
     if (v >= N) return;
     const float cx = canonical[3 * v], cy = canonical[3 * v + 1], cz = canonical[3 * v + 2];
     const float lx = live[3 * v], ly = live[3 * v + 1], lz = live[3 * v + 2];
-    const bool valid = !(isnan(cx) || isnan(cy) || isnan(cz) || isnan(lx) || isnan(ly) || isnan(lz));   // warp_field.cpp:130-136
+    bool valid = !(isnan(cx) || isnan(cy) || isnan(cz) || isnan(lx) || isnan(ly) || isnan(lz));         // warp_field.cpp:130-136
+    if constexpr (PLANE) valid = valid && isfinite(normals[3 * v]) && isfinite(normals[3 * v + 1]) && isfinite(normals[3 * v + 2]);
     float sx = 0.f, sy = 0.f, sz = 0.f;
     for (int j = 0; j < k; ++j) {
         const int e = v * k + j;
@@ -73,16 +78,20 @@ __global__ __launch_bounds__(256) void df_sv_offsets_kernel(const unsigned int* 
 // ---- u = W p : per point, slot order
 // K > 0: compile-time neighbour count, so that the 2K entry loads and 3K gathers of a point are all in flight before the first sum
 // (with a run-time k the loop issues and waits entry by entry); K = 0: any k.  Same sums in the same order either way.
-template <int K>
+// PLANE: u = n (n . W p), the point-to-plane operator's N N^T W p.  The normal is loaded before the entries, so that it
+// arrives while the gathers are in flight, and an invalid point (no entry: its normal may hold anything) stores 0.
+template <int K, bool PLANE>
 __global__ __launch_bounds__(256) void df_sv_w_apply_kernel(const float* __restrict__ w, const unsigned int* __restrict__ keys, int N, int k,
                                                             int M, const float* __restrict__ p, float* __restrict__ u,
-                                                            const float* __restrict__ active)
+                                                            const float* __restrict__ active, const float* __restrict__ normals)
 {
     // `active` (nullable): scal + SV_ACTIVE, the number of CG components still iterating.  Once it is 0 every further step is an exact no-op
     // (alpha = beta = 0), so the kernels of the remaining steps return at once -- the host enqueues all steps without looking.
     if (active && *active == 0.f) return;
     const int v = blockIdx.x * 256 + threadIdx.x;
     if (v >= N) return;
+    float nx = 0.f, ny = 0.f, nz = 0.f;
+    if constexpr (PLANE) { nx = normals[3 * v]; ny = normals[3 * v + 1]; nz = normals[3 * v + 2]; }
     float sx = 0.f, sy = 0.f, sz = 0.f;
     if constexpr (K > 0) {
         unsigned int n[K]; float wj[K], px[K], py[K], pz[K];
@@ -105,6 +114,11 @@ __global__ __launch_bounds__(256) void df_sv_w_apply_kernel(const float* __restr
                 sx = sx + wj * p[3 * n]; sy = sy + wj * p[3 * n + 1]; sz = sz + wj * p[3 * n + 2];
             }
         }
+    }
+    if constexpr (PLANE) {
+        const float d = (nx * sx + ny * sy) + nz * sz;
+        const bool valid = keys[v * k] < (unsigned int)M;               // (a point's k entries are valid together)
+        sx = valid ? nx * d : 0.f; sy = valid ? ny * d : 0.f; sz = valid ? nz * d : 0.f;
     }
     u[3 * v] = sx; u[3 * v + 1] = sy; u[3 * v + 2] = sz;
 }
@@ -160,7 +174,8 @@ __global__ __launch_bounds__(256) void df_sv_wt_apply_kernel(const unsigned int*
     }
 }
 
-// ---- single-workgroup vector algebra: three independent CG recurrences (x, y, z components share the matrix)
+// ---- single-workgroup vector algebra: three independent CG recurrences (x, y, z components share the matrix), or ONE over all three
+// (COUPLED, below: the point-to-plane matrix mixes the components)
 // block-wide sums of three values: thread t owns elements t, t + 1024, ... ; then the tree 512 .. 1 in LDS
 __device__ __forceinline__ void sv_block_sum3(float (&s)[3], float* lds /* [3][1024] */)
 {
@@ -199,6 +214,16 @@ enum {
     SV_SCAL_N = 16
 };
 #define SV_REL_TOL2 1.0e-10f        // stop a component once |r|^2 <= 1e-10 |r0|^2
+
+// COUPLED (the point-to-plane solve, whose matrix differs between x, y and z): ONE recurrence over the 3M vector.  Every dot product is
+// the three per-component sums combined; with the same value in all three slots the per-component code below is the scalar recurrence.
+template <bool COUPLED>
+__device__ __forceinline__ void sv_cg_couple(float (&s)[3])
+{
+    if constexpr (COUPLED) s[0] = s[1] = s[2] = (s[0] + s[1]) + s[2];
+}
+
+template <bool COUPLED>
 __global__ __launch_bounds__(SV_BLOCK) void df_sv_init_kernel(const float* __restrict__ r, int M, float* __restrict__ x, float* __restrict__ p,
                                                               float* __restrict__ scal)
 {
@@ -207,9 +232,10 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_init_kernel(const float* __res
     for (int n = threadIdx.x; n < M; n += SV_BLOCK)
         for (int c = 0; c < 3; ++c) { const float rv = r[3 * n + c]; x[3 * n + c] = 0.f; p[3 * n + c] = rv; s[c] = s[c] + rv * rv; }
     sv_block_sum3(s, lds);
+    sv_cg_couple<COUPLED>(s);
     if (threadIdx.x == 0) {
         for (int c = 0; c < 3; ++c) { scal[SV_RR + c] = s[c]; scal[SV_RR0 + c] = s[c]; }
-        scal[SV_ACTIVE] = (float)((s[0] > 0.f) + (s[1] > 0.f) + (s[2] > 0.f));
+        scal[SV_ACTIVE] = COUPLED ? (float)(s[0] > 0.f) : (float)((s[0] > 0.f) + (s[1] > 0.f) + (s[2] > 0.f));
     }
 }
 
@@ -225,6 +251,8 @@ __device__ __forceinline__ float sv_cg_beta(float alpha, float rr, float rr_old)
 }
 
 // one thread, once every thread has read scal's rr: the new rr (0 = frozen from here on) and the number of components left
+// (COUPLED: the three slots hold one recurrence, which counts once)
+template <bool COUPLED>
 __device__ __forceinline__ void sv_cg_freeze(const float (&alpha)[3], const float (&rr)[3], float* scal)
 {
     float active = 0.f;
@@ -233,9 +261,10 @@ __device__ __forceinline__ void sv_cg_freeze(const float (&alpha)[3], const floa
         scal[SV_RR + c] = keep;
         active += keep > 0.f ? 1.f : 0.f;
     }
-    scal[SV_ACTIVE] = active;
+    scal[SV_ACTIVE] = COUPLED ? (active > 0.f ? 1.f : 0.f) : active;
 }
 
+template <bool COUPLED>
 __global__ __launch_bounds__(SV_BLOCK) void df_sv_step_kernel(const float* __restrict__ q, int M, float* __restrict__ x, float* __restrict__ r,
                                                               float* __restrict__ p, float* __restrict__ scal)
 {
@@ -245,6 +274,7 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_step_kernel(const float* __res
     for (int n = threadIdx.x; n < M; n += SV_BLOCK)
         for (int c = 0; c < 3; ++c) pq[c] = pq[c] + p[3 * n + c] * q[3 * n + c];
     sv_block_sum3(pq, lds);
+    sv_cg_couple<COUPLED>(pq);
     float alpha[3], rr_old[3];
     for (int c = 0; c < 3; ++c) { rr_old[c] = scal[SV_RR + c]; alpha[c] = sv_cg_alpha(pq[c], rr_old[c]); }
     float rr[3] = {0.f, 0.f, 0.f};
@@ -256,17 +286,18 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_step_kernel(const float* __res
             rr[c] = rr[c] + rv * rv;
         }
     sv_block_sum3(rr, lds);
+    sv_cg_couple<COUPLED>(rr);
     float beta[3];
     for (int c = 0; c < 3; ++c) beta[c] = sv_cg_beta(alpha[c], rr[c], rr_old[c]);
     for (int n = threadIdx.x; n < M; n += SV_BLOCK)
         for (int c = 0; c < 3; ++c) p[3 * n + c] = r[3 * n + c] + beta[c] * p[3 * n + c];
     __syncthreads();
-    if (threadIdx.x == 0) sv_cg_freeze(alpha, rr, scal);
+    if (threadIdx.x == 0) sv_cg_freeze<COUPLED>(alpha, rr, scal);
 }
 
 // df_sv_step_kernel for M <= EPT * SV_BLOCK: x, r, p, q are read once and stay in registers between the three passes (the passes of
 // the kernel above each wait for their own global loads).  Same element -> thread assignment, same sums, same trees.
-template <int EPT>
+template <int EPT, bool COUPLED>
 __global__ __launch_bounds__(SV_BLOCK) void df_sv_step_reg_kernel(const float* __restrict__ q, int M, float* __restrict__ x, float* __restrict__ r,
                                                                   float* __restrict__ p, float* __restrict__ scal)
 {
@@ -290,6 +321,7 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_step_reg_kernel(const float* _
 #pragma unroll
             for (int c = 0; c < 3; ++c) pq[c] = pq[c] + pv[j][c] * qv[j][c];
     sv_block_sum3(pq, lds);
+    sv_cg_couple<COUPLED>(pq);
     float alpha[3], rr_old[3];
     for (int c = 0; c < 3; ++c) { rr_old[c] = scal[SV_RR + c]; alpha[c] = sv_cg_alpha(pq[c], rr_old[c]); }
     float rr[3] = {0.f, 0.f, 0.f};
@@ -303,6 +335,7 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_step_reg_kernel(const float* _
                 rr[c] = rr[c] + rv[j][c] * rv[j][c];
             }
     sv_block_sum3(rr, lds);
+    sv_cg_couple<COUPLED>(rr);
     float beta[3];
     for (int c = 0; c < 3; ++c) beta[c] = sv_cg_beta(alpha[c], rr[c], rr_old[c]);
 #pragma unroll
@@ -312,7 +345,7 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_step_reg_kernel(const float* _
 #pragma unroll
             for (int c = 0; c < 3; ++c) { x[3 * n + c] = xv[j][c]; r[3 * n + c] = rv[j][c]; p[3 * n + c] = rv[j][c] + beta[c] * pv[j][c]; }
     }
-    if (threadIdx.x == 0) sv_cg_freeze(alpha, rr, scal);
+    if (threadIdx.x == 0) sv_cg_freeze<COUPLED>(alpha, rr, scal);
 }
 
 // ---- energy = sum_v |e_v|^2 (single workgroup, same tree)
@@ -556,6 +589,54 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_huber_energy_kernel(const int*
     if (threadIdx.x == 0) *out = acc[0];
 }
 
+// ---------------------------------------------------------------- point-to-plane data term
+// E_data = sum_v rho_v^2, rho_v = n_v . e_v with the normals as given (never normalised): the rows of W are projected on n_v, so the
+// normal matrix is W^T N N^T W (df_sv_w_apply_kernel<K, true> followed by the unchanged W^T walk), the right-hand side W^T (n rho), and
+// the three components are one system (the COUPLED step kernels).  Tukey works on rho^2.
+
+// rho_v = (nx ex + ny ey) + nz ez and, with b, b_v = n_v rho_v; 0 for an invalid point (e = 0 there, but its normal may be NaN or inf)
+__global__ __launch_bounds__(256) void df_sv_plane_rho_kernel(const float* __restrict__ e, const float* __restrict__ normals,
+                                                              const unsigned int* __restrict__ keys, int N, int k, int M,
+                                                              float* __restrict__ rho, float* __restrict__ b)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= N) return;
+    const float nx = normals[3 * v], ny = normals[3 * v + 1], nz = normals[3 * v + 2];
+    const bool valid = keys[v * k] < (unsigned int)M;
+    const float r = valid ? (nx * e[3 * v] + ny * e[3 * v + 1]) + nz * e[3 * v + 2] : 0.f;
+    rho[v] = r;
+    if (b) { b[3 * v] = valid ? nx * r : 0.f; b[3 * v + 1] = valid ? ny * r : 0.f; b[3 * v + 2] = valid ? nz * r : 0.f; }
+}
+
+// df_sv_tukey_kernel with s = rho^2
+__global__ __launch_bounds__(256) void df_sv_plane_tukey_kernel(const float* __restrict__ rho, int N, float c2, float* __restrict__ omega)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= N) return;
+    const float s = rho[v] * rho[v];
+    const float u = 1.f - s / c2;
+    omega[v] = (s < c2) ? u * u : 0.f;
+}
+
+// ---- E_data = sum_v rho_v^2 (TUKEY: sum_v of df_sv_tukey_energy_kernel's value at s = rho_v^2): one value per point, thread t owns points
+// t, t + 1024, ..., then the 1024-tree
+template <bool TUKEY>
+__global__ __launch_bounds__(SV_BLOCK) void df_sv_plane_energy_kernel(const float* __restrict__ rho, int N, float c2, float* __restrict__ out)
+{
+    __shared__ float lds[3 * SV_BLOCK];
+    float acc[3] = {0.f, 0.f, 0.f};
+    const float third = c2 / 3.f;
+    for (int v = threadIdx.x; v < N; v += SV_BLOCK) {
+        const float s = rho[v] * rho[v];
+        if constexpr (TUKEY) {
+            const float u = 1.f - s / c2;
+            acc[0] = acc[0] + ((s < c2) ? third * (1.f - (u * u) * u) : third);
+        } else acc[0] = acc[0] + s;
+    }
+    sv_block_sum3(acc, lds);
+    if (threadIdx.x == 0) *out = acc[0];
+}
+
 // ---------------------------------------------------------------- host side
 // 256-byte aligned pieces of one buffer.  A carve-up is written once and run twice: from base 0, where `at` ends as the size to
 // reserve, and from the reserved buffer's address.
@@ -625,12 +706,13 @@ struct SvWorkspace {
     float* scal;                                            // [SV_SCAL_N]
     float* dq;                                              // [8M] the transforms a round writes
     float* g;                                               // [3Eg] edge values
+    float* rho;                                             // [N] point-to-plane: n . e (otherwise empty)
     float *omega, *sw_scaled;                               // [N], [E] Tukey: point weights, sorted_w' (no Tukey: empty)
     float *alpha_scaled, *omega_e;                          // [Eg] Huber: alpha', edge weights (no Huber: empty)
     char* sort; size_t sort_bytes;
 };
 
-static int df_sv_workspace(DfWarpField* wf, int N, int k, int M, int Eg, bool tukey, bool huber, hipStream_t st, SvWorkspace* ws)
+static int df_sv_workspace(DfWarpField* wf, int N, int k, int M, int Eg, bool plane, bool tukey, bool huber, hipStream_t st, SvWorkspace* ws)
 {
     const size_t E = (size_t)N * k, n = N, m = M, eg = Eg;
     int rc;
@@ -644,6 +726,7 @@ static int df_sv_workspace(DfWarpField* wf, int N, int k, int M, int Eg, bool tu
         ws->e0 = b.take<float>(3 * n); ws->u = b.take<float>(3 * n); ws->off = b.take<unsigned int>(m + 2);
         ws->x = b.take<float>(3 * m); ws->r = b.take<float>(3 * m); ws->p = b.take<float>(3 * m); ws->q = b.take<float>(3 * m);
         ws->scal = b.take<float>(SV_SCAL_N); ws->dq = b.take<float>(8 * m); ws->g = b.take<float>(3 * eg);
+        ws->rho = b.take<float>(plane ? n : 0);
         ws->omega = b.take<float>(tukey ? n : 0); ws->sw_scaled = b.take<float>(tukey ? E : 0);
         ws->alpha_scaled = b.take<float>(huber ? eg : 0); ws->omega_e = b.take<float>(huber ? eg : 0);
         ws->sort = b.take<char>(ws->sort_bytes);
@@ -655,8 +738,10 @@ static int df_sv_workspace(DfWarpField* wf, int N, int k, int M, int Eg, bool tu
 }
 
 // Once per call, what depends only on the canonical points and the node positions: the graph (kg > 0), the k-NN, the entries' weights
-// and node ids (with e0 at the transforms the handle holds now), the node offsets and the node-major lists.
-static int df_sv_prepare(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int kg, const SvWorkspace& ws, dfStream stream)
+// and node ids (with e0 at the transforms the handle holds now), the node offsets and the node-major lists.  `normals` (nullable: the
+// point-to-plane solve's) only add to what makes a point invalid.
+static int df_sv_prepare(DfWarpField* wf, int k, const float* canonical, const float* live, const float* normals, int N, int kg,
+                         const SvWorkspace& ws, dfStream stream)
 {
     hipStream_t st = (hipStream_t)stream;
     const int M = wf->M, E = N * k;
@@ -664,8 +749,8 @@ static int df_sv_prepare(DfWarpField* wf, int k, const float* canonical, const f
     int rc;
     if (kg && (rc = df_sv_graph(wf, kg, stream))) return rc;
     if ((rc = dfusion_knn(wf, k, canonical, N, ws.idx, ws.d2, stream))) return rc;   // getWeightsAndUpdateKNN's k-NN (NaN queries are masked below)
-    hipLaunchKernelGGL(df_sv_setup_kernel, dim3((N + 255) / 256), dim3(256), 0, st, canonical, live, N, k, ws.idx, ws.d2, wf->pos_sigma, wf->node_t, M,
-                       ws.w, ws.keys, ws.vals, ws.e0);
+    hipLaunchKernelGGL(normals ? df_sv_setup_kernel<true> : df_sv_setup_kernel<false>, dim3((N + 255) / 256), dim3(256), 0, st, canonical, live, normals,
+                       N, k, ws.idx, ws.d2, wf->pos_sigma, wf->node_t, M, ws.w, ws.keys, ws.vals, ws.e0);
     DF_LAUNCH_CHECK();
     DF_HIP(hipcub::DeviceRadixSort::SortPairs(ws.sort, sort_bytes, ws.keys, ws.skeys, ws.vals, ws.svals, E, 0, 17, st));   // stable
     hipLaunchKernelGGL(df_sv_offsets_kernel, dim3((unsigned)(((size_t)E + 1 + 255) / 256)), dim3(256), 0, st, ws.skeys, E, M, ws.off);
@@ -675,30 +760,44 @@ static int df_sv_prepare(DfWarpField* wf, int k, const float* canonical, const f
     return DF_OK;
 }
 
-// The solve behind the three entry points (arguments checked and normalised by df_sv_check: kg = 0 means no regularisation).
+// The solve behind the four entry points (arguments checked and normalised by df_sv_check: kg = 0 means no regularisation).
 // `rounds` solves, each from the transforms the one before wrote; tukey_c / huber_delta = 0: that penalty is quadratic and its kernels
 // are not launched, so rounds = 1 with both 0 is the plain solve, launch for launch.  `energy` (nullable) holds n_energy floats:
-// 2 = {E_data before, after}, 4 = with {E_reg before, after}, which are 0 without the term.
-static int df_sv_rounds(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int kg, float lambda_reg,
+// 2 = {E_data before, after}, 4 = with {E_reg before, after}, which are 0 without the term.  `normals` (nullable) switches the data term
+// to point-to-plane: the residual a round starts at becomes rho = n . e0 (the energies and the Tukey weights read it), the right-hand
+// side W^T (n rho), W p is projected, and the three CG recurrences become one.
+static int df_sv_rounds(DfWarpField* wf, int k, const float* canonical, const float* live, const float* normals, int N, int iters, float lambda, int kg, float lambda_reg,
                         int rounds, float tukey_c, float huber_delta, float* dq_out, float* energy, int n_energy, float* point_weights,
                         float* edge_weights, dfStream stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    const bool reg = kg > 0, tukey = tukey_c != 0.f, huber = reg && huber_delta != 0.f;
+    const bool reg = kg > 0, tukey = tukey_c != 0.f, huber = reg && huber_delta != 0.f, plane = normals != nullptr;
     const int M = wf->M, E = N * k, Eg = M * kg;
     const float c2 = tukey_c * tukey_c, dd2 = huber_delta * huber_delta;
     SvWorkspace ws;
     int rc;
-    if ((rc = df_sv_workspace(wf, N, k, M, Eg, tukey, huber, st, &ws))) return rc;
-    if ((rc = df_sv_prepare(wf, k, canonical, live, N, kg, ws, stream))) return rc;
+    if ((rc = df_sv_workspace(wf, N, k, M, Eg, plane, tukey, huber, st, &ws))) return rc;
+    if ((rc = df_sv_prepare(wf, k, canonical, live, normals, N, kg, ws, stream))) return rc;
     const float* const sw_use = tukey ? ws.sw_scaled : ws.sw;           // what W^T reads: the scaled copy, or the list as it is
     const float* const alpha_use = huber ? ws.alpha_scaled : wf->graph_alpha.p;   // the handle's cached alpha is only read
     const float* const active = ws.scal + SV_ACTIVE; float* const en = ws.scal + SV_ENERGY;
     const dim3 gN((N + 255) / 256), gM((M + 255) / 256), gE((unsigned)(((size_t)E + 255) / 256)), gG((Eg + 255) / 256), gW(M), one(1);
-    auto step = M <= 2 * SV_BLOCK ? df_sv_step_reg_kernel<2> : M <= 5 * SV_BLOCK ? df_sv_step_reg_kernel<5> : M <= 8 * SV_BLOCK ? df_sv_step_reg_kernel<8> : df_sv_step_kernel;
-    auto w_apply = k == 8 ? df_sv_w_apply_kernel<8> : k == 4 ? df_sv_w_apply_kernel<4> : df_sv_w_apply_kernel<0>;
+    auto step = M <= 2 * SV_BLOCK ? df_sv_step_reg_kernel<2, false> : M <= 5 * SV_BLOCK ? df_sv_step_reg_kernel<5, false> : M <= 8 * SV_BLOCK ? df_sv_step_reg_kernel<8, false> : df_sv_step_kernel<false>;
+    auto w_apply = k == 8 ? df_sv_w_apply_kernel<8, false> : k == 4 ? df_sv_w_apply_kernel<4, false> : df_sv_w_apply_kernel<0, false>;
+    auto wp_apply = w_apply;                                            // W p inside the CG loop: projected on the normals with `plane`
+    auto init = df_sv_init_kernel<false>;
+    if (plane) {
+        step = M <= 2 * SV_BLOCK ? df_sv_step_reg_kernel<2, true> : M <= 5 * SV_BLOCK ? df_sv_step_reg_kernel<5, true> : M <= 8 * SV_BLOCK ? df_sv_step_reg_kernel<8, true> : df_sv_step_kernel<true>;
+        wp_apply = k == 8 ? df_sv_w_apply_kernel<8, true> : k == 4 ? df_sv_w_apply_kernel<4, true> : df_sv_w_apply_kernel<0, true>;
+        init = df_sv_init_kernel<true>;
+    }
+    // the data energy of the residual e (plane: of rho = n . e, which lands in ws.rho)
     auto data_energy = [&](const float* e, float* out) {
-        if (tukey) hipLaunchKernelGGL(df_sv_tukey_energy_kernel, one, dim3(SV_BLOCK), 0, st, e, N, c2, out);
+        if (plane) {
+            if (e != ws.e0) hipLaunchKernelGGL(df_sv_plane_rho_kernel, gN, dim3(256), 0, st, e, normals, ws.keys, N, k, M, ws.rho, (float*)nullptr);
+            hipLaunchKernelGGL(tukey ? df_sv_plane_energy_kernel<true> : df_sv_plane_energy_kernel<false>, one, dim3(SV_BLOCK), 0, st, ws.rho, N, c2, out);
+        }
+        else if (tukey) hipLaunchKernelGGL(df_sv_tukey_energy_kernel, one, dim3(SV_BLOCK), 0, st, e, N, c2, out);
         else hipLaunchKernelGGL(df_sv_energy_kernel, one, dim3(SV_BLOCK), 0, st, e, N, out);
     };
     auto reg_energy = [&](const float* xv, float* out) {                // (the energies weigh an edge with alpha_e itself, not alpha'_e)
@@ -711,14 +810,19 @@ static int df_sv_rounds(DfWarpField* wf, int k, const float* canonical, const fl
             hipLaunchKernelGGL(df_sv_round_e0_kernel, gN, dim3(256), 0, st, canonical, live, N, k, ws.keys, ws.w, wf->node_t.p, M, ws.e0);
             DF_LAUNCH_CHECK();
         }
+        if (plane) {                                                    // rho of e0, and b = n rho in u
+            hipLaunchKernelGGL(df_sv_plane_rho_kernel, gN, dim3(256), 0, st, ws.e0, normals, ws.keys, N, k, M, ws.rho, ws.u);
+            DF_LAUNCH_CHECK();
+        }
         if (tukey) {
-            hipLaunchKernelGGL(df_sv_tukey_kernel, gN, dim3(256), 0, st, ws.e0, N, c2, ws.omega);
+            if (plane) hipLaunchKernelGGL(df_sv_plane_tukey_kernel, gN, dim3(256), 0, st, ws.rho, N, c2, ws.omega);
+            else hipLaunchKernelGGL(df_sv_tukey_kernel, gN, dim3(256), 0, st, ws.e0, N, c2, ws.omega);
             hipLaunchKernelGGL(df_sv_scale_list_kernel, gE, dim3(256), 0, st, ws.spt, ws.sw, ws.omega, E, ws.sw_scaled);
             DF_LAUNCH_CHECK();
         }
         if (energy && first) { data_energy(ws.e0, en); DF_LAUNCH_CHECK(); }
-        // r0 = W^T Omega e0 - lambda_reg * b' ; p0 = r0 ; x0 = 0
-        hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, sw_use, M, ws.e0, 0.f, (const float*)nullptr, ws.r, (const float*)nullptr);
+        // r0 = W^T Omega e0 - lambda_reg * b' (plane: W^T Omega n rho) ; p0 = r0 ; x0 = 0
+        hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, sw_use, M, plane ? ws.u : ws.e0, 0.f, (const float*)nullptr, ws.r, (const float*)nullptr);
         DF_LAUNCH_CHECK();
         if (reg) {
             hipLaunchKernelGGL(df_sv_reg_edge_kernel, gG, dim3(256), 0, st, wf->graph_nbr.p, wf->pos_sigma.p, wf->rot.p, wf->dual.p, Eg, kg, ws.g);
@@ -727,10 +831,10 @@ static int df_sv_rounds(DfWarpField* wf, int k, const float* canonical, const fl
             if (energy && first) reg_energy(nullptr, en + 2);
             DF_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(df_sv_init_kernel, one, dim3(SV_BLOCK), 0, st, ws.r, M, ws.x, ws.p, ws.scal);
+        hipLaunchKernelGGL(init, one, dim3(SV_BLOCK), 0, st, ws.r, M, ws.x, ws.p, ws.scal);
         DF_LAUNCH_CHECK();
         for (int it = 0; it < iters; ++it) {
-            hipLaunchKernelGGL(w_apply, gN, dim3(256), 0, st, ws.w, ws.keys, N, k, M, ws.p, ws.u, active);
+            hipLaunchKernelGGL(wp_apply, gN, dim3(256), 0, st, ws.w, ws.keys, N, k, M, ws.p, ws.u, active, normals);
             hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, sw_use, M, ws.u, lambda, ws.p, ws.q, active);
             if (reg) hipLaunchKernelGGL(df_sv_reg_apply_kernel, gM, dim3(256), 0, st, wf->graph_nbr.p, alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg, ws.p,
                                         lambda_reg, ws.q, active);
@@ -738,7 +842,7 @@ static int df_sv_rounds(DfWarpField* wf, int k, const float* canonical, const fl
             DF_LAUNCH_CHECK();
         }
         if (energy && last) {
-            hipLaunchKernelGGL(w_apply, gN, dim3(256), 0, st, ws.w, ws.keys, N, k, M, ws.x, ws.u, (const float*)nullptr);
+            hipLaunchKernelGGL(w_apply, gN, dim3(256), 0, st, ws.w, ws.keys, N, k, M, ws.x, ws.u, (const float*)nullptr, (const float*)nullptr);
             hipLaunchKernelGGL(df_sv_residual_kernel, dim3((unsigned)((3 * (size_t)N + 255) / 256)), dim3(256), 0, st, ws.e0, ws.u, 3 * N, ws.u);
             data_energy(ws.u, en + 1);
             if (reg) reg_energy(ws.x, en + 3);
@@ -782,14 +886,14 @@ extern "C" int dfusion_warp_solve_data_term(DfWarpField* wf, int k, const float*
 {
     int kg = 0;
     if (df_sv_check(wf, k, canonical, live, N, iters, lambda, &kg, 0.f)) return DF_E_INVALID;
-    return df_sv_rounds(wf, k, canonical, live, N, iters, lambda, kg, 0.f, 1, 0.f, 0.f, dq_out, energy, 2, nullptr, nullptr, stream);
+    return df_sv_rounds(wf, k, canonical, live, nullptr, N, iters, lambda, kg, 0.f, 1, 0.f, 0.f, dq_out, energy, 2, nullptr, nullptr, stream);
 }
 
 extern "C" int dfusion_warp_solve(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int kg,
                                   float lambda_reg, float* dq_out, float* energy, dfStream stream)
 {
     if (df_sv_check(wf, k, canonical, live, N, iters, lambda, &kg, lambda_reg)) return DF_E_INVALID;
-    return df_sv_rounds(wf, k, canonical, live, N, iters, lambda, kg, lambda_reg, 1, 0.f, 0.f, dq_out, energy, 4, nullptr, nullptr, stream);
+    return df_sv_rounds(wf, k, canonical, live, nullptr, N, iters, lambda, kg, lambda_reg, 1, 0.f, 0.f, dq_out, energy, 4, nullptr, nullptr, stream);
 }
 
 extern "C" int dfusion_warp_solve_robust(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int kg,
@@ -798,8 +902,18 @@ extern "C" int dfusion_warp_solve_robust(DfWarpField* wf, int k, const float* ca
 {
     if (df_sv_check(wf, k, canonical, live, N, iters, lambda, &kg, lambda_reg)) return DF_E_INVALID;
     if (rounds < 1 || !(tukey_c >= 0.f) || !(huber_delta >= 0.f) || (edge_weights && kg == 0)) return DF_E_INVALID;
-    return df_sv_rounds(wf, k, canonical, live, N, iters, lambda, kg, lambda_reg, rounds, tukey_c, huber_delta, dq_out, energy, 4, point_weights,
+    return df_sv_rounds(wf, k, canonical, live, nullptr, N, iters, lambda, kg, lambda_reg, rounds, tukey_c, huber_delta, dq_out, energy, 4, point_weights,
                         edge_weights, stream);
+}
+
+extern "C" int dfusion_warp_solve_plane(DfWarpField* wf, int k, const float* canonical, const float* live, const float* normals, int N, int iters,
+                                        float lambda, int kg, float lambda_reg, int rounds, float tukey_c, float huber_delta, float* dq_out,
+                                        float* energy, float* point_weights, float* edge_weights, dfStream stream)
+{
+    if (df_sv_check(wf, k, canonical, live, N, iters, lambda, &kg, lambda_reg) || !normals) return DF_E_INVALID;
+    if (rounds < 1 || !(tukey_c >= 0.f) || !(huber_delta >= 0.f) || (edge_weights && kg == 0)) return DF_E_INVALID;
+    return df_sv_rounds(wf, k, canonical, live, normals, N, iters, lambda, kg, lambda_reg, rounds, tukey_c, huber_delta, dq_out, energy, 4,
+                        point_weights, edge_weights, stream);
 }
 
 extern "C" int dfusion_warp_node_graph(DfWarpField* wf, int kg, int* nbr, float* alpha, dfStream stream)

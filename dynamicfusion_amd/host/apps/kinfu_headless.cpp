@@ -3,7 +3,8 @@
 //   kinfu_headless <cols> <rows> <frames> <dims> <size_m> <in.bin> <out.bin> [warped|host|warped-host]
 //   (warped: per-voxel warped integrate instead of surface_fusion; host: the reference's host-staged data flow; nosolver: skip the
 //   warp data-term solve; depth: the reference's USE_DEPTH build -- depth pyramids and masked-depth ICP; assoc: projective data
-//   association in front of the warp solve, KinFuParams::warp_projective_association -- under trace its counts are printed per frame)
+//   association in front of the warp solve, KinFuParams::warp_projective_association -- under trace its counts are printed per frame;
+//   plane: the warp solve's point-to-plane data term, KinFuParams::warp_point_to_plane)
 // in.bin : intrinsics fx fy cx cy f32[4], then per frame depth u16[rows*cols] (mm).
 // out.bin: per frame { tracked i32 (operator()'s return value), pose f32[12] (R row-major, t) }, then the extracted surface
 //          count u64 and the volume u32[dims^3].
@@ -20,7 +21,7 @@ using namespace kfusion;
 
 int main(int argc, char** argv)
 {
-    if (argc != 8 && argc != 9) { std::fprintf(stderr, "usage: %s cols rows frames dims size in.bin out.bin [warped|host|nosolver|depth|assoc|trace, '-' separated]\n", argv[0]); return 2; }
+    if (argc != 8 && argc != 9) { std::fprintf(stderr, "usage: %s cols rows frames dims size in.bin out.bin [warped|host|nosolver|depth|assoc|plane|trace, '-' separated]\n", argv[0]); return 2; }
     const int cols = std::atoi(argv[1]), rows = std::atoi(argv[2]), frames = std::atoi(argv[3]), dims = std::atoi(argv[4]);
     const float size = (float)std::atof(argv[5]);
     FILE* in = std::fopen(argv[6], "rb");
@@ -40,6 +41,7 @@ int main(int argc, char** argv)
     if (mode.find("nosolver") != std::string::npos) p.warp_solver_iterations = 0;
     p.use_depth_pyramids = mode.find("depth") != std::string::npos;
     p.warp_projective_association = mode.find("assoc") != std::string::npos;
+    p.warp_point_to_plane = mode.find("plane") != std::string::npos;
     KinFu kinfu(p);
 
     FILE* out = std::fopen(argv[7], "wb");

@@ -54,6 +54,8 @@ namespace kfusion
         int warp_robust_rounds = 1;          // robust warp solve (WarpField::setRobust): re-weighted rounds per frame,
         float warp_tukey_c = 0.f;            // the Tukey threshold of the point residuals (metres; 0 = quadratic data term)
         float warp_huber_delta = 0.f;        // and the Huber threshold of the graph edges (0 = quadratic regularisation); default: off
+        bool warp_point_to_plane = false;    // device-resident dynamicfusion(): the warp solve's data term along the warped model normals
+                                             // (WarpField::setPointToPlane) instead of point-to-point; default off = the reference's energy
         bool warp_projective_association = false;   // device-resident dynamicfusion(): pair every warped point with the live sample at the
                                              // pixel it projects to (cuda::associateProjective) instead of by pixel index; default off =
                                              // the reference's pairing
@@ -112,7 +114,7 @@ namespace kfusion
         std::unique_ptr<WarpField> warp_;
         // scratch of the device-resident dynamicfusion()
         cuda::Cloud df_cloud_; cuda::Normals df_normals_;
-        cuda::DeviceArray<float> df_points3_, df_normals3_, df_live3_, df_assoc3_;
+        cuda::DeviceArray<float> df_points3_, df_normals3_, df_live3_, df_assoc3_, df_plane_normals3_;
         cuda::DeviceArray<unsigned long long> df_assoc_counts_; bool df_assoc_valid_ = false;
         cuda::DeviceArray<Point> df_warped4_;
         cuda::Normals df_live_normals_;

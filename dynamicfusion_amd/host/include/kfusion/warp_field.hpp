@@ -74,10 +74,14 @@ namespace kfusion
         void warp(cuda::DeviceArray<float>& points, cuda::DeviceArray<float>& normals, int n) const;
         /// warp_field.cpp:117-163 (Ceres) == WarpFieldOptimiser::optimiseWarpData (Opt): least-squares update of the node
         /// translations from the data term, solved on the GPU (dfusion_warp_solve_data_term); the nodes are updated like
-        /// WarpProblem::updateWarp / copyResultToCPUFromFloat3 do.  The normals are unused, as in the reference's energy.
+        /// WarpProblem::updateWarp / copyResultToCPUFromFloat3 do.  The normals are unused, as in the reference's energy, unless
+        /// setPointToPlane is on, which reads the canonical ones.
         void energy_data(const std::vector<Vec3f>& canonical_vertices, const std::vector<Vec3f>& canonical_normals,
                          const std::vector<Vec3f>& live_vertices, const std::vector<Vec3f>& live_normals);
         void energy_data(const cuda::DeviceArray<float>& canonical_vertices, const cuda::DeviceArray<float>& live_vertices, int n);
+        /// the same with the points' normals (packed float3, in the frame of the points): what setPointToPlane's data term reads
+        void energy_data(const cuda::DeviceArray<float>& canonical_vertices, const cuda::DeviceArray<float>& live_vertices,
+                         const cuda::DeviceArray<float>& canonical_normals, int n);
         /// conjugate-gradient steps of energy_data (Opt's linearIter = 100, kinfu.cpp:118) and its damping
         void setSolverIterations(int iters) { solver_iters_ = iters; }
         int getSolverIterations() const { return solver_iters_; }
@@ -90,6 +94,10 @@ namespace kfusion
         /// (threshold `tukey_c`, metres) on every point and a Huber weight (threshold `huber_delta`) on every graph edge; a threshold of 0
         /// keeps that term quadratic.  Off by default (rounds <= 1 and both thresholds 0): energy_data then takes exactly the path above.
         void setRobust(int rounds, float tukey_c, float huber_delta) { robust_rounds_ = rounds; tukey_c_ = tukey_c; huber_delta_ = huber_delta; }
+        /// DynamicFusion's point-to-plane data term in energy_data (dfusion_warp_solve_plane): every residual is taken along the canonical
+        /// normal given with the point, used as it is, so that a live point that slid along the surface does not move the nodes.  It needs
+        /// an energy_data that is given normals; the overload without them keeps the point-to-point term.  Off by default.
+        void setPointToPlane(bool on) { point_to_plane_ = on; }
         /// E_reg before / after the last regularised energy_data (with setTrackEnergy; 0 while the term is off)
         float lastRegEnergyBefore() const { return last_energy_[2]; }
         float lastRegEnergyAfter() const { return last_energy_[3]; }
@@ -146,6 +154,7 @@ namespace kfusion
         float reg_lambda_ = 0.f;
         int robust_rounds_ = 1;
         float tukey_c_ = 0.f, huber_delta_ = 0.f;
+        bool point_to_plane_ = false;
         float last_energy_[4] = {0.f, 0.f, 0.f, 0.f};
         bool track_energy_ = false;
     };

@@ -556,11 +556,21 @@ int WarpField::extend(const std::vector<Vec3f>& points, float radius, float sigm
 
 void WarpField::energy_data(const cuda::DeviceArray<float>& canonical_vertices, const cuda::DeviceArray<float>& live_vertices, int n)
 {
+    energy_data(canonical_vertices, live_vertices, cuda::DeviceArray<float>(), n);
+}
+
+void WarpField::energy_data(const cuda::DeviceArray<float>& canonical_vertices, const cuda::DeviceArray<float>& live_vertices,
+                            const cuda::DeviceArray<float>& canonical_normals, int n)
+{
     const size_t M = nodes_.size();
     if (!M || n <= 0) return;
     solve_dq_.create(M * 8); solve_energy_.create(4);      // no-ops after the first frame
     const bool reg = reg_neighbours_ != 0 && reg_lambda_ != 0.f;
-    if (robust_rounds_ > 1 || tukey_c_ != 0.f || huber_delta_ != 0.f)   // robust penalties by re-weighted rounds (setRobust)
+    if (point_to_plane_ && canonical_normals.size() >= (size_t)3 * n)   // the data term along the normals (setPointToPlane)
+        KF_DF(dfusion_warp_solve_plane(handle_, k_, canonical_vertices.ptr(), live_vertices.ptr(), canonical_normals.ptr(), n, solver_iters_,
+                                       solver_lambda_, reg ? reg_neighbours_ : 0, reg ? reg_lambda_ : 0.f, robust_rounds_, tukey_c_, huber_delta_,
+                                       solve_dq_.ptr(), track_energy_ ? solve_energy_.ptr() : nullptr, nullptr, nullptr, nullptr));
+    else if (robust_rounds_ > 1 || tukey_c_ != 0.f || huber_delta_ != 0.f)   // robust penalties by re-weighted rounds (setRobust)
         KF_DF(dfusion_warp_solve_robust(handle_, k_, canonical_vertices.ptr(), live_vertices.ptr(), n, solver_iters_, solver_lambda_,
                                         reg ? reg_neighbours_ : 0, reg ? reg_lambda_ : 0.f, robust_rounds_, tukey_c_, huber_delta_, solve_dq_.ptr(),
                                         track_energy_ ? solve_energy_.ptr() : nullptr, nullptr, nullptr, nullptr));
@@ -588,15 +598,16 @@ void WarpField::pullNodes() const
     for (size_t i = 0; i < M; ++i) std::memcpy((void*)nodes_[i].transform.raw(), &dq[8 * i], 32);
 }
 
-void WarpField::energy_data(const std::vector<Vec3f>& canonical_vertices, const std::vector<Vec3f>& /*canonical_normals*/,
+void WarpField::energy_data(const std::vector<Vec3f>& canonical_vertices, const std::vector<Vec3f>& canonical_normals,
                             const std::vector<Vec3f>& live_vertices, const std::vector<Vec3f>& /*live_normals*/)
 {
     const size_t n = std::min(canonical_vertices.size(), live_vertices.size());
     if (!n) return;
-    DeviceArray<float> c, l;
+    DeviceArray<float> c, l, nrm;
     c.upload(canonical_vertices[0].val, n * 3);
     l.upload(live_vertices[0].val, n * 3);
-    energy_data(c, l, (int)n);
+    if (point_to_plane_ && canonical_normals.size() >= n) nrm.upload(canonical_normals[0].val, n * 3);
+    energy_data(c, l, nrm, (int)n);
     KF_HIP(hipDeviceSynchronize());                       // the solve reads c and l, which are freed on return (hipFree does not wait for it)
 }
 
@@ -1149,7 +1160,18 @@ void KinFu::dynamicfusion(cuda::Depth& depth, cuda::Cloud live_frame, cuda::Norm
             warp_->setSolverIterations(params_.warp_solver_iterations);
             warp_->setRegularisation(params_.warp_reg_neighbours, params_.warp_reg_lambda);
             warp_->setRobust(params_.warp_robust_rounds, params_.warp_tukey_c, params_.warp_huber_delta);
-            warp_->energy_data(df_points3_, df_live3_, (int)n);
+            warp_->setPointToPlane(params_.warp_point_to_plane);
+            if (params_.warp_point_to_plane) {
+                // df_normals3_ holds the ray-cast's normals re-strided as they came (the camera's frame) and warped, while df_points3_ and
+                // df_live3_ are inverse_pose * the camera's frame: the solve gets a copy in the points' frame, rotation only (df_normals3_
+                // itself goes on into the second warp as it is)
+                if (df_plane_normals3_.size() < 3 * n) df_plane_normals3_.create(3 * n);
+                float rot12[12]; std::memcpy(rot12, inv12, sizeof(rot12)); rot12[9] = rot12[10] = rot12[11] = 0.f;
+                KF_DF(dfusion_transform_points(df_normals3_.ptr(), 3 * n * sizeof(float), 3, df_plane_normals3_.ptr(), 3 * n * sizeof(float), 3, (int)n, 1,
+                                               rot12, nullptr));
+                warp_->energy_data(df_points3_, df_live3_, df_plane_normals3_, (int)n);
+            } else
+                warp_->energy_data(df_points3_, df_live3_, (int)n);
         }
         warp_->warp(df_points3_, df_normals3_, (int)n);                      // :391
         if (params_.warped_fusion) {

@@ -216,6 +216,33 @@ class WarpField:
             return dq, en, pw, ew
         return dq, en
 
+    def solve_plane(self, canonical_dev, live_dev, normals_dev, iters=100, lam=0.0, reg_neighbours=0, reg_lambda=0.0, rounds=1, tukey_c=0.0,
+                    huber_delta=0.0, k=None, return_weights=False):
+        """solve_robust with the point-to-plane data term (include/dfusion.h dfusion_warp_solve_plane): the residual of every point is
+        taken along its normal (`normals_dev`, device [N,3], in the frame of the points, used as given), so that a live point that slid
+        along the surface -- what projective association leaves -- does not pull on the nodes.  A point with a NaN or infinite normal
+        is skipped.  Returns what solve_robust returns; the data energies are those of the projected residual."""
+        k = self.k if k is None else k
+        n = int(canonical_dev.shape[0])
+        if int(normals_dev.numel()) != 3 * n:
+            raise ValueError("one normal per point expected (%d points, normals of shape %s)" % (n, tuple(normals_dev.shape)))
+        kg = int(reg_neighbours)
+        dq = torch.empty((self.M, 8), dtype=torch.float32, device=self.device)
+        en = torch.zeros(4, dtype=torch.float32, device=self.device)
+        pw = ew = None
+        if return_weights:
+            pw = torch.empty(n, dtype=torch.float32, device=self.device)
+            if kg > 0 and float(reg_lambda) != 0.0:
+                ew = torch.empty((self.M, kg), dtype=torch.float32, device=self.device)
+        capi.check(capi.lib().dfusion_warp_solve_plane(self.handle, k, _flat(canonical_dev), _flat(live_dev), _flat(normals_dev), n, int(iters),
+                                                       float(lam), kg, float(reg_lambda), int(rounds), float(tukey_c), float(huber_delta),
+                                                       _ptr(dq), _ptr(en), _ptr(pw) if pw is not None else None,
+                                                       _ptr(ew) if ew is not None else None, _stream()), "dfusion_warp_solve_plane")
+        self._dq = dq
+        if return_weights:
+            return dq, en, pw, ew
+        return dq, en
+
     def node_graph(self, kg):
         """The graph solve() regularises over: (nbr int32 [M, kg], alpha float32 [M, kg]) device tensors -- node i's kg nearest other
         nodes and the edge weights max(dg_w_i, dg_w_j)."""

@@ -438,6 +438,21 @@ int dfusion_warp_solve(DfWarpField *wf, int k, const float *canonical_dev, const
 int dfusion_warp_solve_robust(DfWarpField *wf, int k, const float *canonical_dev, const float *live_dev, int N, int iters, float lambda,
                               int kg, float lambda_reg, int rounds, float tukey_c, float huber_delta, float *dq_out_dev,
                               float *energy_dev, float *point_weights_dev, float *edge_weights_dev, dfStream stream);
+/* dfusion_warp_solve_robust with the paper's point-to-plane data term (DynamicFusion section 3.3, eq. 7: the residual along the predicted
+ * model normal) -- an addition to ABI 7.  normals_dev [N*3] packed, in the frame of canonical_dev and live_dev, used as given (never
+ * normalised).  With e0 as above and n_v the point's normal:
+ *     rho_v = (nx ex + ny ey) + nz ez;     E_data = sum_v rho_v^2;     omega_v from s_v = rho_v^2
+ *     `iters` conjugate-gradient steps on (W^T N Omega N^T W + lambda I + lambda_reg L') delta = W^T Omega (n rho) - lambda_reg b',
+ * N N^T the per-point projection u -> n (n . u).  The matrix differs between x, y and z, so the three components are ONE conjugate-
+ * gradient recurrence: every dot product is the three per-component sums combined as (s0 + s1) + s2.  A point is also skipped when a
+ * component of its normal is NaN or infinite; a zero normal leaves a valid point that contributes nothing.  Everything else -- the
+ * rounds, Huber, the energies' layout (E_data of rho), point_weights_dev, edge_weights_dev -- is dfusion_warp_solve_robust's; tangential
+ * slip of the live points along the surface, which projective association leaves behind, does not move the nodes.
+ * Restated in tests/solver_plane_ref.py.
+ * DF_E_INVALID: what dfusion_warp_solve_robust refuses, normals_dev == NULL.                                                              */
+int dfusion_warp_solve_plane(DfWarpField *wf, int k, const float *canonical_dev, const float *live_dev, const float *normals_dev, int N,
+                             int iters, float lambda, int kg, float lambda_reg, int rounds, float tukey_c, float huber_delta,
+                             float *dq_out_dev, float *energy_dev, float *point_weights_dev, float *edge_weights_dev, dfStream stream);
 /* The node graph dfusion_warp_solve uses for `kg` (1..7, M >= kg + 1; built now if the handle does not hold it):
  * nbr_dev[M*kg] int32 the head node of every edge, alpha_dev[M*kg] (nullable) the edge weights.                                      */
 int dfusion_warp_node_graph(DfWarpField *wf, int kg, int *nbr_dev, float *alpha_dev, dfStream stream);
