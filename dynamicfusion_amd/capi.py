@@ -39,6 +39,7 @@ DF_WARP_BLOCK_MODEL_NOW = 256
 DF_WARP_NO_PREFETCH = 512
 DF_WARP_STEADY_PREFETCH = 1024
 DF_WARP_NO_CODES = 2048
+DF_WARP_NO_SUB_VERDICT = 4096
 DF_RIGID_NO_DEPTH_CULL = 1
 DF_RIGID_NO_SHORT_FORMS = 2
 DF_RIGID_KEEP_ALL = 4

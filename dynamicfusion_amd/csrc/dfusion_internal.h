@@ -115,7 +115,7 @@ struct __attribute__((visibility("hidden"))) DfWarpField {     // (opaque in dfu
     unsigned long long ring_seq[2] = {};             // the sweep whose completion ev_sweep_done[i] stands for (0: none)
     unsigned long long node_reader[2] = {}; int nphase = 0;  // [nphase] = the current node set's last reader, [nphase ^ 1] = the alternate's
     unsigned long long plan_reader[2] = {};
-    DfDevBuf<unsigned long long> plan_mask2[2]; DfDevBuf<unsigned int> plan_list2[2]; int pphase = 0; unsigned hphase = 0;
+    DfDevBuf<unsigned long long> plan_mask2[2]; DfDevBuf<unsigned int> plan_list2[2]; int pphase = 0; unsigned hphase = 0;   // (masks: two words per item, a bit per half layer)
     DfDevBuf<unsigned long long> plan_code2[2];      // per strip item: which of its (patch, layer) cells read 4-bit codes
     DfDevBuf<uint16_t> pyr_mem;             // max-pyramid of the frame's dists image (warped sweep's depth cull), entries
     // scratch of the warp solver (dfusion_solver.hip: one carve-up for its three entry points; grown on demand)
@@ -151,6 +151,12 @@ struct __attribute__((visibility("hidden"))) DfWarpField {     // (opaque in dfu
     //   bm_coded [block] 1 = every sub-block's union fits 16 entries and the codes are written
     //   code_tab one u32 per voxel, tile-major like the tables but PATCH-major inside a tile plane
     DfDevBuf<uint32_t> code_tab; size_t code_cap = 0; DfDevBuf<uint32_t> bm_ids; DfDevBuf<uint8_t> bm_coded;
+    // sub-block blend models (k = 8; reserved and voided with the codes: the same pass writes them) and this frame's sub-verdicts:
+    //   bm_sub_lam, bm_sub_w [block][DF_BM_NU][sub] the intervals of a sub-block's union entries over its 64 voxels (sub = 4 h + q)
+    //   bm_sub_cnt [block * 8 + sub] entries | reference entry << 8 ; bm_sub_ok [block] 1 = the block has them
+    //   blk_sub [block] bit 4 h + q = the sub-block may update this frame (0xff where not judged) ; sub_list the blocks to judge ;
+    //   blk_alive_prev the verdicts of the pass before (the two arrays are swapped by every pass)
+    DfDevBuf<uint32_t> bm_sub_lam, bm_sub_w; DfDevBuf<uint16_t> bm_sub_cnt; DfDevBuf<uint8_t> bm_sub_ok, blk_sub, blk_alive_prev; DfDevBuf<uint32_t> sub_list;
     bool tab_complete = false;   // every block's tables are built
     int tab_sweeps = 0;          // sweeps over the current tables so far (the models are made from the second one on)
     unsigned long long* dbg_swept = nullptr;   // dfusion_warp_debug_counters: nullable device counter (the caller's) the sweeps through this handle add to

@@ -16,6 +16,7 @@
 #include "dfusion_warp_sweep.h"
 #include "dfusion_warp_blocks.h"
 #include "dfusion_warp_pipe.h"
+#include <algorithm>
 #include <atomic>
 #include <stdlib.h>
 #include <stdio.h>
@@ -118,6 +119,9 @@ DfWarpedArgs df_table_args(const DfWarpField* wf)
     a.bz0 = wf->tab_z0 / DF_BRICK;
     a.bm_nbx = ntx * (DF_TAB_TX / 8); a.bm_nby = nty * (DF_TAB_TY / 8);
     a.code_tab = wf->code_tab; a.bm_ids = wf->bm_ids; a.bm_coded = wf->bm_coded;
+    if (wf->bm_sub_lam && wf->bm_sub_w && wf->bm_sub_cnt && wf->bm_sub_ok) {
+        a.bm_sub_lam = wf->bm_sub_lam; a.bm_sub_w = wf->bm_sub_w; a.bm_sub_cnt = wf->bm_sub_cnt; a.bm_sub_ok = wf->bm_sub_ok;
+    }
     a.blk_tie = wf->blk_tie;
     return a;
 }
@@ -203,12 +207,21 @@ static int df_block_verdicts(DfWarpField* wf, DfWarpedArgs& a, int k, unsigned f
         wf->bm_cap = nblk;
     }
     // 4-bit neighbour codes + the sub-blocks' union lists (the sweep reads them at k = 8 only: no 4 bytes a voxel for the others)
-    if (want_models && k == 8 && (nblk * 512 > wf->code_cap || !wf->bm_ids || !wf->code_tab || !wf->bm_coded)) {
+    // ... and the sub-blocks' own blend models, 2 x 4 bytes per union entry: what the sub-verdicts judge half layers by
+    if (want_models && k == 8 && (nblk * 512 > wf->code_cap || !wf->bm_ids || !wf->code_tab || !wf->bm_coded || !wf->bm_sub_lam || !wf->bm_sub_w ||
+                                  !wf->bm_sub_cnt || !wf->bm_sub_ok || !wf->blk_sub || !wf->sub_list)) {
         wf->code_cap = 0;
         { int rc = wf->bm_ids.reserve(nblk * 64); if (rc) return rc; }
         { int rc = wf->code_tab.reserve(nblk * 512); if (rc) return rc; }
         { int rc = wf->bm_coded.reserve(nblk); if (rc) return rc; }
         DF_HIP(hipMemsetAsync(wf->bm_coded, 0, nblk, st));
+        { int rc = wf->bm_sub_lam.reserve(nblk * 8 * DF_BM_NU); if (rc) return rc; }
+        { int rc = wf->bm_sub_w.reserve(nblk * 8 * DF_BM_NU); if (rc) return rc; }
+        { int rc = wf->bm_sub_cnt.reserve(nblk * 8); if (rc) return rc; }
+        { int rc = wf->bm_sub_ok.reserve(nblk); if (rc) return rc; }
+        { int rc = wf->blk_sub.reserve(nblk); if (rc) return rc; }
+        { int rc = wf->sub_list.reserve(nblk); if (rc) return rc; }
+        DF_HIP(hipMemsetAsync(wf->bm_sub_ok, 0, nblk, st));
         wf->code_cap = nblk * 512;
     }
     // look-ahead: with on-demand tables or models still to make, blocks NEAR the alive set get theirs on the side
@@ -235,12 +248,19 @@ static int df_block_verdicts(DfWarpField* wf, DfWarpedArgs& a, int k, unsigned f
     uint32_t* cnt = wf->blk_cnt + 8 * wf->blk_phase;
     uint32_t* cnt_next = wf->blk_cnt + 8 * (wf->blk_phase ^ 1);
     uint32_t* list_urgent = wf->blk_work, *list_ahead = wf->blk_work + wf->blk_cap, *list_model = wf->blk_work + 2 * wf->blk_cap;
+    // sub-verdicts (k = 8): the kept blocks that have sub-block models and touch the dead set are listed and judged per 4 x 4 x 4 sub-block
+    // right after the pass.  The verdict bytes alternate between two arrays: the pass reads its neighbours' verdicts of the frame before.
+    std::swap(wf->blk_alive, wf->blk_alive_prev);
+    const bool codes_exist = k == 8 && wf->bm_cnt && wf->code_tab && wf->bm_ids && wf->bm_coded && wf->code_cap >= nblk * 512;
+    const bool sub_verdicts = use_models && wf->bm_cap >= nblk && codes_exist && !(flags & DF_WARP_NO_SUB_VERDICT) && wf->bm_sub_lam && wf->bm_sub_w &&
+                              wf->bm_sub_cnt && wf->bm_sub_ok && wf->blk_sub && wf->sub_list && wf->blk_alive_prev;
+    if (sub_verdicts) { a.bm_ids = wf->bm_ids; a.bm_sub_lam = wf->bm_sub_lam; a.bm_sub_w = wf->bm_sub_w; a.bm_sub_cnt = wf->bm_sub_cnt; a.bm_sub_ok = wf->bm_sub_ok; }
     hipLaunchKernelGGL(df_block_verdict_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, a, wf->rot, wf->node_t, nbx, nby, nbz,
                        wf->blk_state, wf->blk_wmax, wf->brick_thr + wf->off_cap, wf->bx, wf->by, a.tile_wmax != nullptr ? 1 : 0,
-                       (use_models && wf->bm_cap >= nblk ? 1 : 0) | (k == 8 && wf->bm_cnt && wf->code_tab && wf->bm_ids && wf->bm_coded && wf->code_cap >= nblk * 512 ? 2 : 0),     // (bit 1: the blocks' codes exist)
+                       (use_models && wf->bm_cap >= nblk ? 1 : 0) | (codes_exist ? 2 : 0) | (sub_verdicts ? 4 : 0),     // (bit 1: the blocks' codes exist; bit 2: sub-verdicts follow)
                        want_models_now,
                        wf->tab_complete ? 0 : 1, wf->bm_idx, wf->bm_lam, wf->bm_w, wf->bm_cnt, wf->bm_coded, wf->blk_alive, list_urgent, list_ahead, list_model,
-                       cnt, cnt_next);
+                       cnt, cnt_next, sub_verdicts ? (uint8_t*)wf->blk_sub : nullptr, wf->sub_list, wf->blk_alive_prev);
     a.blk_cnt = cnt; a.host_report = (uint32_t*)wf->host_report; a.sweep_no = (uint32_t)wf->tab_sweeps;
     DF_LAUNCH_CHECK();
 #ifdef DF_TRACE_VERDICT
@@ -281,6 +301,14 @@ static int df_block_verdicts(DfWarpField* wf, DfWarpedArgs& a, int k, unsigned f
         if (hipEventRecord(wf->ev_join, wf->side) == hipSuccess) wf->side_pending = true;      // joined by the next call that touches the tables
         else { (void)hipGetLastError(); df_side_drain(wf); if (rc_side == DF_OK) rc_side = (int)hipErrorUnknown; }
         if (rc_side != DF_OK) return rc_side;
+    }
+    if (sub_verdicts) {
+        // (it reads models of blocks whose state was 2 when the verdict pass ran -- none that this frame's side-stream model builds write.
+        // The list's length stays on the device: at most 1024 workgroups stride over it, those past its end return at once.)
+        const unsigned sub_grid = (unsigned)std::min<size_t>((nblk * 8 + 255) / 256, 1024);
+        hipLaunchKernelGGL(df_sub_verdict_kernel, dim3(sub_grid), dim3(256), 0, st, a, wf->rot, wf->node_t, nbx, nby, nbz, wf->sub_list, cnt + 5, wf->blk_sub);
+        DF_LAUNCH_CHECK();
+        a.blk_sub = wf->blk_sub;
     }
     if (!wf->tab_complete) { int rc = df_build_listed(wf, cnt, st, 0); if (rc) return rc; }      // urgent: before this frame's sweep
     if (want_models_now && !ahead) { int rc = launch_models(st); if (rc) return rc; }
@@ -504,7 +532,7 @@ static int df_integrate_warped_impl(const uint16_t* dists, size_t pitch, int col
                 { int rc = df_wait_all_sweeps_host(wf); if (rc) return rc; }
                 wf->plan_cap = 0;
                 for (int i = 0; i < 2; ++i) {
-                    { int rc = wf->plan_mask2[i].reserve(n_items); if (rc) return rc; }
+                    { int rc = wf->plan_mask2[i].reserve((size_t)n_items * 2); if (rc) return rc; }
                     { int rc = wf->plan_list2[i].reserve((size_t)n_items * DF_PLAN_BINS); if (rc) return rc; }      // the bins
                     { int rc = wf->plan_code2[i].reserve(n_items); if (rc) return rc; }
                 }
@@ -623,6 +651,7 @@ int df_build_voxel_table(DfWarpField* wf, const DfVolume& v, const DfSlab& s, co
         { int rc = wf->blk_tie.reserve(nblk); if (rc) return rc; }
         { int rc = wf->blk_wmax.reserve(nblk); if (rc) return rc; }
         { int rc = wf->blk_alive.reserve(nblk); if (rc) return rc; }
+        { int rc = wf->blk_alive_prev.reserve(nblk); if (rc) return rc; }
         { int rc = wf->blk_work.reserve(3 * nblk); if (rc) return rc; }
         wf->blk_cap = nblk;
     }
@@ -631,6 +660,8 @@ int df_build_voxel_table(DfWarpField* wf, const DfVolume& v, const DfSlab& s, co
     DF_HIP(hipMemsetAsync(wf->blk_state, on_demand ? 0 : 1, nblk, st));
     DF_HIP(hipMemsetAsync(wf->blk_tie, 0, nblk, st));
     DF_HIP(hipMemsetAsync(wf->blk_wmax, 0, nblk * sizeof(float), st));
+    DF_HIP(hipMemsetAsync(wf->blk_alive, 1, nblk, st));                   // (no verdicts yet: "every neighbour kept" for the first pass's sub-verdict list)
+    DF_HIP(hipMemsetAsync(wf->blk_alive_prev, 1, nblk, st));
     wf->blk_phase = 0;
     wf->tab_z0 = tz0; wf->tab_zn = tzn; wf->tab_k = k; wf->tab_valid = true; wf->w_tab_valid = weights;
     wf->tab_complete = !on_demand; wf->tab_sweeps = 0; wf->alive_valid = false;

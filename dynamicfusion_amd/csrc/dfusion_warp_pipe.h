@@ -2,6 +2,7 @@
 // dfusion_warp.hip only.
 #pragma once
 #include "dfusion_warp_sweep.h"
+#include "dfusion_plan_halves.h"
 
 // ---- software-pipelined form of the kernel above (the default).  PMC on the batched kernel: waves spend ~45 % of their
 // cycles parked on the table loads and raising occupancy is not possible (~100 VGPRs),
@@ -194,7 +195,9 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t df_plane_rsrc(uint32_t* plane_
 
 // The launch plan of the pipelined sweep.  One wave per strip item: lane = (patch p = lane / 16, layer l = lane % 16) judges the
 // 8 x 8 x 8 voxels of its patch and layer (the verdict costs ~200 instructions; in the sweep itself it held a workgroup's LDS while
-// it ran); the ballot is the item's mask, its population count w the item's work.  Alive items go into bin w (bins[w * n_items ...],
+// it ran), per HALF layer of 4 planes: a half is swept when the block is alive, the sub-verdicts (a.blk_sub, where there are any) keep one
+// of the half's four sub-blocks, and the slab owns one of its planes.  The ballots of the two halves, interleaved per patch
+// (dfusion_plan_halves.h), are the item's mask; its work w is half the number of set bits, rounded up.  Alive items go into bin w (bins[w * n_items ...],
 // cnt[w] entries; the order inside a bin is whatever the atomics make it -- items are independent, the result does not depend on
 // it): the sweep takes the bins from w = 64 down, i.e. the items most work first, without a sorting pass.  `cnt_next` is the counter
 // set of the NEXT launch (the two sets alternate), zeroed here: nothing reads it any more once this kernel runs.
@@ -214,7 +217,8 @@ __global__ __launch_bounds__(DF_PLAN_WG) void df_sweep_plan_kernel(const DfWarpe
     __syncthreads();
     const unsigned item = blockIdx.x * (DF_PLAN_WG / 64) + (threadIdx.x >> 6);
     const int ln = threadIdx.x & 63, p = ln >> 4, l = ln & 15;
-    unsigned long long m = 0;
+    unsigned long long m = 0, hw01 = 0, hw23 = 0;
+    unsigned n_half = 0;
     if (item < n_items) {                                                  // wave-uniform
         const unsigned half = item & 1u, tcol = item >> 1;
         const int tx = (int)(tcol % (unsigned)tiles_x), ty = (int)((tcol / (unsigned)tiles_x) % (unsigned)tiles_y);
@@ -224,32 +228,48 @@ __global__ __launch_bounds__(DF_PLAN_WG) void df_sweep_plan_kernel(const DfWarpe
         const int x0 = tx * DF_ROW_TX + p * 8, y0 = ty * DF_LDS_TY + (int)half * 8;                  // first column of the patch
         bool keep = l < a.zt && max((lt0 + l) * DF_ROW_TZ, a.z_own0) < min((lt0 + l + 1) * DF_ROW_TZ, own1) && x0 < a.X && y0 < a.Y;
         // the verdict pass has judged the patch's 8 x 8 x 8 voxels of the layer (df_block_verdict_kernel: zero-weight, ball, blend-model box)
-        unsigned verdict = 1u;
+        unsigned verdict = 1u, sub = 0xffu;
         if (keep && a.blk_alive) {
-            verdict = a.blk_alive[((size_t)(lt0 + l - a.tab_z0 / DF_ROW_TZ) * a.bm_nby + (unsigned)(y0 >> 3)) * a.bm_nbx + (unsigned)(x0 >> 3)];
+            const size_t blk = ((size_t)(lt0 + l - a.tab_z0 / DF_ROW_TZ) * a.bm_nby + (unsigned)(y0 >> 3)) * a.bm_nbx + (unsigned)(x0 >> 3);
+            verdict = a.blk_alive[blk];
             keep = verdict != 0u;
+            if (keep && a.blk_sub) {
+                sub = a.blk_sub[blk];                                      // (bit 4 h + q: df_sub_verdict_kernel)
+                // (no sub-block kept: the block leaves the frame's verdicts too)
+                if (sub == 0u) const_cast<uint8_t*>(a.blk_alive)[blk] = 0;
+            }
         }
+        // the planes of either half that this launch sweeps (never one the slab does not own)
+        const int np0 = keep && (sub & 0x0fu) ? df_half_planes((lt0 + l) * DF_ROW_TZ, 0, a.z_own0, own1) : 0;
+        const int np1 = keep && (sub & 0xf0u) ? df_half_planes((lt0 + l) * DF_ROW_TZ, 1, a.z_own0, own1) : 0;
+        keep = (np0 | np1) != 0;
         m = __builtin_amdgcn_ballot_w64(keep);
+        const unsigned long long m0 = __builtin_amdgcn_ballot_w64(np0 != 0), m1 = __builtin_amdgcn_ballot_w64(np1 != 0);
+        n_half = (unsigned)__popcll(m0) + (unsigned)__popcll(m1);
+        hw01 = (unsigned long long)df_halves_word((unsigned)m0 & 0xffffu, (unsigned)m1 & 0xffffu) |
+               ((unsigned long long)df_halves_word((unsigned)(m0 >> 16) & 0xffffu, (unsigned)(m1 >> 16) & 0xffffu) << 32);
+        hw23 = (unsigned long long)df_halves_word((unsigned)(m0 >> 32) & 0xffffu, (unsigned)(m1 >> 32) & 0xffffu) |
+               ((unsigned long long)df_halves_word((unsigned)(m0 >> 48) & 0xffffu, (unsigned)(m1 >> 48) & 0xffffu) << 32);
         if (code_out) {                                                    // (wave-uniform) which alive cells' blocks have 4-bit neighbour codes
             const bool coded = keep && a.blk_alive && (verdict & 2u) != 0u;                          // (bit 1 of the verdict byte: see df_block_verdict_kernel)
             const unsigned long long cm = __builtin_amdgcn_ballot_w64(coded);
             if (ln == 0 && m) code_out[item] = cm;
         }
         if (a.n_swept) {                                                   // (measurement hook: what the sweep will put through the warp)
-            unsigned v = keep ? (unsigned)(64 * (min((lt0 + l + 1) * DF_ROW_TZ, own1) - max((lt0 + l) * DF_ROW_TZ, a.z_own0))) : 0u;
+            unsigned v = (unsigned)(64 * (np0 + np1));
 #pragma unroll
             for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
             if (ln == 0 && v) atomicAdd(a.n_swept, (unsigned long long)v);
         }
     }
-    const unsigned w = (unsigned)__popcll(m);
+    const unsigned w = (n_half + 1u) >> 1;                                 // 1 .. 64 for 1 .. 128 half layers: the 65 bins
     unsigned slot = 0;
     if (ln == 0 && m) slot = atomicAdd(&s_cnt[w], 1u);
     __syncthreads();
     if (threadIdx.x < DF_PLAN_BINS && s_cnt[threadIdx.x]) s_base[threadIdx.x] = atomicAdd(&cnt[threadIdx.x], s_cnt[threadIdx.x]);
     __syncthreads();
     if (ln == 0 && m) {
-        mask_out[item] = m;
+        mask_out[2 * (size_t)item] = hw01; mask_out[2 * (size_t)item + 1] = hw23;
         bins[(size_t)w * n_items + s_base[w] + slot] = item;
     }
 }
@@ -311,22 +331,26 @@ __global__ __launch_bounds__(WGT, LDSN ? (WGT == 512 ? 4 : 1) : (K == 8 ? 6 : 5)
     // the workgroup's patches form ONE sequence (item, patch, layer, half-layer of 4 planes) and wave w takes the w-th of WGT / 64
     // equal shares of it: a run of layers of one patch, or the tail of one patch and the head of the next -- SEGMENTS, each walked by
     // the pipelined loop below as before.  Which voxel is updated by which wave changes; what is computed for it does not.
-    unsigned items_s[SPW]; unsigned long long masks_s[SPW];
+    // (round 7: the cells are the plan's HALF layers -- where the sub-verdicts found a half's four sub-blocks dead, the sequence skips it)
+    unsigned items_s[SPW]; unsigned long long masks_s[2 * SPW];             // (per item: patches 0-1, patches 2-3; dfusion_plan_halves.h)
     unsigned long long cmask_s[SPW];
     unsigned total2 = 0;
 #pragma unroll
     for (unsigned s_ = 0; s_ < SPW; ++s_) {
         const unsigned sidx = group * SPW + s_;
-        items_s[s_] = 0u; masks_s[s_] = 0ull;
+        items_s[s_] = 0u; masks_s[2 * s_] = masks_s[2 * s_ + 1] = 0ull;
         cmask_s[s_] = 0ull;
         if (sidx < n_alive) {
             const int j = __ffsll((unsigned long long)__builtin_amdgcn_ballot_w64(sidx < bin_end)) - 1;      // its bin: the first running total above sidx
             const unsigned r = sidx - ((unsigned)__builtin_amdgcn_readlane((int)bin_end, j) - (unsigned)__builtin_amdgcn_readlane((int)bin_cnt, j));
             items_s[s_] = (unsigned)__builtin_amdgcn_readfirstlane((int)a.plan_bins[(size_t)(DF_PLAN_BINS - 1 - j) * a.plan_items + r]);
-            const unsigned long long m = a.plan_mask[items_s[s_]];
-            masks_s[s_] = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(m >> 32)) << 32) |
-                          (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)m);
-            total2 += 2u * (unsigned)__popcll(masks_s[s_]);
+#pragma unroll
+            for (unsigned w_ = 0; w_ < 2u; ++w_) {
+                const unsigned long long m = a.plan_mask[2 * (size_t)items_s[s_] + w_];
+                masks_s[2 * s_ + w_] = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(m >> 32)) << 32) |
+                                       (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)m);
+                total2 += (unsigned)__popcll(masks_s[2 * s_ + w_]);
+            }
             if (CODES && a.plan_code) {
                 const unsigned long long cm = a.plan_code[items_s[s_]];
                 cmask_s[s_] = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(cm >> 32)) << 32) |
@@ -340,27 +364,22 @@ __global__ __launch_bounds__(WGT, LDSN ? (WGT == 512 ? 4 : 1) : (K == 8 ? 6 : 5)
     for (unsigned q = 0; q < SPW * 4u; ++q) {
     unsigned item = items_s[0]; unsigned long long m_item = masks_s[0];
 #pragma unroll
-    for (unsigned s_ = 1; s_ < SPW; ++s_) if ((q >> 2) == s_) { item = items_s[s_]; m_item = masks_s[s_]; }
-    const unsigned a16 = (unsigned)(m_item >> (16u * (q & 3u))) & 0xffffu;
+    for (unsigned s_ = 1; s_ < SPW; ++s_) if ((q >> 2) == s_) item = items_s[s_];
+#pragma unroll
+    for (unsigned w_ = 1; w_ < 2 * SPW; ++w_) if ((q >> 1) == w_) m_item = masks_s[w_];
+    const unsigned h32 = (unsigned)(m_item >> (32u * (q & 1u)));           // the patch's half layers, bit 2 l + h
     unsigned long long c_item = cmask_s[0];
 #pragma unroll
     for (unsigned s_ = 1; s_ < SPW; ++s_) if ((q >> 2) == s_) c_item = cmask_s[s_];
     const unsigned cbits = CODES ? (unsigned)(c_item >> (16u * (q & 3u))) & 0xffffu : 0u;      // layers of this patch whose block has 4-bit codes
-    const unsigned n2 = 2u * (unsigned)__popc(a16);
+    const unsigned n2 = (unsigned)__popc(h32);
     const unsigned seg_lo = max(c0, pre), seg_hi = min(c1, pre + n2);
     const unsigned pre0 = pre;
     pre += n2;
     if (seg_lo >= seg_hi) continue;                                        // none of this patch's cells are this wave's
-    const unsigned lo = seg_lo - pre0, hi = seg_hi - pre0;                 // half-layer cells [lo, hi) of the patch's 2 popc(a16)
-    unsigned alive = a16;
-    for (unsigned i = 0; i < (lo >> 1); ++i) alive &= alive - 1u;          // drop the layers before the segment ...
-    {
-        unsigned keep = ((hi - 1u) >> 1) - (lo >> 1) + 1u, rest = alive, seg = 0u;
-        for (unsigned i = 0; i < keep; ++i) { const unsigned low = rest & (0u - rest); seg |= low; rest ^= low; }
-        alive = seg;                                                       // ... and those after it
-    }
-    int first_l = __ffs(alive) - 1, last_l = 31 - __clz(alive);
-    int z_first_off = (int)(lo & 1u) * (DF_ROW_TZ / 2), z_last_off = ((int)((hi - 1u) & 1u) + 1) * (DF_ROW_TZ / 2);
+    const unsigned lo = seg_lo - pre0, hi = seg_hi - pre0;                 // half-layer cells [lo, hi) of the patch's popc(h32)
+    const unsigned seg = df_halves_segment(h32, lo, hi);                   // ... as bits: what this segment sweeps
+    const unsigned alive = df_halves_layers(seg);                          // its layers
     const int wave_patch = (int)(q & 3u);
     // item -> tile column, half, layer block; the wave's 8 x 8 patch is number wv of the 32 x 16 footprint (4 across, 2 down): a compact
     // footprint, so that the voxels of a wave fall on the same side of the frustum and of the observed surface more often
@@ -374,11 +393,11 @@ __global__ __launch_bounds__(WGT, LDSN ? (WGT == 512 ? 4 : 1) : (K == 8 ? 6 : 5)
     const int xc = min(x, a.X - 1), yc = min(y, a.Y - 1);                 // clamped: out-of-volume lanes read valid entries, write nothing
     const float fxv = (float)x * a.vsx, fyv = (float)y * a.vsy;
     const int lt0 = a.bz0 + (int)(tcol / ((unsigned)tiles_x * (unsigned)a.plan_tiles_y)) * a.zt;     // first tile layer of the item
-    // the segment's first / last layer start / end at a half-layer boundary; a layer the slab's own range cuts down to nothing is dropped
-    auto layer_zb = [&](int l) { const int z = max((lt0 + l) * DF_ROW_TZ, a.z_own0); return l == first_l ? max(z, (lt0 + l) * DF_ROW_TZ + z_first_off) : z; };
-    auto layer_ze = [&](int l) { const int z = min((lt0 + l + 1) * DF_ROW_TZ, own1); return l == last_l ? min(z, (lt0 + l) * DF_ROW_TZ + z_last_off) : z; };
-    if (alive && layer_zb(first_l) >= layer_ze(first_l)) { alive &= alive - 1u; first_l = alive ? __ffs(alive) - 1 : 0; z_first_off = 0; }   // (the next layer, if any, is taken whole)
-    if (alive && layer_zb(last_l) >= layer_ze(last_l)) { alive &= ~(1u << last_l); last_l = alive ? 31 - __clz(alive) : 0; z_last_off = DF_ROW_TZ; }
+    // a layer's first and last plane follow from its half bits: a layer whose upper half alone is swept starts at + 4, one whose lower
+    // half alone is swept ends at + 4 -- at the segment's ends (the neighbouring wave has the other half) as inside it (the sub-verdicts
+    // found the other half dead).  Every set half has a plane the slab owns (the plan kernel saw to it), so no layer is cut down to nothing.
+    auto layer_zb = [&](int l) { return max((lt0 + l) * DF_ROW_TZ + df_halves_z0(seg, l), a.z_own0); };
+    auto layer_ze = [&](int l) { return min((lt0 + l) * DF_ROW_TZ + df_halves_z1(seg, l), own1); };
     if (alive) {
         // batch sequence: U planes per batch inside a layer, then the first batch of the next alive layer; l < 0 = none
         auto advance = [&](int l, int z0, int* nl, int* nz0) {

@@ -14,7 +14,7 @@ struct DfWarpedArgs {
     DfAff vol2world, world2cam;
     DfIntegrateParams P;
     unsigned long long* n_upd;
-    unsigned long long* n_swept;   // nullable (dfusion_warp_debug_counters): += voxels of the plan's alive (patch, layer) cells
+    unsigned long long* n_swept;   // nullable (dfusion_warp_debug_counters): += voxels of the plan's alive (patch, half layer) cells
     // conservative cull (disabled when cull == null).  cull[0] = max |t_i|, cull[1] = max sin(theta_i/2)
     // (> 1 => bound unavailable), cull[2] = max dists value of this frame; all produced on the stream, so the
     // frame needs no host round trip.
@@ -35,8 +35,9 @@ struct DfWarpedArgs {
     int sat_ok;                    // trunc inside the domain of the saturated-sample shortcut (df_sat_trunc_ok; set by the launcher)
     // pipelined sweep: the launch plan.  A STRIP item is half a 32 x 16 tile column (4 patches of 8 x 8 columns side by side: the
     // waves that share the 128-byte lines of the voxel rows) over one block of zt tile layers; item = ((zb * tiles_y + ty) * tiles_x
-    // + tx) * 2 + half.  plan_mask[item] holds its 4 x 16 verdict bits (bit 16 p + l: patch p, layer l alive); the items with w > 0
-    // bits set are listed in bin w (plan_bins[w * plan_items ...], plan_cnt[w] of them) -- all made on the stream by
+    // + tx) * 2 + half.  plan_mask[2 item], [2 item + 1] hold its 4 x 16 x 2 verdict bits, one per HALF layer (8 x 8 x 4 voxels): word
+    // p >> 1, bit 32 (p & 1) + 2 l + h = planes 4 h .. 4 h + 3 of layer l of patch p are swept (dfusion_plan_halves.h); the items with
+    // any bit set are listed in bin w = half the set bits, rounded up (plan_bins[w * plan_items ...], plan_cnt[w] of them) -- all made on the stream by
     // df_sweep_plan_kernel, so the sweep's workgroups are full of work from the first to the last, whatever the frustum cuts out.
     const unsigned long long* plan_mask; const unsigned int* plan_bins; const unsigned int* plan_cnt; unsigned int plan_items; int plan_tiles_y;
     // the verdict pass's list lengths (device, this frame's counter set) and where the plan kernel reports them to the host (pinned; both nullable)
@@ -52,6 +53,12 @@ struct DfWarpedArgs {
     // 4-bit neighbour codes (null = none): see df_code_index / df_block_model_kernel
     uint32_t* code_tab; uint32_t* bm_ids; uint8_t* bm_coded;
     const unsigned long long* plan_code;       // pipelined sweep: per strip item, bit 16 p + l: the cell's block has codes
+    // sub-block models (k = 8, written by the model pass beside the union lists; null = none): per union entry of every 4 x 4 x 4 sub-block
+    // the {mid, half width} half pairs of lambda and of w over its 64 voxels, [block][entry][sub] (sub = 4 h + q); bm_sub_cnt
+    // [block * 8 + sub] = entries | reference entry << 8; bm_sub_ok [block] 1 = the block has them (every sub-union fits, weights normalise)
+    uint32_t* bm_sub_lam; uint32_t* bm_sub_w; uint16_t* bm_sub_cnt; uint8_t* bm_sub_ok;
+    // this frame's sub-verdicts (df_sub_verdict_kernel), one byte per block, bit 4 h + q; null = every half layer of an alive block is swept
+    const uint8_t* blk_sub;
     // table build (df_warp_brick_kernel<K, true>): per-block bound on sum_i w_i (same block grid), and -- when the build is driven by a
     // work list instead of the launch grid -- the list of packed brick coordinates (x | y << 10 | z << 20) and its length
     float* blk_wmax; const uint32_t* work; const uint32_t* work_cnt; uint32_t* work_cursor;

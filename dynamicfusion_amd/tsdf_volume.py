@@ -241,12 +241,13 @@ class TsdfVolume:
     # ---- the north-star composition; no reference method of this name exists
     def integrate_warped(self, dists, camera_pose, intr, warp_field, k=None, n_updated=None, cull=True, sync=True,
                          use_table=True, use_weights=True, use_lds=True, pipelined=True, zero_skip=True, depth_pyramid=True, block_model=True,
-                         prefetch=True, codes=True):
+                         prefetch=True, codes=True, sub_verdict=True):
         """block_model: True = the library's policy (models built the second time a weight table is swept), "now" = at the first
         sweep, False = never (DF_WARP_NO_BLOCK_MODEL).  prefetch: True = the library's policy (look-ahead builds on the handle's side
         stream, switched off on a scene at rest from an unsynchronised report), False = DF_WARP_NO_PREFETCH, "steady" = on in every
         frame (DF_WARP_STEADY_PREFETCH: reproducible swept-voxel counters).  codes: False = DF_WARP_NO_CODES (modelled blocks read the full
-        16-B neighbour record instead of their 4-bit codes)."""
+        16-B neighbour record instead of their 4-bit codes).  sub_verdict: False = DF_WARP_NO_SUB_VERDICT (whole blocks are kept or
+        dropped; no half layer is skipped inside a kept block)."""
         k = warp_field.k if k is None else k
         world2cam = affine_mul(affine_inv(np.asarray(camera_pose, F32)), warp_field.warp_to_live_)
         warp_field.ensure_index(self, k)
@@ -258,7 +259,7 @@ class TsdfVolume:
             (0 if use_weights else capi.DF_WARP_NO_WEIGHT_TABLE) | (0 if use_lds else capi.DF_WARP_NO_LDS) |
             (0 if pipelined else capi.DF_WARP_NO_PIPELINE) | (0 if zero_skip else capi.DF_WARP_NO_ZERO_SKIP) |
             (0 if depth_pyramid else capi.DF_WARP_NO_DEPTH_PYRAMID) | (capi.DF_WARP_STEADY_PREFETCH if prefetch == "steady" else 0 if prefetch else capi.DF_WARP_NO_PREFETCH) |
-            (0 if codes else capi.DF_WARP_NO_CODES) |
+            (0 if codes else capi.DF_WARP_NO_CODES) | (0 if sub_verdict else capi.DF_WARP_NO_SUB_VERDICT) |
             (capi.DF_WARP_BLOCK_MODEL_NOW if block_model == "now" else 0 if block_model else capi.DF_WARP_NO_BLOCK_MODEL),
             _ptr(n_updated) if n_updated is not None else None, _stream()), "dfusion_integrate_warped")
         if sync:
@@ -266,7 +267,7 @@ class TsdfVolume:
 
     # ---- the same frame in two calls (include/dfusion.h dfusion_integrate_warped_prepare / _sweep): `prepare` does everything that does
     # not touch the volume and may run on another stream (beside the previous frame's ray-cast); `sweep` waits for it on the device
-    def integrate_warped_prepare(self, dists, camera_pose, intr, warp_field, k=None, prefetch=True, block_model=True, codes=True):
+    def integrate_warped_prepare(self, dists, camera_pose, intr, warp_field, k=None, prefetch=True, block_model=True, codes=True, sub_verdict=True):
         k = warp_field.k if k is None else k
         world2cam = affine_mul(affine_inv(np.asarray(camera_pose, F32)), warp_field.warp_to_live_)
         warp_field.ensure_index(self, k)
@@ -275,7 +276,7 @@ class TsdfVolume:
             dp, pitch, cols, rows, self.c_volume(), self.c_slab(), capi.floats(aff12(self.pose_)),
             capi.floats(aff12(world2cam)), intr.as_proj(), warp_field.handle, k,
             (capi.DF_WARP_STEADY_PREFETCH if prefetch == "steady" else 0 if prefetch else capi.DF_WARP_NO_PREFETCH) |
-            (0 if codes else capi.DF_WARP_NO_CODES) |
+            (0 if codes else capi.DF_WARP_NO_CODES) | (0 if sub_verdict else capi.DF_WARP_NO_SUB_VERDICT) |
             (capi.DF_WARP_BLOCK_MODEL_NOW if block_model == "now" else 0 if block_model else capi.DF_WARP_NO_BLOCK_MODEL),
             _stream()), "dfusion_integrate_warped_prepare")
 

@@ -109,6 +109,10 @@ enum {
 #define DF_WARP_NO_CODES 2048u /* the sweep reads the 16-byte neighbour-index record of every voxel and gathers its neighbours' transforms
                                  * from global memory, instead of the 4-bit codes into the per-wave copies of the 4 x 4 x 4 sub-block unions
                                  * (k = 8; every block the model pass has visited); validation / A/B switch (ABI 5)                      */
+#define DF_WARP_NO_SUB_VERDICT 4096u /* the launch plan keeps or drops whole 8 x 8 x 8 blocks: no second verdict per 4 x 4 x 4 sub-block (from blend
+                                 * models of the sub-blocks, made beside the block models at k = 8), by which the sweep skips a half layer
+                                 * (8 x 8 x 4 voxels) none of whose four sub-blocks can update; validation / A/B switch.  Implied by
+                                 * DF_WARP_NO_BLOCK_MODEL and DF_WARP_NO_CULL.                                                        */
 #define DF_WARP_STEADY_PREFETCH 1024u /* keep the look-ahead side stream on in EVERY frame.  By default a handle whose last plan-kernel report
                                  * listed nothing to build switches it off until the next probe (every 8th sweep); that report is read from
                                  * pinned host memory WITHOUT a synchronisation, so which frame switches depends on host / GPU timing --
@@ -361,7 +365,7 @@ int dfusion_warp_set_point_tiling(DfWarpField *wf, int image_cols);
 int dfusion_selftest_exact_forms(unsigned long long n_random, unsigned long long *counts_dev, dfStream stream);
 
 /* Measurement hook of dfusion_integrate_warped's cached sweep, per warp-field handle (NULL switches it off): while set, every
- * launch through this handle ADDS to *swept_dev (device, 8 bytes) the voxels of the (8 x 8 column patch, 8-plane layer) cells its
+ * launch through this handle ADDS to *swept_dev (device, 8 bytes) the voxels of the (8 x 8 column patch, 4-plane half layer) cells its
  * launch plan keeps, i.e. the voxels that go through blend -> transform -> project.                                              */
 int dfusion_warp_debug_counters(DfWarpField *wf, unsigned long long *swept_dev);
 
