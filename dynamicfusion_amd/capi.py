@@ -63,6 +63,7 @@ SYMBOLS = [
     "dfusion_render_image_points", "dfusion_render_image_depth", "dfusion_render_tangent_colors", "dfusion_cloud_to_depth",
     "dfusion_warp_extend", "dfusion_warp_solve", "dfusion_warp_node_graph", "dfusion_extract_mesh",
     "dfusion_warp_solve_robust", "dfusion_associate_projective", "dfusion_warp_solve_plane",
+    "dfusion_color_clear", "dfusion_color_integrate", "dfusion_color_fetch",
 ]
 
 
@@ -124,6 +125,10 @@ def load(path, strict=True):
     L.dfusion_extract_cloud.argtypes = [DfVolume, C.POINTER(DfSlab), fp, vp, C.c_ulonglong, vp, vp]
     L.dfusion_extract_normals.argtypes = [DfVolume, C.POINTER(DfSlab), fp, fp, vp, C.c_ulonglong, C.c_float, vp, vp]
     L.dfusion_extract_mesh.argtypes = [DfVolume, C.POINTER(DfSlab), fp, vp, C.c_ulonglong, vp, C.c_ulonglong, vp, vp]
+    L.dfusion_color_clear.argtypes = [vp, DfVolume, C.POINTER(DfSlab), vp]
+    L.dfusion_color_integrate.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, DfVolume, C.POINTER(DfSlab), vp, fp, fp, fp, vp, C.c_int,
+                                          C.c_float, C.c_int, C.c_longlong, vp, vp, vp]
+    L.dfusion_color_fetch.argtypes = [vp, DfVolume, C.POINTER(DfSlab), fp, vp, C.c_ulonglong, vp, vp]
     L.dfusion_warp_create.argtypes = [C.POINTER(vp)]
     L.dfusion_warp_destroy.argtypes = [vp]
     L.dfusion_warp_set_nodes.argtypes = [vp, vp, vp, vp, C.c_int, vp]

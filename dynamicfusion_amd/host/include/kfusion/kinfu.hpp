@@ -11,6 +11,7 @@
 #include <kfusion/types.hpp>
 #include <kfusion/cuda/projective_icp.hpp>
 #include <kfusion/cuda/tsdf_volume.hpp>
+#include <kfusion/cuda/color_volume.hpp>
 #include <kfusion/warp_field.hpp>
 
 namespace kfusion
@@ -62,6 +63,11 @@ namespace kfusion
         float warp_assoc_dist_thres = 0.05f; // its distance gate (metres),
         float warp_assoc_angle_thres = 0.52359878f;   // its normal gate (radians: 30 degrees, used as its cosine)
         float warp_assoc_occlusion_margin = 0.02f;    // and how far behind the nearest warped point of its pixel a point may lie (< 0: off)
+        bool integrate_color = false;        // fuse operator()'s colour image into a colour volume (cuda::ColorVolume) after the frame's depth
+                                             // integrate -- through the warp field when warped_fusion is on; default off = the image is
+                                             // dropped, as in the reference, and no launch is added
+        float color_band = 1.f;              // its band (ColorVolume::setBand)
+        int color_max_weight = 64;           // and the cap of its weight byte (ColorVolume::setMaxWeight)
     };
 
     class KinFu
@@ -83,6 +89,8 @@ namespace kfusion
         cuda::ProjectiveICP& icp() { return *icp_; }
         const WarpField& getWarp() const { return *warp_; }
         WarpField& getWarp() { return *warp_; }
+        /// the colour volume integrate_color fuses into (allocated on first use: 4 bytes a voxel)
+        cuda::ColorVolume& colorVolume();
 
         void reset();
         bool operator()(const cuda::Depth& depth, const cuda::Image& image = cuda::Image());
@@ -103,6 +111,8 @@ namespace kfusion
         virtual void optimiseWarp(std::vector<Vec3f>& canonical, std::vector<Vec3f>& canonical_normals, const std::vector<Vec3f>& live);
     private:
         void allocate_buffers();
+        void fuse_color(const cuda::Dists& dists, const Affine3f& camera_pose, bool warped);
+        void color_dists_before_surface_fusion(const cuda::Depth& depth);
         int frame_counter_;
         KinFuParams params_;
         std::vector<Affine3f> poses_;
@@ -112,6 +122,8 @@ namespace kfusion
         std::unique_ptr<cuda::TsdfVolume> volume_;
         std::unique_ptr<cuda::ProjectiveICP> icp_;
         std::unique_ptr<WarpField> warp_;
+        std::unique_ptr<cuda::ColorVolume> color_; cuda::Dists color_dists_;
+        const cuda::Image* frame_image_ = nullptr;                          // operator()'s image while the frame runs
         // scratch of the device-resident dynamicfusion()
         cuda::Cloud df_cloud_; cuda::Normals df_normals_;
         cuda::DeviceArray<float> df_points3_, df_normals3_, df_live3_, df_assoc3_, df_plane_normals3_;

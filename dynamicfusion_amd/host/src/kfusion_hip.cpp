@@ -8,6 +8,7 @@
 #include <cstring>
 #include <hip/hip_runtime_api.h>
 #include <kfusion/cuda/tsdf_volume.hpp>
+#include <kfusion/cuda/color_volume.hpp>
 #include <kfusion/cuda/imgproc.hpp>
 #include <kfusion/warp_field.hpp>
 #include <kfusion/cuda/projective_icp.hpp>
@@ -312,6 +313,61 @@ void TsdfVolume::fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& trian
     if (!n[0] && !n[1]) return;
     KF_DF(dfusion_extract_mesh(c_volume(*this), c_slab(*this).ptr(), aff, n[0] ? (float*)vertices.ptr() : nullptr, n[0],
                                n[1] ? (unsigned int*)triangles.ptr() : nullptr, n[1], counts.ptr(), nullptr));
+}
+
+// ------------------------------------------------------------------------------------------ ColorVolume (include/dfusion.h dfusion_color_*)
+ColorVolume::ColorVolume(const TsdfVolume& volume) : volume_(&volume)
+{
+    const Vec3i dims = volume.getDims();
+    data_.create((size_t)dims[0] * dims[1] * (size_t)volume.slabStoreN() * 4);
+    counts_.create(2);
+    clear();
+}
+
+void ColorVolume::clear()
+{
+    KF_DF(dfusion_color_clear(data_.ptr<char>(), c_volume(*volume_), c_slab(*volume_).ptr(), nullptr));
+}
+
+void ColorVolume::integrate_impl(const Image& image, const Dists& dists, const Affine3f& camera_pose, const Intr& intr, const WarpField* warp)
+{
+    if (image.rows() != dists.rows() || image.cols() != dists.cols()) kfusion::cuda::error("image and dists differ in size", __FILE__, __LINE__, "ColorVolume::integrate");
+    float v2w[12], w2c[12];
+    affine_to_aff12(volume_->getPose(), v2w);
+    affine_to_aff12(warp ? camera_pose.inv() * warp->getWarpToLive() : camera_pose.inv(), w2c);
+    const float proj[4] = {intr.fx, intr.fy, intr.cx, intr.cy};
+    long long capacity = capacity_;
+    if (capacity <= 0) {
+        const Vec3i dims = volume_->getDims();
+        const long long n = (long long)dims[0] * dims[1] * volume_->slabOwnN();
+        capacity = std::max(1ll, std::min(n, std::max(n / 16, 65536ll)));
+    }
+    KF_DF(dfusion_color_integrate((const unsigned char*)image.ptr(), image.step(), dists.ptr(), dists.step(), dists.cols(), dists.rows(), c_volume(*volume_),
+                                  c_slab(*volume_).ptr(), data_.ptr<char>(), v2w, w2c, proj, warp ? warp->handle() : nullptr, warp ? warp->k() : 0, band_,
+                                  max_weight_, capacity, counts_.ptr(), counts_.ptr() + 1, nullptr));
+}
+void ColorVolume::integrate(const Image& image, const Dists& dists, const Affine3f& camera_pose, const Intr& intr)
+{
+    integrate_impl(image, dists, camera_pose, intr, nullptr);
+}
+void ColorVolume::integrate(const Image& image, const Dists& dists, const Affine3f& camera_pose, const Intr& intr, const WarpField& warp)
+{
+    integrate_impl(image, dists, camera_pose, intr, &warp);
+}
+
+void ColorVolume::fetchColors(const DeviceArray<Point>& points, DeviceArray<RGB>& colors) const
+{
+    colors.create(points.size());
+    if (!points.size()) return;
+    float w2v[12]; affine_to_aff12(volume_->getPose().inv(), w2v);          // (the inverse in double, like fetchNormals' Rinv)
+    KF_DF(dfusion_color_fetch(data_.ptr<char>(), c_volume(*volume_), c_slab(*volume_).ptr(), w2v, (const float*)points.ptr(), points.size(),
+                              (unsigned char*)colors.ptr(), nullptr));
+}
+
+void ColorVolume::download(std::vector<unsigned char>& bytes) const
+{
+    bytes.resize(data_.sizeBytes());
+    data_.download(bytes.data());
 }
 
 void TsdfVolume::compute_points()
@@ -987,6 +1043,7 @@ void KinFu::reset()                                                    // kinfu.
     poses_.reserve(30000);
     poses_.push_back(Affine3f::Identity());
     volume_->clear();
+    if (color_) color_->clear();
 }
 
 void KinFu::optimiseWarp(std::vector<Vec3f>& canonical, std::vector<Vec3f>& canonical_normals, const std::vector<Vec3f>& live)
@@ -1044,9 +1101,38 @@ Affine3f KinFu::getCameraPose(int time) const                          // kinfu.
     return poses_[time];
 }
 
-bool KinFu::operator()(const cuda::Depth& depth, const cuda::Image& /*image*/)    // kinfu.cpp:220-304 (default build: points pyramids)
+cuda::ColorVolume& KinFu::colorVolume()
+{
+    if (!color_) {                                                      // made on first use: 4 bytes a voxel that a run without colour never allocates
+        color_.reset(new cuda::ColorVolume(*volume_));
+    }
+    return *color_;
+}
+
+// KinFuParams::integrate_color: the frame's image into the colour volume, after the frame's depth integrate (which the colour reads)
+void KinFu::fuse_color(const cuda::Dists& dists, const Affine3f& camera_pose, bool warped)
+{
+    if (!params_.integrate_color || !frame_image_ || frame_image_->empty()) return;
+    cuda::ColorVolume& c = colorVolume();
+    c.setBand(params_.color_band);
+    c.setMaxWeight(params_.color_max_weight);
+    if (warped) c.integrate(*frame_image_, dists, camera_pose, params_.intr, *warp_);
+    else c.integrate(*frame_image_, dists, camera_pose, params_.intr);
+}
+
+// surface_fusion fuses rigidly, on a dists image of its own, and zeroes the pixels of `depth` that the warped model explains: the
+// colour goes in rigidly too, after it, against the dists of the whole depth image -- taken here, before surface_fusion runs
+void KinFu::color_dists_before_surface_fusion(const cuda::Depth& depth)
+{
+    if (!params_.integrate_color || !frame_image_ || frame_image_->empty()) return;
+    cuda::computeDists(depth, color_dists_, params_.intr);
+}
+
+bool KinFu::operator()(const cuda::Depth& depth, const cuda::Image& image)    // kinfu.cpp:220-304 (default build: points pyramids)
 {
     const KinFuParams& p = params_;
+    frame_image_ = &image;                                              // (dynamicfusion() keeps the reference's signature)
+    struct Forget { const cuda::Image*& p; ~Forget() { p = nullptr; } } forget{frame_image_};
     const int LEVELS = icp_->getUsedLevelsNum();
     cuda::computeDists(depth, dists_, p.intr);
     cuda::depthBilateralFilter(depth, curr_.depth_pyr[0], p.bilateral_kernel_size, p.bilateral_sigma_spatial, p.bilateral_sigma_depth);
@@ -1062,6 +1148,7 @@ bool KinFu::operator()(const cuda::Depth& depth, const cuda::Image& /*image*/)  
 
     if (frame_counter_ == 0) {                                          // :246-265
         volume_->integrate(dists_, poses_.back(), p.intr);
+        fuse_color(dists_, poses_.back(), false);
         volume_->compute_points();
         volume_->compute_normals();
         // warp_->init(cloud): the reference's cv::Mat overload keeps every 50th point (warp_field.cpp:49-60) and leaves the rest of
@@ -1119,6 +1206,7 @@ void KinFu::dynamicfusion(cuda::Depth& depth, cuda::Cloud live_frame, cuda::Norm
     if (warp_->nodeCount() < (size_t)warp_->k()) {                      // no usable warp field (empty first frame): plain KinFu fusion
         cuda::Dists dists; cuda::computeDists(depth, dists, params_.intr);
         volume_->integrate(dists, camera_pose, params_.intr);
+        fuse_color(dists, camera_pose, false);
         return;
     }
     const size_t n = (size_t)depth.rows() * depth.cols();
@@ -1177,11 +1265,14 @@ void KinFu::dynamicfusion(cuda::Depth& depth, cuda::Cloud live_frame, cuda::Norm
         if (params_.warped_fusion) {
             cuda::Dists dists; cuda::computeDists(depth, dists, params_.intr);
             volume_->integrate(dists, camera_pose, params_.intr, *warp_);
+            fuse_color(dists, camera_pose, true);
         } else {
             KF_DF(dfusion_transform_points(df_points3_.ptr(), 3 * n * sizeof(float), 3, (float*)df_warped4_.ptr(), n * sizeof(Point), 4, (int)n, 1,
                                            nullptr, nullptr));
             cuda::DeviceArray<Point> warped(df_warped4_.ptr(), n);
+            color_dists_before_surface_fusion(depth);
             volume_->surface_fusion(*warp_, warped, depth, camera_pose, params_.intr);
+            fuse_color(color_dists_, camera_pose, false);
         }
         volume_->compute_points();
         volume_->compute_normals();
@@ -1209,8 +1300,11 @@ void KinFu::dynamicfusion(cuda::Depth& depth, cuda::Cloud live_frame, cuda::Norm
     if (params_.warped_fusion) {
         cuda::Dists dists; cuda::computeDists(depth, dists, params_.intr);
         volume_->integrate(dists, camera_pose, params_.intr, *warp_);
+        fuse_color(dists, camera_pose, true);
     } else {
+        color_dists_before_surface_fusion(depth);
         volume_->surface_fusion(*warp_, canonical, canonical_visible, depth, camera_pose, params_.intr);   // :393
+        fuse_color(color_dists_, camera_pose, false);
     }
     volume_->compute_points();                                          // :398-399
     volume_->compute_normals();

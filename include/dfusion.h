@@ -297,6 +297,45 @@ int dfusion_extract_mesh(DfVolume v, const DfSlab *slab, const float aff[12], fl
                          unsigned long long vertex_capacity, unsigned int *triangles_dev,
                          unsigned long long triangle_capacity, unsigned long long *counts_dev, dfStream stream);
 
+/* ---- colour volume (no reference counterpart: KinFu::operator() drops its colour image; additive, ABI 7) ----------------------
+ * A colour volume belongs to a TSDF volume: the same dims, linear layout (x + y X + z X Y) and stored planes (DfSlab), 4 bytes a
+ * voxel {c0, c1, c2, w}: three channels in the byte order of the input image (the kernels treat them alike) and a weight byte;
+ * cleared = all zero.  `geometry` is the TSDF volume's DfVolume; its data pointer is not looked at.  DESIGN.md states the rule in
+ * full; tests/color_ref.py restates it in numpy and the bytes equal it.
+ *
+ * dfusion_color_integrate fuses one image (rgb_dev: 4 bytes a pixel, the 4th ignored; same cols x rows as dists) through the
+ * composition of dfusion_integrate_warped.  It READS the TSDF volume as it is when the call runs (in a frame: after that frame's
+ * depth integrate) and never writes it.
+ *   select   voxels of the slab's own planes with stored weight > 0 and fabsf(tsdf) < band (0 < band <= 1; strict, so saturated
+ *            free space is out), in ascending linear index; at most `capacity` of them, lowest indices first, are processed;
+ *            *n_selected_dev (nullable) is WRITTEN with the full count, so a caller can see a truncation;
+ *   project  x_c = vol2world * (x vsx, y vsy, z vsz); x_w = DQB(x_c).transform(x_c) over the k nearest nodes in nanoflann's tie order
+ *            (wf NULL: x_w = x_c; k is then ignored); vc = world2cam * x_w; u = fmaf(fx, vc.x / vc.z, cx), v alike; skipped unless
+ *            u >= 0 && v >= 0 && u < cols && v < rows (NaN skips); Dp = dists[(int)v][(int)u]; skipped if Dp == 0 || vc.z <= 0;
+ *            sdf = Dp - sqrtf(dot(vc, vc)); the voxel is OBSERVED iff fabsf(sdf) < band * trunc_dist -- the occlusion test: a voxel
+ *            behind what the camera sees keeps its colour;
+ *   fuse     integer arithmetic, c = the bytes of pixel [(int)v][(int)u], w = the stored weight byte: every channel becomes
+ *            (old w + c + ((w + 1) >> 1)) / (w + 1), then w <- min(w + 1, max_weight), 1 <= max_weight <= 255.  One thread writes a
+ *            voxel; *n_fused_dev (nullable) is WRITTEN with the number of voxels fused.
+ * No device-to-host copy and no synchronisation: the launches cover the capacity and the device-side count bounds the work.
+ * Workspace: 8 bytes per 256 voxels + 16 bytes per voxel of capacity, from the per-(device, stream) scratch of dfusion_integrate.
+ * DF_E_INVALID: a NULL pointer (wf, the counters excepted), a pitch shorter than a row, rgb_dev or its pitch not 4-byte aligned, band outside (0, 1] or NaN, max_weight outside
+ * 1..255, capacity <= 0, with a warp field k outside 1..8 or fewer nodes than k, more than 2^32 - 1 stored voxels.
+ *
+ * dfusion_color_fetch reads the colour of N points (float4, as dfusion_extract_cloud / _mesh return them) into rgba_out_dev (4 bytes
+ * a point): p = world2vol * point (the caller inverts the volume pose); cf = p / voxel_size per axis; g = floorf(cf), a, b, c = cf - g;
+ * the eight taps g + (dx, dy, dz) in the order z fastest, then y, then x, each with weight ((dx ? a : 1 - a) (dy ? b : 1 - b))
+ * (dz ? c : 1 - c); a tap outside the stored volume or with weight byte 0 is left out; sw and the three channel sums add up in tap
+ * order (products rounded before the add); sw > 0: every channel is min(255, (int)floorf(sc / sw + 0.5f)) and the 4th byte 255, else
+ * all four bytes are 0, as for a point with a non-finite component.                                                              */
+int dfusion_color_clear(void *color_dev, DfVolume geometry, const DfSlab *slab, dfStream stream);
+int dfusion_color_integrate(const unsigned char *rgb_dev, size_t rgb_pitch, const uint16_t *dists_dev, size_t dists_pitch, int cols,
+                            int rows, DfVolume v, const DfSlab *slab, void *color_dev, const float vol2world[12],
+                            const float world2cam[12], const float proj[4], DfWarpField *wf, int k, float band, int max_weight,
+                            long long capacity, unsigned long long *n_selected_dev, unsigned long long *n_fused_dev, dfStream stream);
+int dfusion_color_fetch(const void *color_dev, DfVolume geometry, const DfSlab *slab, const float world2vol[12],
+                        const float *points_dev, unsigned long long N, unsigned char *rgba_out_dev, dfStream stream);
+
 /* ---- warp field -----------------------------------------------------------------------------
  * WarpField::WarpField / ~WarpField (warp_field.cpp:17-34).                                    */
 int dfusion_warp_create(DfWarpField **out);
