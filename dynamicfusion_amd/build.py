@@ -95,6 +95,7 @@ HOST_ROBUST_SOLVE = os.path.join(HOST_DIR, "robust_solve")
 HOST_ASSOCIATE = os.path.join(HOST_DIR, "associate")
 HOST_PLANE_SOLVE = os.path.join(HOST_DIR, "plane_solve")
 HOST_COLOR_FRAME = os.path.join(HOST_DIR, "color_frame")
+HOST_RIGID_SOLVE = os.path.join(HOST_DIR, "rigid_solve")
 HOST_ZSLAB_LIB = os.path.join(HOST_DIR, "libkfusion_zslab.so")       # kfusion::cuda::ZSlabComm: the RCCL side of the Z-slab sharding
 HOST_ZSLAB_APP = os.path.join(HOST_DIR, "zslab_frame")
 
@@ -114,8 +115,9 @@ def build_host(force=False, verbose=False):
     app8 = os.path.join(HOST_DIR, "apps", "associate.cpp")
     app9 = os.path.join(HOST_DIR, "apps", "plane_solve.cpp")
     app10 = os.path.join(HOST_DIR, "apps", "color_frame.cpp")
-    deps = [src, app, app2, app3, app4, zsrc, app5, app6, app7, app8, app9, app10, LIB_PATH] + [os.path.join(r, f) for r, _, fs in os.walk(os.path.join(HOST_DIR, "include")) for f in fs]
-    outs = (HOST_LIB, HOST_APP, HOST_KINFU_APP, HOST_WARP_TESTS, HOST_DEMO_CALLS, HOST_ZSLAB_LIB, HOST_ZSLAB_APP, HOST_REG_SOLVE, HOST_ROBUST_SOLVE, HOST_ASSOCIATE, HOST_PLANE_SOLVE, HOST_COLOR_FRAME)
+    app11 = os.path.join(HOST_DIR, "apps", "rigid_solve.cpp")
+    deps = [src, app, app2, app3, app4, zsrc, app5, app6, app7, app8, app9, app10, app11, LIB_PATH] + [os.path.join(r, f) for r, _, fs in os.walk(os.path.join(HOST_DIR, "include")) for f in fs]
+    outs = (HOST_LIB, HOST_APP, HOST_KINFU_APP, HOST_WARP_TESTS, HOST_DEMO_CALLS, HOST_ZSLAB_LIB, HOST_ZSLAB_APP, HOST_REG_SOLVE, HOST_ROBUST_SOLVE, HOST_ASSOCIATE, HOST_PLANE_SOLVE, HOST_COLOR_FRAME, HOST_RIGID_SOLVE)
     if not force and all(os.path.exists(f) for f in outs) and min(os.path.getmtime(f) for f in outs) >= max(os.path.getmtime(d) for d in deps):
         return HOST_LIB, HOST_APP
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
@@ -132,6 +134,7 @@ def build_host(force=False, verbose=False):
             common + [app8, "-o", HOST_ASSOCIATE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + [app9, "-o", HOST_PLANE_SOLVE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + [app10, "-o", HOST_COLOR_FRAME, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
+            common + [app11, "-o", HOST_RIGID_SOLVE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + ["-fPIC", "-shared", zsrc, "-o", HOST_ZSLAB_LIB, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-lrccl", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + [app5, "-o", HOST_ZSLAB_APP, "-L", HOST_DIR, "-lkfusion_zslab", "-lkfusion_hip"] + link + ["-lrccl", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."]]
     for c in cmds:

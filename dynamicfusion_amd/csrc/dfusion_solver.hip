@@ -20,6 +20,8 @@
 // data term along the model normals (point-to-plane).  The four entry points share one
 // host pipeline at the end of this file: one workspace (SvWorkspace), one preparation (df_sv_prepare: what depends only on the
 // canonical points and the node positions) and one round loop (df_sv_rounds), in which a term that is switched off launches nothing.
+// dfusion_warp_solve_rigid makes the node rotations unknowns too, against the warp dfusion_warp_points applies: its own
+// round loop (df_sv_rigid_rounds) on the same workspace, graph, sort, lists, penalty and coupled step kernels.
 // Nothing returns to the host between iterations: once every component has converged (scal[SV_ACTIVE] == 0) the kernels of the
 // remaining steps return at once.
 #include <hipcub/hipcub.hpp>
@@ -637,6 +639,311 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_plane_energy_kernel(const floa
     if (threadIdx.x == 0) *out = acc[0];
 }
 
+// ---------------------------------------------------------------- node rotations as unknowns
+// dfusion_warp_solve_rigid: Gauss-Newton rounds against the warp the pipeline applies, y_v = DQB(canonical_v).transform(canonical_v)
+// from dfusion_warp_points.  That blend (dqb_blend_w) turns the point by the normalised sum of the weighted node rotations and adds the
+// sum of the node translations under the UNNORMALISED weights: y_v = R_v p_v + T_v, T_v = sum_i w_vi t_i.  Six unknowns a node, a rotation
+// omega_n about the node's warped position c_n = T_n(pos_n) and a translation tau_n, change t_n by tau_n - omega_n x q_n, q_n = c_n - t_n,
+// and R_v by the blend of the omega_i under wn_vi = w_vi / S_v (to first order, for node rotations that are close to each other):
+//     dy_v = sum_i w_vi (tau_i - omega_i x q_i) + (sum_i wn_vi omega_i) x a_v,   a_v = y_v - T_v = R_v p_v.
+// The unknowns are one 3-component array of 2M entries (omega_n at entry n, tau_n at entry M + n), so that the COUPLED init and step
+// kernels above run on it as they are.  Products are rounded before they are added, sums run in slot / list / edge order.
+
+// ---- per point, once per call: validity (the first round's warp included), the blend weights and their normalised copies, node ids
+__global__ __launch_bounds__(256) void df_sv_rigid_setup_kernel(const float* __restrict__ canonical, const float* __restrict__ live,
+                                                                const float* __restrict__ normals, const float* __restrict__ y,
+                                                                const float* __restrict__ nw, int N, int k, const int* __restrict__ idx,
+                                                                const float* __restrict__ d2, const float4* __restrict__ pos_sigma, int M,
+                                                                float* __restrict__ w, float* __restrict__ wn, unsigned int* __restrict__ keys,
+                                                                unsigned int* __restrict__ vals)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= N) return;
+    bool valid = true;
+    for (int c = 0; c < 3; ++c) {
+        valid = valid && !isnan(canonical[3 * v + c]) && !isnan(live[3 * v + c]) && isfinite(y[3 * v + c]);
+        if (normals) valid = valid && isfinite(normals[3 * v + c]) && isfinite(nw[3 * v + c]);
+    }
+    float S = 0.f;
+    for (int j = 0; j < k; ++j) {                                       // (a finite y had a finite query: its k ids are node ids)
+        const int e = v * k + j;
+        const float wj = valid ? dqb_weight(d2[e], pos_sigma[min(max(idx[e], 0), M - 1)].w) : 0.f;
+        w[e] = wj;
+        S = S + wj;
+    }
+    valid = valid && !(S == 0.f);
+    for (int j = 0; j < k; ++j) {
+        const int e = v * k + j;
+        const float wj = w[e];
+        w[e] = valid ? wj : 0.f;
+        wn[e] = valid ? wj / S : 0.f;
+        keys[e] = valid ? (unsigned int)min(max(idx[e], 0), M - 1) : (unsigned int)M;
+        vals[e] = (unsigned int)e;
+    }
+}
+
+// ---- per node and round: c_n = T_n(pos_n), the point the round's rotation update turns about, and q_n = c_n - t_n
+__global__ __launch_bounds__(256) void df_sv_rigid_centre_kernel(const float4* __restrict__ pos_sigma, const float4* __restrict__ rot,
+                                                                 const float4* __restrict__ dual, const float4* __restrict__ node_t, int M,
+                                                                 float4* __restrict__ c, float4* __restrict__ qc)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= M) return;
+    const float4 p = pos_sigma[n], r = rot[n], d = dual[n], nt = node_t[n];
+    quat a, b;
+    a.w = r.x; a.x = r.y; a.y = r.z; a.z = r.w; b.w = d.x; b.x = d.y; b.y = d.z; b.z = d.w;
+    const f3 t = dq_transform(a, b, mk3(p.x, p.y, p.z));
+    c[n] = make_float4(t.x, t.y, t.z, 0.f);
+    qc[n] = make_float4(t.x - nt.y, t.y - nt.z, t.z - nt.w, 0.f);
+}
+
+// ---- e_v = live_v - y_v and a_v = y_v - T_v, T_v = sum_i w_vi t_i in slot order (df_sv_setup_kernel's sums); 0 for an invalid point
+__global__ __launch_bounds__(256) void df_sv_rigid_residual_kernel(const float* __restrict__ live, const float* __restrict__ y,
+                                                                   const unsigned int* __restrict__ keys, const float* __restrict__ w,
+                                                                   const float4* __restrict__ node_t, int N, int k, int M,
+                                                                   float* __restrict__ e, float* __restrict__ arm)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= N) return;
+    const bool valid = keys[v * k] < (unsigned int)M;                   // (a point's k entries are valid together)
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    if (arm && valid)
+        for (int j = 0; j < k; ++j) {
+            const float wj = w[v * k + j];
+            const float4 t = node_t[keys[v * k + j]];                   // (w, x, y, z): translation in .y .z .w
+            sx = sx + wj * t.y; sy = sy + wj * t.z; sz = sz + wj * t.w;
+        }
+    const float yx = y[3 * v], yy = y[3 * v + 1], yz = y[3 * v + 2];
+    e[3 * v] = valid ? live[3 * v] - yx : 0.f; e[3 * v + 1] = valid ? live[3 * v + 1] - yy : 0.f; e[3 * v + 2] = valid ? live[3 * v + 2] - yz : 0.f;
+    if (arm) { arm[3 * v] = valid ? yx - sx : 0.f; arm[3 * v + 1] = valid ? yy - sy : 0.f; arm[3 * v + 2] = valid ? yz - sz : 0.f; }
+}
+
+// What J^T reads of a point, as one 32-byte record: (u, 0) and (a_v x u, 0).  The cross product depends on the point alone, so it is
+// formed once here instead of once per list entry, and a list entry's gather is two 16-byte loads of one aligned record.
+__device__ __forceinline__ void sv_rigid_store(float4* __restrict__ rec, int v, float ux, float uy, float uz, float ax, float ay, float az)
+{
+    rec[2 * (size_t)v] = make_float4(ux, uy, uz, 0.f);
+    rec[2 * (size_t)v + 1] = make_float4(ay * uz - az * uy, az * ux - ax * uz, ax * uy - ay * ux, 0.f);
+}
+
+// ---- u = J p : per point, slot order:  st = st + w (p_tau_n - (p_om_n x q_n)),  sr = sr + wn p_om_n,  u = st + (sr x a_v).
+// K as in df_sv_w_apply_kernel: with K > 0 the normal, a_v, the 3K entry loads and the K x (two p triples + one 16-byte q gather) are
+// all in flight before the first sum.  PLANE: u = n' (n' . J p) with n' the warped normal of the round; an invalid point stores 0.
+template <int K, bool PLANE>
+__global__ __launch_bounds__(256) void df_sv_rigid_j_apply_kernel(const float* __restrict__ w, const float* __restrict__ wn,
+                                                                  const unsigned int* __restrict__ keys, int N, int k, int M,
+                                                                  const float* __restrict__ p, const float* __restrict__ arm,
+                                                                  const float4* __restrict__ qc, float4* __restrict__ rec,
+                                                                  const float* __restrict__ active, const float* __restrict__ nw)
+{
+    if (active && *active == 0.f) return;                               // see df_sv_w_apply_kernel
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= N) return;
+    float nx = 0.f, ny = 0.f, nz = 0.f;
+    if constexpr (PLANE) { nx = nw[3 * v]; ny = nw[3 * v + 1]; nz = nw[3 * v + 2]; }
+    const float ax = arm[3 * v], ay = arm[3 * v + 1], az = arm[3 * v + 2];
+    const float* const pt = p + 3 * (size_t)M;                          // the tau half
+    float tx = 0.f, ty = 0.f, tz = 0.f, rx = 0.f, ry = 0.f, rz = 0.f;
+    if constexpr (K > 0) {
+        unsigned int n[K]; float wj[K], wnj[K], ox[K], oy[K], oz[K], hx[K], hy[K], hz[K]; float4 qn[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) { n[j] = keys[v * K + j]; wj[j] = w[v * K + j]; wnj[j] = wn[v * K + j]; }
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            const unsigned int nc = min(n[j], (unsigned int)(M - 1));            // clamped gather; the entry is skipped below if n >= M
+            ox[j] = p[3 * nc]; oy[j] = p[3 * nc + 1]; oz[j] = p[3 * nc + 2];
+            hx[j] = pt[3 * nc]; hy[j] = pt[3 * nc + 1]; hz[j] = pt[3 * nc + 2];
+            qn[j] = qc[nc];
+        }
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            if (n[j] < (unsigned int)M) {
+                const float gx = hx[j] - (oy[j] * qn[j].z - oz[j] * qn[j].y), gy = hy[j] - (oz[j] * qn[j].x - ox[j] * qn[j].z),
+                            gz = hz[j] - (ox[j] * qn[j].y - oy[j] * qn[j].x);
+                tx = tx + wj[j] * gx; ty = ty + wj[j] * gy; tz = tz + wj[j] * gz;
+                rx = rx + wnj[j] * ox[j]; ry = ry + wnj[j] * oy[j]; rz = rz + wnj[j] * oz[j];
+            }
+    } else {
+        for (int j = 0; j < k; ++j) {
+            const int e = v * k + j;
+            const unsigned int n = keys[e];
+            if (n < (unsigned int)M) {
+                const float wj = w[e], wnj = wn[e];
+                const float4 qn = qc[n];
+                const float ox = p[3 * n], oy = p[3 * n + 1], oz = p[3 * n + 2];
+                const float gx = pt[3 * n] - (oy * qn.z - oz * qn.y), gy = pt[3 * n + 1] - (oz * qn.x - ox * qn.z), gz = pt[3 * n + 2] - (ox * qn.y - oy * qn.x);
+                tx = tx + wj * gx; ty = ty + wj * gy; tz = tz + wj * gz;
+                rx = rx + wnj * ox; ry = ry + wnj * oy; rz = rz + wnj * oz;
+            }
+        }
+    }
+    float sx = tx + (ry * az - rz * ay), sy = ty + (rz * ax - rx * az), sz = tz + (rx * ay - ry * ax);
+    if constexpr (PLANE) {
+        const float d = (nx * sx + ny * sy) + nz * sz;
+        const bool valid = keys[v * k] < (unsigned int)M;               // (a point's k entries are valid together)
+        sx = valid ? nx * d : 0.f; sy = valid ? ny * d : 0.f; sz = valid ? nz * d : 0.f;
+    }
+    sv_rigid_store(rec, v, sx, sy, sz, ax, ay, az);
+}
+
+// ---- the record of a right-hand side u that no J p made (a round's b): see sv_rigid_store
+__global__ __launch_bounds__(256) void df_sv_rigid_pack_kernel(const float* __restrict__ u, const float* __restrict__ arm, int N,
+                                                               float4* __restrict__ rec)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= N) return;
+    sv_rigid_store(rec, v, u[3 * v], u[3 * v + 1], u[3 * v + 2], arm[3 * v], arm[3 * v + 1], arm[3 * v + 2]);
+}
+
+// ---- out = J^T u (+ lambda_rot * p_om, + lambda * p_tau) : df_sv_wt_apply_kernel's walk, thread stride and tree with six sums a node,
+// S1 = sum w u (the tau part) and S2 = sum wn (a_v x u); the omega part is S2 - (q_n x S1).
+__global__ __launch_bounds__(256) void df_sv_rigid_jt_apply_kernel(const unsigned int* __restrict__ off, const unsigned int* __restrict__ sorted_pt,
+                                                                   const float* __restrict__ sorted_w, const float* __restrict__ sorted_wn, int M,
+                                                                   const float4* __restrict__ rec, const float4* __restrict__ qc, float lambda,
+                                                                   float lambda_rot,
+                                                                   const float* __restrict__ p, float* __restrict__ out,
+                                                                   const float* __restrict__ active)
+{
+    __shared__ float lds[6 * 128];
+    if (active && *active == 0.f) return;                               // see df_sv_w_apply_kernel
+    const int n = blockIdx.x, t = threadIdx.x, wv = t >> 6, l = t & 63;
+    const unsigned int b = off[n], e_end = off[n + 1];
+    float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (unsigned int i = b + t; i < e_end; i += 256) {
+        const unsigned int v = sorted_pt[i];
+        const float we = sorted_w[i], wne = sorted_wn[i];
+        const float4 uv = rec[2 * (size_t)v], xv = rec[2 * (size_t)v + 1];   // (u, a_v x u): sv_rigid_store
+        s[0] = s[0] + we * uv.x; s[1] = s[1] + we * uv.y; s[2] = s[2] + we * uv.z;
+        s[3] = s[3] + wne * xv.x; s[4] = s[4] + wne * xv.y; s[5] = s[5] + wne * xv.z;
+    }
+    if (wv >= 2) { for (int q = 0; q < 6; ++q) lds[q * 128 + (t - 128)] = s[q]; }
+    __syncthreads();
+    if (wv < 2) { for (int q = 0; q < 6; ++q) s[q] = s[q] + lds[q * 128 + t]; }
+    __syncthreads();
+    if (wv == 1) { for (int q = 0; q < 6; ++q) lds[q * 128 + l] = s[q]; }
+    __syncthreads();
+    if (wv == 0) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            float a = s[q] + lds[q * 128 + l];
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) a = a + __shfl_down(a, o, 64);
+            s[q] = a;
+        }
+        if (l == 0) {
+            const float4 qn = qc[n];
+            float om[3] = {s[3] - (qn.y * s[2] - qn.z * s[1]), s[4] - (qn.z * s[0] - qn.x * s[2]), s[5] - (qn.x * s[1] - qn.y * s[0])};
+            float* const ot = out + 3 * (size_t)M;
+            if (p) {
+                const float* const pt = p + 3 * (size_t)M;
+                for (int q = 0; q < 3; ++q) { om[q] = om[q] + lambda_rot * p[3 * n + q]; s[q] = s[q] + lambda * pt[3 * n + q]; }
+            }
+            for (int q = 0; q < 3; ++q) { out[3 * n + q] = om[q]; ot[3 * n + q] = s[q]; }
+        }
+    }
+}
+
+// ---- per edge e = (i -> j) and round: g_e = T_i(v_j) - c_j (the regularisation residual) and b_e = T_i(v_j) - c_i (the arm omega_i turns)
+__global__ __launch_bounds__(256) void df_sv_rigid_edge_kernel(const int* __restrict__ nbr, const float4* __restrict__ pos_sigma,
+                                                               const float4* __restrict__ rot, const float4* __restrict__ dual,
+                                                               const float4* __restrict__ c, int E, int kg, float* __restrict__ g,
+                                                               float* __restrict__ arm)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    const int i = e / kg, j = nbr[e];
+    const float4 pj = pos_sigma[j], ri = rot[i], di = dual[i], ci = c[i], cj = c[j];
+    quat a, b;
+    a.w = ri.x; a.x = ri.y; a.y = ri.z; a.z = ri.w; b.w = di.x; b.x = di.y; b.y = di.z; b.z = di.w;
+    const f3 ti = dq_transform(a, b, mk3(pj.x, pj.y, pj.z));
+    g[3 * e] = ti.x - cj.x; g[3 * e + 1] = ti.y - cj.y; g[3 * e + 2] = ti.z - cj.z;
+    arm[3 * e] = ti.x - ci.x; arm[3 * e + 1] = ti.y - ci.y; arm[3 * e + 2] = ti.z - ci.z;
+}
+
+// ---- the regularisation on the six unknowns, one thread per node, df_sv_reg_apply_kernel's sum orders.  Per edge d_e = g_e (RHS) or
+// (p_tau_i + (p_om_i x b_e)) - p_tau_j, formed in the thread.  tau_n: + alpha_e d_e over the outgoing edges in slot order, then
+// - alpha_e d_e over the incoming edges in ascending edge id; om_n: + alpha_e (b_e x d_e) over the outgoing edges.
+// RHS: out = out - lambda_reg * acc (out holds J^T Omega b) ; else out = out + lambda_reg * acc (out holds (J^T Omega J + damping) p).
+template <bool RHS>
+__global__ __launch_bounds__(256) void df_sv_rigid_reg_kernel(const int* __restrict__ nbr, const float* __restrict__ alpha,
+                                                              const unsigned int* __restrict__ in_off, const unsigned int* __restrict__ in_edge,
+                                                              int M, int kg, const float* __restrict__ g, const float* __restrict__ arm,
+                                                              const float* __restrict__ p, float lambda_reg, float* __restrict__ out,
+                                                              const float* __restrict__ active)
+{
+    if (active && *active == 0.f) return;                               // see df_sv_w_apply_kernel
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= M) return;
+    const float* const pt = RHS ? nullptr : p + 3 * (size_t)M;
+    float on[3] = {0.f, 0.f, 0.f}, tn[3] = {0.f, 0.f, 0.f};
+    if constexpr (!RHS) for (int q = 0; q < 3; ++q) { on[q] = p[3 * n + q]; tn[q] = pt[3 * n + q]; }
+    float acc_o[3] = {0.f, 0.f, 0.f}, acc_t[3] = {0.f, 0.f, 0.f};
+    for (int s = 0; s < kg; ++s) {
+        const int e = n * kg + s;
+        const float a = alpha[e];
+        const float bx = arm[3 * e], by = arm[3 * e + 1], bz = arm[3 * e + 2];
+        float d[3];
+        if constexpr (RHS) { d[0] = g[3 * e]; d[1] = g[3 * e + 1]; d[2] = g[3 * e + 2]; }
+        else {
+            const int j = nbr[e];
+            d[0] = (tn[0] + (on[1] * bz - on[2] * by)) - pt[3 * j];
+            d[1] = (tn[1] + (on[2] * bx - on[0] * bz)) - pt[3 * j + 1];
+            d[2] = (tn[2] + (on[0] * by - on[1] * bx)) - pt[3 * j + 2];
+        }
+        for (int q = 0; q < 3; ++q) acc_t[q] = acc_t[q] + a * d[q];
+        acc_o[0] = acc_o[0] + a * (by * d[2] - bz * d[1]);
+        acc_o[1] = acc_o[1] + a * (bz * d[0] - bx * d[2]);
+        acc_o[2] = acc_o[2] + a * (bx * d[1] - by * d[0]);
+    }
+    for (unsigned int i = in_off[n]; i < in_off[n + 1]; ++i) {
+        const unsigned int e = in_edge[i], t = e / (unsigned int)kg;     // the edge t -> n
+        const float a = alpha[e];
+        float d[3];
+        if constexpr (RHS) { d[0] = g[3 * e]; d[1] = g[3 * e + 1]; d[2] = g[3 * e + 2]; }
+        else {
+            const float bx = arm[3 * e], by = arm[3 * e + 1], bz = arm[3 * e + 2];
+            const float ox = p[3 * t], oy = p[3 * t + 1], oz = p[3 * t + 2];
+            d[0] = (pt[3 * t] + (oy * bz - oz * by)) - tn[0];
+            d[1] = (pt[3 * t + 1] + (oz * bx - ox * bz)) - tn[1];
+            d[2] = (pt[3 * t + 2] + (ox * by - oy * bx)) - tn[2];
+        }
+        for (int q = 0; q < 3; ++q) acc_t[q] = acc_t[q] - a * d[q];
+    }
+    float* const ot = out + 3 * (size_t)M;
+    for (int q = 0; q < 3; ++q) {
+        if constexpr (RHS) { out[3 * n + q] = out[3 * n + q] - lambda_reg * acc_o[q]; ot[3 * n + q] = ot[3 * n + q] - lambda_reg * acc_t[q]; }
+        else { out[3 * n + q] = out[3 * n + q] + lambda_reg * acc_o[q]; ot[3 * n + q] = ot[3 * n + q] + lambda_reg * acc_t[q]; }
+    }
+}
+
+// ---- write back.  A node whose six update components are all exactly 0 keeps its eight floats; otherwise
+//   qo = normalize((1, om / 2)),  r' = qo * normalize(rot),  t' = (qo (t - c) + c) + tau,  dual' = 0.5 (0, t') r'
+// -- correctly rounded operations only (no sin / cos), so that the restatement is exact.
+__global__ __launch_bounds__(256) void df_sv_rigid_writeback_kernel(const float4* __restrict__ rot, const float4* __restrict__ dual,
+                                                                    const float4* __restrict__ node_t, const float4* __restrict__ c,
+                                                                    const float* __restrict__ x, int M, float* __restrict__ dq_out)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= M) return;
+    const float4 r4 = rot[n], d4 = dual[n], t4 = node_t[n], cn = c[n];
+    const float* const xt = x + 3 * (size_t)M;
+    const float ox = x[3 * n], oy = x[3 * n + 1], oz = x[3 * n + 2], tx = xt[3 * n], ty = xt[3 * n + 1], tz = xt[3 * n + 2];
+    float* o = dq_out + 8 * (size_t)n;
+    if (ox == 0.f && oy == 0.f && oz == 0.f && tx == 0.f && ty == 0.f && tz == 0.f) {
+        o[0] = r4.x; o[1] = r4.y; o[2] = r4.z; o[3] = r4.w; o[4] = d4.x; o[5] = d4.y; o[6] = d4.z; o[7] = d4.w;
+        return;
+    }
+    quat r; r.w = r4.x; r.x = r4.y; r.y = r4.z; r.z = r4.w;
+    quat qo; qo.w = 1.f; qo.x = 0.5f * ox; qo.y = 0.5f * oy; qo.z = 0.5f * oz;
+    qo = q_normalize(qo);
+    const quat r1 = q_mul(qo, q_normalize(r));
+    quat zero; zero.w = 0.f; zero.x = 0.f; zero.y = 0.f; zero.z = 0.f;
+    const f3 turned = dq_transform(qo, zero, mk3(t4.y - cn.x, t4.z - cn.y, t4.w - cn.z));
+    quat T; T.w = 0.f; T.x = (turned.x + cn.x) + tx; T.y = (turned.y + cn.y) + ty; T.z = (turned.z + cn.z) + tz;
+    const quat d = q_mul(q_scale(0.5f, T), r1);
+    o[0] = r1.w; o[1] = r1.x; o[2] = r1.y; o[3] = r1.z; o[4] = d.w; o[5] = d.x; o[6] = d.y; o[7] = d.z;
+}
+
 // ---------------------------------------------------------------- host side
 // 256-byte aligned pieces of one buffer.  A carve-up is written once and run twice: from base 0, where `at` ends as the size to
 // reserve, and from the reserved buffer's address.
@@ -709,12 +1016,16 @@ struct SvWorkspace {
     float* rho;                                             // [N] point-to-plane: n . e (otherwise empty)
     float *omega, *sw_scaled;                               // [N], [E] Tukey: point weights, sorted_w' (no Tukey: empty)
     float *alpha_scaled, *omega_e;                          // [Eg] Huber: alpha', edge weights (no Huber: empty)
+    float *y, *nw, *a; float4 *c, *qc, *rec; float* arm;    // rigid: [3N] warped points, warped normals (with normals), a_v ; [M] node
+    float *wn, *swn, *swn_scaled;                           // centres c_n, q_n ; [2N] J^T's point records ; [3Eg] edge arms ; [E] normalised
+                                                            // weights point-major, node-major, Tukey (otherwise empty; x, r, p, q: 6M floats)
     char* sort; size_t sort_bytes;
 };
 
-static int df_sv_workspace(DfWarpField* wf, int N, int k, int M, int Eg, bool plane, bool tukey, bool huber, hipStream_t st, SvWorkspace* ws)
+static int df_sv_workspace(DfWarpField* wf, int N, int k, int M, int Eg, bool plane, bool tukey, bool huber, bool rigid, hipStream_t st,
+                           SvWorkspace* ws)
 {
-    const size_t E = (size_t)N * k, n = N, m = M, eg = Eg;
+    const size_t E = (size_t)N * k, n = N, m = M, eg = Eg, mx = rigid ? 2 * m : m;
     int rc;
     if ((rc = df_sv_sort_bytes(E, 17, st, &ws->sort_bytes))) return rc;
     auto carve = [&](char* base) {
@@ -724,11 +1035,15 @@ static int df_sv_workspace(DfWarpField* wf, int N, int k, int M, int Eg, bool pl
         ws->skeys = b.take<unsigned int>(E); ws->svals = b.take<unsigned int>(E);
         ws->spt = b.take<unsigned int>(E); ws->sw = b.take<float>(E);
         ws->e0 = b.take<float>(3 * n); ws->u = b.take<float>(3 * n); ws->off = b.take<unsigned int>(m + 2);
-        ws->x = b.take<float>(3 * m); ws->r = b.take<float>(3 * m); ws->p = b.take<float>(3 * m); ws->q = b.take<float>(3 * m);
+        ws->x = b.take<float>(3 * mx); ws->r = b.take<float>(3 * mx); ws->p = b.take<float>(3 * mx); ws->q = b.take<float>(3 * mx);
         ws->scal = b.take<float>(SV_SCAL_N); ws->dq = b.take<float>(8 * m); ws->g = b.take<float>(3 * eg);
         ws->rho = b.take<float>(plane ? n : 0);
         ws->omega = b.take<float>(tukey ? n : 0); ws->sw_scaled = b.take<float>(tukey ? E : 0);
         ws->alpha_scaled = b.take<float>(huber ? eg : 0); ws->omega_e = b.take<float>(huber ? eg : 0);
+        ws->y = b.take<float>(rigid ? 3 * n : 0); ws->nw = b.take<float>(rigid && plane ? 3 * n : 0);
+        ws->a = b.take<float>(rigid ? 3 * n : 0); ws->c = b.take<float4>(rigid ? m : 0); ws->qc = b.take<float4>(rigid ? m : 0); ws->rec = b.take<float4>(rigid ? 2 * n : 0);
+        ws->arm = b.take<float>(rigid ? 3 * eg : 0); ws->wn = b.take<float>(rigid ? E : 0); ws->swn = b.take<float>(rigid ? E : 0);
+        ws->swn_scaled = b.take<float>(rigid && tukey ? E : 0);
         ws->sort = b.take<char>(ws->sort_bytes);
         return (size_t)(b.at - (uintptr_t)base);
     };
@@ -740,24 +1055,55 @@ static int df_sv_workspace(DfWarpField* wf, int N, int k, int M, int Eg, bool pl
 // Once per call, what depends only on the canonical points and the node positions: the graph (kg > 0), the k-NN, the entries' weights
 // and node ids (with e0 at the transforms the handle holds now), the node offsets and the node-major lists.  `normals` (nullable: the
 // point-to-plane solve's) only add to what makes a point invalid.
+// The node-major side of the entries, from the point-major keys / vals the setup kernel wrote: the stable sort by node id, the node
+// offsets, and the node-major copy of the point ids with the weights `w` (and, for the solve with rotations, of a second weight list).
+static int df_sv_lists(const SvWorkspace& ws, int E, int k, int M, const float* w, float* sw, const float* w2, float* sw2, hipStream_t st)
+{
+    size_t sort_bytes = ws.sort_bytes;
+    const dim3 gE((unsigned)(((size_t)E + 255) / 256));
+    DF_HIP(hipcub::DeviceRadixSort::SortPairs(ws.sort, sort_bytes, ws.keys, ws.skeys, ws.vals, ws.svals, E, 0, 17, st));   // stable
+    hipLaunchKernelGGL(df_sv_offsets_kernel, dim3((unsigned)(((size_t)E + 1 + 255) / 256)), dim3(256), 0, st, ws.skeys, E, M, ws.off);
+    DF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(df_sv_sorted_kernel, gE, dim3(256), 0, st, ws.svals, w, E, k, ws.spt, sw);
+    if (w2) hipLaunchKernelGGL(df_sv_sorted_kernel, gE, dim3(256), 0, st, ws.svals, w2, E, k, ws.spt, sw2);
+    DF_LAUNCH_CHECK();
+    return DF_OK;
+}
+
+// What a solve hands back besides the transforms it set: the energies (a call without the regularisation term reports 0 for it), the
+// last round's transforms and weights (1 everywhere for a penalty that is off).
+static int df_sv_outputs(const SvWorkspace& ws, int N, int M, int Eg, bool reg, bool tukey, bool huber, float* dq_out, float* energy, int n_energy,
+                         float* point_weights, float* edge_weights, hipStream_t st)
+{
+    if (energy) {
+        DF_HIP(hipMemcpyAsync(energy, ws.scal + SV_ENERGY, (reg ? n_energy : 2) * sizeof(float), hipMemcpyDeviceToDevice, st));
+        static const float zeros[2] = {0.f, 0.f};                       // (a copy from the host, not a fill: no kernel of any kind is added)
+        if (!reg && n_energy == 4) DF_HIP(hipMemcpyAsync(energy + 2, zeros, sizeof(zeros), hipMemcpyHostToDevice, st));
+    }
+    if (dq_out) DF_HIP(hipMemcpyAsync(dq_out, ws.dq, (size_t)M * 32, hipMemcpyDeviceToDevice, st));
+    if (point_weights) {
+        if (tukey) DF_HIP(hipMemcpyAsync(point_weights, ws.omega, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+        else DF_HIP(hipMemsetD32Async((hipDeviceptr_t)point_weights, 0x3f800000, (size_t)N, st));
+    }
+    if (edge_weights) {
+        if (huber) DF_HIP(hipMemcpyAsync(edge_weights, ws.omega_e, (size_t)Eg * 4, hipMemcpyDeviceToDevice, st));
+        else DF_HIP(hipMemsetD32Async((hipDeviceptr_t)edge_weights, 0x3f800000, (size_t)Eg, st));
+    }
+    return DF_OK;
+}
+
 static int df_sv_prepare(DfWarpField* wf, int k, const float* canonical, const float* live, const float* normals, int N, int kg,
                          const SvWorkspace& ws, dfStream stream)
 {
     hipStream_t st = (hipStream_t)stream;
     const int M = wf->M, E = N * k;
-    size_t sort_bytes = ws.sort_bytes;
     int rc;
     if (kg && (rc = df_sv_graph(wf, kg, stream))) return rc;
     if ((rc = dfusion_knn(wf, k, canonical, N, ws.idx, ws.d2, stream))) return rc;   // getWeightsAndUpdateKNN's k-NN (NaN queries are masked below)
     hipLaunchKernelGGL(normals ? df_sv_setup_kernel<true> : df_sv_setup_kernel<false>, dim3((N + 255) / 256), dim3(256), 0, st, canonical, live, normals,
                        N, k, ws.idx, ws.d2, wf->pos_sigma, wf->node_t, M, ws.w, ws.keys, ws.vals, ws.e0);
     DF_LAUNCH_CHECK();
-    DF_HIP(hipcub::DeviceRadixSort::SortPairs(ws.sort, sort_bytes, ws.keys, ws.skeys, ws.vals, ws.svals, E, 0, 17, st));   // stable
-    hipLaunchKernelGGL(df_sv_offsets_kernel, dim3((unsigned)(((size_t)E + 1 + 255) / 256)), dim3(256), 0, st, ws.skeys, E, M, ws.off);
-    DF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(df_sv_sorted_kernel, dim3((unsigned)(((size_t)E + 255) / 256)), dim3(256), 0, st, ws.svals, ws.w, E, k, ws.spt, ws.sw);
-    DF_LAUNCH_CHECK();
-    return DF_OK;
+    return df_sv_lists(ws, E, k, M, ws.w, ws.sw, nullptr, nullptr, st);
 }
 
 // The solve behind the four entry points (arguments checked and normalised by df_sv_check: kg = 0 means no regularisation).
@@ -776,7 +1122,7 @@ static int df_sv_rounds(DfWarpField* wf, int k, const float* canonical, const fl
     const float c2 = tukey_c * tukey_c, dd2 = huber_delta * huber_delta;
     SvWorkspace ws;
     int rc;
-    if ((rc = df_sv_workspace(wf, N, k, M, Eg, plane, tukey, huber, st, &ws))) return rc;
+    if ((rc = df_sv_workspace(wf, N, k, M, Eg, plane, tukey, huber, false, st, &ws))) return rc;
     if ((rc = df_sv_prepare(wf, k, canonical, live, normals, N, kg, ws, stream))) return rc;
     const float* const sw_use = tukey ? ws.sw_scaled : ws.sw;           // what W^T reads: the scaled copy, or the list as it is
     const float* const alpha_use = huber ? ws.alpha_scaled : wf->graph_alpha.p;   // the handle's cached alpha is only read
@@ -852,21 +1198,116 @@ static int df_sv_rounds(DfWarpField* wf, int k, const float* canonical, const fl
         DF_LAUNCH_CHECK();
         if ((rc = dfusion_warp_set_transforms(wf, ws.dq, stream))) return rc;   // (the handle's rot / dual / node_t are the new ones from here on)
     }
-    if (energy) {
-        DF_HIP(hipMemcpyAsync(energy, en, (reg ? n_energy : 2) * sizeof(float), hipMemcpyDeviceToDevice, st));
-        static const float zeros[2] = {0.f, 0.f};                       // (a copy from the host, not a fill: no kernel of any kind is added)
-        if (!reg && n_energy == 4) DF_HIP(hipMemcpyAsync(energy + 2, zeros, sizeof(zeros), hipMemcpyHostToDevice, st));
+    return df_sv_outputs(ws, N, M, Eg, reg, tukey, huber, dq_out, energy, n_energy, point_weights, edge_weights, st);
+}
+
+// The solve behind dfusion_warp_solve_rigid (arguments checked by df_sv_check and the entry point).  df_sv_rounds'
+// shape: one workspace, one preparation, `rounds` rounds, a term that is switched off launches nothing -- but every round starts with the
+// warp of the canonical points (and normals) at the transforms the handle holds, and the unknowns are 2M entries.
+static int df_sv_rigid_rounds(DfWarpField* wf, int k, const float* canonical, const float* live, const float* normals, int N, int iters, float lambda,
+                              float lambda_rot, int kg, float lambda_reg, int rounds, float tukey_c, float huber_delta, float* dq_out, float* energy,
+                              float* point_weights, float* edge_weights, dfStream stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const bool reg = kg > 0, tukey = tukey_c != 0.f, huber = reg && huber_delta != 0.f, plane = normals != nullptr;
+    const int M = wf->M, M2 = 2 * M, E = N * k, Eg = M * kg;
+    const float c2 = tukey_c * tukey_c, dd2 = huber_delta * huber_delta;
+    static const float ident[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
+    SvWorkspace ws;
+    int rc;
+    if ((rc = df_sv_workspace(wf, N, k, M, Eg, plane, tukey, huber, true, st, &ws))) return rc;
+    if (kg && (rc = df_sv_graph(wf, kg, stream))) return rc;           // (before alpha_use below: the first call on a handle allocates the graph)
+    const float* const sw_use = tukey ? ws.sw_scaled : ws.sw;
+    const float* const swn_use = tukey ? ws.swn_scaled : ws.swn;
+    const float* const alpha_use = huber ? ws.alpha_scaled : wf->graph_alpha.p;
+    const float* const active = ws.scal + SV_ACTIVE; float* const en = ws.scal + SV_ENERGY;
+    const dim3 gN((N + 255) / 256), gM((M + 255) / 256), gE((unsigned)(((size_t)E + 255) / 256)), gG((Eg + 255) / 256), gW(M), one(1);
+    auto step = M2 <= 2 * SV_BLOCK ? df_sv_step_reg_kernel<2, true> : M2 <= 5 * SV_BLOCK ? df_sv_step_reg_kernel<5, true> : M2 <= 8 * SV_BLOCK ? df_sv_step_reg_kernel<8, true> : df_sv_step_kernel<true>;
+    auto j_apply = plane ? (k == 8 ? df_sv_rigid_j_apply_kernel<8, true> : k == 4 ? df_sv_rigid_j_apply_kernel<4, true> : df_sv_rigid_j_apply_kernel<0, true>)
+                         : (k == 8 ? df_sv_rigid_j_apply_kernel<8, false> : k == 4 ? df_sv_rigid_j_apply_kernel<4, false> : df_sv_rigid_j_apply_kernel<0, false>);
+    // y, n' at the transforms the handle holds now: copies through the point path with an identity warp_to_live
+    auto warp = [&]() -> int {
+        DF_HIP(hipMemcpyAsync(ws.y, canonical, (size_t)N * 12, hipMemcpyDeviceToDevice, st));
+        if (plane) DF_HIP(hipMemcpyAsync(ws.nw, normals, (size_t)N * 12, hipMemcpyDeviceToDevice, st));
+        return dfusion_warp_points(wf, k, ws.y, plane ? ws.nw : nullptr, N, ident, stream);
+    };
+    // e = live - y in e0 (plane: rho = n' . e in ws.rho); with b for a round's solve: a_v too, and (plane) n' rho in u
+    auto residual = [&](bool b) {
+        hipLaunchKernelGGL(df_sv_rigid_residual_kernel, gN, dim3(256), 0, st, live, ws.y, ws.keys, ws.w, wf->node_t.p, N, k, M, ws.e0, b ? ws.a : (float*)nullptr);
+        if (plane) hipLaunchKernelGGL(df_sv_plane_rho_kernel, gN, dim3(256), 0, st, ws.e0, ws.nw, ws.keys, N, k, M, ws.rho, b ? ws.u : (float*)nullptr);
+    };
+    auto data_energy = [&](float* out) {
+        if (plane) hipLaunchKernelGGL(tukey ? df_sv_plane_energy_kernel<true> : df_sv_plane_energy_kernel<false>, one, dim3(SV_BLOCK), 0, st, ws.rho, N, c2, out);
+        else if (tukey) hipLaunchKernelGGL(df_sv_tukey_energy_kernel, one, dim3(SV_BLOCK), 0, st, ws.e0, N, c2, out);
+        else hipLaunchKernelGGL(df_sv_energy_kernel, one, dim3(SV_BLOCK), 0, st, ws.e0, N, out);
+    };
+    auto centres = [&]() { hipLaunchKernelGGL(df_sv_rigid_centre_kernel, gM, dim3(256), 0, st, wf->pos_sigma.p, wf->rot.p, wf->dual.p, wf->node_t.p, M, ws.c, ws.qc); };
+    auto edges = [&]() {
+        hipLaunchKernelGGL(df_sv_rigid_edge_kernel, gG, dim3(256), 0, st, wf->graph_nbr.p, wf->pos_sigma.p, wf->rot.p, wf->dual.p, ws.c, Eg, kg, ws.g, ws.arm);
+    };
+    auto reg_energy = [&](float* out) {                                 // (the energies weigh an edge with alpha_e itself, not alpha'_e)
+        if (huber) hipLaunchKernelGGL(df_sv_huber_energy_kernel, one, dim3(SV_BLOCK), 0, st, wf->graph_nbr.p, wf->graph_alpha.p, ws.g, (const float*)nullptr, Eg, kg, huber_delta, dd2, out);
+        else hipLaunchKernelGGL(df_sv_reg_energy_kernel, one, dim3(SV_BLOCK), 0, st, wf->graph_nbr.p, wf->graph_alpha.p, ws.g, (const float*)nullptr, Eg, kg, out);
+    };
+    // once per call: the graph, the k-NN, the first round's warp (it decides validity too), the entries, the node-major lists
+    {
+        if ((rc = dfusion_knn(wf, k, canonical, N, ws.idx, ws.d2, stream))) return rc;
+        if ((rc = warp())) return rc;
+        hipLaunchKernelGGL(df_sv_rigid_setup_kernel, gN, dim3(256), 0, st, canonical, live, normals, ws.y, ws.nw, N, k, ws.idx, ws.d2, wf->pos_sigma.p, M,
+                           ws.w, ws.wn, ws.keys, ws.vals);
+        DF_LAUNCH_CHECK();
+        if ((rc = df_sv_lists(ws, E, k, M, ws.w, ws.sw, ws.wn, ws.swn, st))) return rc;
     }
-    if (dq_out) DF_HIP(hipMemcpyAsync(dq_out, ws.dq, (size_t)M * 32, hipMemcpyDeviceToDevice, st));
-    if (point_weights) {
-        if (tukey) DF_HIP(hipMemcpyAsync(point_weights, ws.omega, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-        else DF_HIP(hipMemsetD32Async((hipDeviceptr_t)point_weights, 0x3f800000, (size_t)N, st));
+    for (int round = 0; round < rounds; ++round) {
+        const bool first = round == 0;
+        if (!first && (rc = warp())) return rc;
+        centres();
+        residual(true);
+        DF_LAUNCH_CHECK();
+        if (tukey) {
+            if (plane) hipLaunchKernelGGL(df_sv_plane_tukey_kernel, gN, dim3(256), 0, st, ws.rho, N, c2, ws.omega);
+            else hipLaunchKernelGGL(df_sv_tukey_kernel, gN, dim3(256), 0, st, ws.e0, N, c2, ws.omega);
+            hipLaunchKernelGGL(df_sv_scale_list_kernel, gE, dim3(256), 0, st, ws.spt, ws.sw, ws.omega, E, ws.sw_scaled);
+            hipLaunchKernelGGL(df_sv_scale_list_kernel, gE, dim3(256), 0, st, ws.spt, ws.swn, ws.omega, E, ws.swn_scaled);
+            DF_LAUNCH_CHECK();
+        }
+        if (energy && first) { data_energy(en); DF_LAUNCH_CHECK(); }
+        // r0 = J^T Omega b - lambda_reg * acc(g) ; p0 = r0 ; x0 = 0
+        hipLaunchKernelGGL(df_sv_rigid_pack_kernel, gN, dim3(256), 0, st, plane ? ws.u : ws.e0, ws.a, N, ws.rec);
+        hipLaunchKernelGGL(df_sv_rigid_jt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, sw_use, swn_use, M, ws.rec, ws.qc, 0.f, 0.f,
+                           (const float*)nullptr, ws.r, (const float*)nullptr);
+        DF_LAUNCH_CHECK();
+        if (reg) {
+            edges();
+            if (huber) hipLaunchKernelGGL(df_sv_huber_kernel, gG, dim3(256), 0, st, ws.g, wf->graph_alpha.p, Eg, huber_delta, dd2, ws.omega_e, ws.alpha_scaled);
+            hipLaunchKernelGGL(df_sv_rigid_reg_kernel<true>, gM, dim3(256), 0, st, wf->graph_nbr.p, alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg, ws.g,
+                               ws.arm, (const float*)nullptr, lambda_reg, ws.r, (const float*)nullptr);
+            if (energy && first) reg_energy(en + 2);
+            DF_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(df_sv_init_kernel<true>, one, dim3(SV_BLOCK), 0, st, ws.r, M2, ws.x, ws.p, ws.scal);
+        DF_LAUNCH_CHECK();
+        for (int it = 0; it < iters; ++it) {
+            hipLaunchKernelGGL(j_apply, gN, dim3(256), 0, st, ws.w, ws.wn, ws.keys, N, k, M, ws.p, ws.a, ws.qc, ws.rec, active, ws.nw);
+            hipLaunchKernelGGL(df_sv_rigid_jt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, sw_use, swn_use, M, ws.rec, ws.qc, lambda, lambda_rot, ws.p, ws.q,
+                               active);
+            if (reg) hipLaunchKernelGGL(df_sv_rigid_reg_kernel<false>, gM, dim3(256), 0, st, wf->graph_nbr.p, alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg,
+                                        ws.g, ws.arm, ws.p, lambda_reg, ws.q, active);
+            hipLaunchKernelGGL(step, one, dim3(SV_BLOCK), 0, st, ws.q, M2, ws.x, ws.r, ws.p, ws.scal);
+            DF_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(df_sv_rigid_writeback_kernel, gM, dim3(256), 0, st, wf->rot.p, wf->dual.p, wf->node_t.p, ws.c, ws.x, M, ws.dq);
+        DF_LAUNCH_CHECK();
+        if ((rc = dfusion_warp_set_transforms(wf, ws.dq, stream))) return rc;   // (the handle's rot / dual / node_t are the new ones from here on)
     }
-    if (edge_weights) {
-        if (huber) DF_HIP(hipMemcpyAsync(edge_weights, ws.omega_e, (size_t)Eg * 4, hipMemcpyDeviceToDevice, st));
-        else DF_HIP(hipMemsetD32Async((hipDeviceptr_t)edge_weights, 0x3f800000, (size_t)Eg, st));
+    if (energy) {                                                       // the true energies behind the last write-back
+        if ((rc = warp())) return rc;
+        residual(false);
+        data_energy(en + 1);
+        if (reg) { centres(); edges(); reg_energy(en + 3); }
+        DF_LAUNCH_CHECK();
     }
-    return DF_OK;
+    return df_sv_outputs(ws, N, M, Eg, reg, tukey, huber, dq_out, energy, 4, point_weights, edge_weights, st);
 }
 
 // The arguments the three entry points share.  DF_OK, with *kg = 0 where the regularisation is switched off (kg == 0 or
@@ -914,6 +1355,16 @@ extern "C" int dfusion_warp_solve_plane(DfWarpField* wf, int k, const float* can
     if (rounds < 1 || !(tukey_c >= 0.f) || !(huber_delta >= 0.f) || (edge_weights && kg == 0)) return DF_E_INVALID;
     return df_sv_rounds(wf, k, canonical, live, normals, N, iters, lambda, kg, lambda_reg, rounds, tukey_c, huber_delta, dq_out, energy, 4,
                         point_weights, edge_weights, stream);
+}
+
+extern "C" int dfusion_warp_solve_rigid(DfWarpField* wf, int k, const float* canonical, const float* live, const float* normals, int N, int iters,
+                                        float lambda, float lambda_rot, int kg, float lambda_reg, int rounds, float tukey_c, float huber_delta,
+                                        float* dq_out, float* energy, float* point_weights, float* edge_weights, dfStream stream)
+{
+    if (df_sv_check(wf, k, canonical, live, N, iters, lambda, &kg, lambda_reg) || !(lambda_rot >= 0.f)) return DF_E_INVALID;
+    if (rounds < 1 || !(tukey_c >= 0.f) || !(huber_delta >= 0.f) || (edge_weights && kg == 0)) return DF_E_INVALID;
+    return df_sv_rigid_rounds(wf, k, canonical, live, normals, N, iters, lambda, lambda_rot, kg, lambda_reg, rounds, tukey_c, huber_delta, dq_out, energy,
+                              point_weights, edge_weights, stream);
 }
 
 extern "C" int dfusion_warp_node_graph(DfWarpField* wf, int kg, int* nbr, float* alpha, dfStream stream)

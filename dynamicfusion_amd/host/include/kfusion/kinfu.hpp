@@ -57,6 +57,9 @@ namespace kfusion
         float warp_huber_delta = 0.f;        // and the Huber threshold of the graph edges (0 = quadratic regularisation); default: off
         bool warp_point_to_plane = false;    // device-resident dynamicfusion(): the warp solve's data term along the warped model normals
                                              // (WarpField::setPointToPlane) instead of point-to-point; default off = the reference's energy
+        bool warp_solve_rotations = false;   // device-resident dynamicfusion(): the node ROTATIONS are unknowns of the warp solve too
+        float warp_rot_lambda = 0.f;         // (WarpField::setNodeRotations, with this damping of the rotations); the solve then gets copies of
+                                             // the canonical points and normals from before the first warp; default off = the launches of before
         bool warp_projective_association = false;   // device-resident dynamicfusion(): pair every warped point with the live sample at the
                                              // pixel it projects to (cuda::associateProjective) instead of by pixel index; default off =
                                              // the reference's pairing
@@ -126,7 +129,7 @@ namespace kfusion
         const cuda::Image* frame_image_ = nullptr;                          // operator()'s image while the frame runs
         // scratch of the device-resident dynamicfusion()
         cuda::Cloud df_cloud_; cuda::Normals df_normals_;
-        cuda::DeviceArray<float> df_points3_, df_normals3_, df_live3_, df_assoc3_, df_plane_normals3_;
+        cuda::DeviceArray<float> df_points3_, df_normals3_, df_live3_, df_assoc3_, df_plane_normals3_, df_unwarped_points3_, df_unwarped_normals3_;
         cuda::DeviceArray<unsigned long long> df_assoc_counts_; bool df_assoc_valid_ = false;
         cuda::DeviceArray<Point> df_warped4_;
         cuda::Normals df_live_normals_;

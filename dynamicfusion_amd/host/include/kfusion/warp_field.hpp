@@ -98,6 +98,11 @@ namespace kfusion
         /// normal given with the point, used as it is, so that a live point that slid along the surface does not move the nodes.  It needs
         /// an energy_data that is given normals; the overload without them keeps the point-to-point term.  Off by default.
         void setPointToPlane(bool on) { point_to_plane_ = on; }
+        /// The node ROTATIONS as unknowns of energy_data too (dfusion_warp_solve_rigid): Gauss-Newton rounds (setRobust's `rounds`) on a
+        /// rotation and a translation per node against the warp that warp() applies, `lambda_rot` damping the rotations as
+        /// setSolverDamping damps the translations.  The canonical points (and normals) must then be the UNWARPED ones: the solve warps
+        /// them itself.  With setPointToPlane and normals the residual is taken along the warped normal.  Off by default.
+        void setNodeRotations(bool on, float lambda_rot = 0.f) { node_rotations_ = on; rot_lambda_ = lambda_rot; }
         /// E_reg before / after the last regularised energy_data (with setTrackEnergy; 0 while the term is off)
         float lastRegEnergyBefore() const { return last_energy_[2]; }
         float lastRegEnergyAfter() const { return last_energy_[3]; }
@@ -155,6 +160,7 @@ namespace kfusion
         int robust_rounds_ = 1;
         float tukey_c_ = 0.f, huber_delta_ = 0.f;
         bool point_to_plane_ = false;
+        bool node_rotations_ = false; float rot_lambda_ = 0.f;
         float last_energy_[4] = {0.f, 0.f, 0.f, 0.f};
         bool track_energy_ = false;
     };

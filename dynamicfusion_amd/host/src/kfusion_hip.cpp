@@ -622,7 +622,12 @@ void WarpField::energy_data(const cuda::DeviceArray<float>& canonical_vertices, 
     if (!M || n <= 0) return;
     solve_dq_.create(M * 8); solve_energy_.create(4);      // no-ops after the first frame
     const bool reg = reg_neighbours_ != 0 && reg_lambda_ != 0.f;
-    if (point_to_plane_ && canonical_normals.size() >= (size_t)3 * n)   // the data term along the normals (setPointToPlane)
+    const bool with_normals = point_to_plane_ && canonical_normals.size() >= (size_t)3 * n;
+    if (node_rotations_)                                   // rotations as unknowns too, against the warp itself (setNodeRotations)
+        KF_DF(dfusion_warp_solve_rigid(handle_, k_, canonical_vertices.ptr(), live_vertices.ptr(), with_normals ? canonical_normals.ptr() : nullptr, n,
+                                       solver_iters_, solver_lambda_, rot_lambda_, reg ? reg_neighbours_ : 0, reg ? reg_lambda_ : 0.f, robust_rounds_,
+                                       tukey_c_, huber_delta_, solve_dq_.ptr(), track_energy_ ? solve_energy_.ptr() : nullptr, nullptr, nullptr, nullptr));
+    else if (with_normals)                                 // the data term along the normals (setPointToPlane)
         KF_DF(dfusion_warp_solve_plane(handle_, k_, canonical_vertices.ptr(), live_vertices.ptr(), canonical_normals.ptr(), n, solver_iters_,
                                        solver_lambda_, reg ? reg_neighbours_ : 0, reg ? reg_lambda_ : 0.f, robust_rounds_, tukey_c_, huber_delta_,
                                        solve_dq_.ptr(), track_energy_ ? solve_energy_.ptr() : nullptr, nullptr, nullptr, nullptr));
@@ -1224,6 +1229,17 @@ void KinFu::dynamicfusion(cuda::Depth& depth, cuda::Cloud live_frame, cuda::Norm
                                        depth.cols(), depth.rows(), inv12, nullptr));
         KF_DF(dfusion_transform_points((const float*)df_normals_.ptr(), df_normals_.step(), 4, df_normals3_.ptr(), (size_t)depth.cols() * 12, 3,
                                        depth.cols(), depth.rows(), nullptr, nullptr));
+        const bool rotations = params_.warp_solve_rotations && params_.warp_solver_iterations > 0;
+        if (rotations) {
+            // the solve with node rotations warps the model points itself: it gets the canonical points, and the normals taken into the
+            // points' frame (rotation only, as for warp_point_to_plane below), as they are BEFORE the first warp, which works in place
+            if (df_unwarped_points3_.size() < 3 * n) { df_unwarped_points3_.create(3 * n); df_unwarped_normals3_.create(3 * n); }
+            float rot12[12]; std::memcpy(rot12, inv12, sizeof(rot12)); rot12[9] = rot12[10] = rot12[11] = 0.f;
+            KF_DF(dfusion_transform_points(df_points3_.ptr(), 3 * n * sizeof(float), 3, df_unwarped_points3_.ptr(), 3 * n * sizeof(float), 3, (int)n, 1,
+                                           nullptr, nullptr));
+            KF_DF(dfusion_transform_points(df_normals3_.ptr(), 3 * n * sizeof(float), 3, df_unwarped_normals3_.ptr(), 3 * n * sizeof(float), 3, (int)n, 1,
+                                           rot12, nullptr));
+        }
         warp_->warp(df_points3_, df_normals3_, (int)n);                      // :387
         if (params_.warp_solver_iterations > 0) {                           // :389 optimiser_->optimiseWarpData(canonical, normals, live, normals)
             if (df_live3_.size() < 3 * n) df_live3_.create(3 * n);
@@ -1249,7 +1265,11 @@ void KinFu::dynamicfusion(cuda::Depth& depth, cuda::Cloud live_frame, cuda::Norm
             warp_->setRegularisation(params_.warp_reg_neighbours, params_.warp_reg_lambda);
             warp_->setRobust(params_.warp_robust_rounds, params_.warp_tukey_c, params_.warp_huber_delta);
             warp_->setPointToPlane(params_.warp_point_to_plane);
-            if (params_.warp_point_to_plane) {
+            warp_->setNodeRotations(rotations, params_.warp_rot_lambda);
+            if (rotations) {                                                 // (the association above still paired the WARPED points)
+                if (params_.warp_point_to_plane) warp_->energy_data(df_unwarped_points3_, df_live3_, df_unwarped_normals3_, (int)n);
+                else warp_->energy_data(df_unwarped_points3_, df_live3_, (int)n);
+            } else if (params_.warp_point_to_plane) {
                 // df_normals3_ holds the ray-cast's normals re-strided as they came (the camera's frame) and warped, while df_points3_ and
                 // df_live3_ are inverse_pose * the camera's frame: the solve gets a copy in the points' frame, rotation only (df_normals3_
                 // itself goes on into the second warp as it is)

@@ -243,6 +243,35 @@ class WarpField:
             return dq, en, pw, ew
         return dq, en
 
+    def solve_rigid(self, canonical_dev, live_dev, normals_dev=None, iters=100, lam=0.0, lam_rot=0.0, reg_neighbours=0, reg_lambda=0.0, rounds=1,
+                    tukey_c=0.0, huber_delta=0.0, k=None, return_weights=False):
+        """The solve with the node rotations as unknowns too (include/dfusion.h dfusion_warp_solve_rigid): `rounds` Gauss-Newton rounds
+        against the DQB warp that warp() and the warped integrate apply, six unknowns a node, `lam_rot` damping the rotations as `lam`
+        damps the translations.  `canonical_dev` and `normals_dev` are the UNWARPED model points and normals (the solve warps them
+        itself); normals_dev None: the point-to-point data term, otherwise the residual along the warped normal.  Returns what
+        solve_robust returns; the data energy `after` is that of the warp at the transforms written, not of the linearisation."""
+        k = self.k if k is None else k
+        n = int(canonical_dev.shape[0])
+        if normals_dev is not None and int(normals_dev.numel()) != 3 * n:
+            raise ValueError("one normal per point expected (%d points, normals of shape %s)" % (n, tuple(normals_dev.shape)))
+        kg = int(reg_neighbours)
+        dq = torch.empty((self.M, 8), dtype=torch.float32, device=self.device)
+        en = torch.zeros(4, dtype=torch.float32, device=self.device)
+        pw = ew = None
+        if return_weights:
+            pw = torch.empty(n, dtype=torch.float32, device=self.device)
+            if kg > 0 and float(reg_lambda) != 0.0:
+                ew = torch.empty((self.M, kg), dtype=torch.float32, device=self.device)
+        capi.check(capi.lib().dfusion_warp_solve_rigid(self.handle, k, _flat(canonical_dev), _flat(live_dev),
+                                                       _flat(normals_dev) if normals_dev is not None else None, n, int(iters), float(lam),
+                                                       float(lam_rot), kg, float(reg_lambda), int(rounds), float(tukey_c), float(huber_delta),
+                                                       _ptr(dq), _ptr(en), _ptr(pw) if pw is not None else None,
+                                                       _ptr(ew) if ew is not None else None, _stream()), "dfusion_warp_solve_rigid")
+        self._dq = dq
+        if return_weights:
+            return dq, en, pw, ew
+        return dq, en
+
     def node_graph(self, kg):
         """The graph solve() regularises over: (nbr int32 [M, kg], alpha float32 [M, kg]) device tensors -- node i's kg nearest other
         nodes and the edge weights max(dg_w_i, dg_w_j)."""

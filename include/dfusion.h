@@ -496,6 +496,39 @@ int dfusion_warp_solve_robust(DfWarpField *wf, int k, const float *canonical_dev
 int dfusion_warp_solve_plane(DfWarpField *wf, int k, const float *canonical_dev, const float *live_dev, const float *normals_dev, int N,
                              int iters, float lambda, int kg, float lambda_reg, int rounds, float tukey_c, float huber_delta,
                              float *dq_out_dev, float *energy_dev, float *point_weights_dev, float *edge_weights_dev, dfStream stream);
+/* The warp solve with the node ROTATIONS as unknowns too, against the warp the rest of the pipeline applies (DynamicFusion section 3.3:
+ * SE(3) per node) -- an addition to ABI 7.  With y_v = DQB(canonical_v).transform(canonical_v) and n'_v the normal as
+ * dfusion_warp_points warps them at the transforms the handle holds (identity warp_to_live), c_n = T_n(pos_n):
+ *     E = sum_v Omega_v |n'_v . (live_v - y_v)|^2 + lambda_reg sum_e alpha_e |T_i v_j - T_j v_j|^2
+ * (normals_dev == NULL: the full 3-vector residual).  `rounds` Gauss-Newton rounds, each re-linearised at the transforms the one before
+ * wrote, each `iters` conjugate-gradient steps on six unknowns a node (omega_n, a rotation about c_n, and tau_n), ONE recurrence over
+ * the 3-component array of 2M entries (omega_n at n, tau_n at M + n).  f32, no contraction, sums in slot / list / edge order:
+ *   once per call   k-NN of canonical; w_vi = exp(-d2 / 2 sigma^2), S_v = ((w_0 + w_1) + ...), wn_vi = w_vi / S_v.  A point is skipped
+ *                   when canonical or live has a NaN, S_v == 0, a normal component is NaN or infinite, or a component of y_v or n'_v
+ *                   of the FIRST round is.  Node-major lists and the graph as in dfusion_warp_solve.
+ *   per round       e_v = live_v - y_v, rho_v = (n'x ex + n'y ey) + n'z ez; T_v = sum_i w_vi t_i, a_v = y_v - T_v; q_n = c_n - t_n; per edge
+ *                   e = (i -> j): g_e = T_i v_j - c_j, b_e = T_i v_j - c_i; Tukey on rho^2 (or |e|^2) and Huber on g as in
+ *                   dfusion_warp_solve_robust.
+ *   J p             the blend turns a point by the normalised sum of the weighted node rotations and adds the node translations under
+ *                   the UNNORMALISED weights, so per point: st = st + w (p_tau_n - (p_om_n x q_n)), sr = sr + wn p_om_n over the slots,
+ *                   u = st + (sr x a_v); with normals u = n' (n' . u)
+ *   J^T u           per node over its list: S1 = sum w u, S2 = sum wn (a_v x u); tau = S1 + lambda p_tau,
+ *                   om = (S2 - (q_n x S1)) + lambda_rot p_om
+ *   regularisation  d_e = (p_tau_i + (p_om_i x b_e)) - p_tau_j; tau_n: + alpha_e d_e over the outgoing edges in slot order, then
+ *                   - alpha_e d_e over the incoming edges in ascending edge id; om_n: + alpha_e (b_e x d_e) over the outgoing edges.
+ *                   Right-hand side: the same with d_e = g_e, r0 = J^T Omega b - lambda_reg acc.
+ *   write-back      a node whose six components are all exactly 0 keeps its eight floats; otherwise qo = normalize((1, om / 2)),
+ *                   r' = qo * normalize(rot), t' = (qo (t - c) + c) + tau, dual' = 0.5 (0, t') r'.
+ *   energy_dev      E_data before (the first round's) and after (one more warp behind the last write-back: the true energy, not the
+ *                   linearised one), E_reg = sum_e alpha_e |g_e|^2 (Huber: psi) before and after.
+ * lambda_rot damps rotations that few or badly placed points determine.  point_weights_dev, edge_weights_dev, dq_out_dev: as in
+ * dfusion_warp_solve_robust.  canonical_dev and normals_dev are the UNWARPED model points and normals.  Restated in
+ * tests/solver_rigid_ref.py.
+ * DF_E_INVALID: what dfusion_warp_solve_robust refuses, lambda_rot negative or NaN.                                                       */
+int dfusion_warp_solve_rigid(DfWarpField *wf, int k, const float *canonical_dev, const float *live_dev, const float *normals_dev, int N,
+                             int iters, float lambda, float lambda_rot, int kg, float lambda_reg, int rounds, float tukey_c,
+                             float huber_delta, float *dq_out_dev, float *energy_dev, float *point_weights_dev, float *edge_weights_dev,
+                             dfStream stream);
 /* The node graph dfusion_warp_solve uses for `kg` (1..7, M >= kg + 1; built now if the handle does not hold it):
  * nbr_dev[M*kg] int32 the head node of every edge, alpha_dev[M*kg] (nullable) the edge weights.                                      */
 int dfusion_warp_node_graph(DfWarpField *wf, int kg, int *nbr_dev, float *alpha_dev, dfStream stream);
