@@ -14,7 +14,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libdfusion_hip.so")
 
 SOURCES = ["dfusion_volume.hip", "dfusion_warp.hip", "dfusion_warp_nodes.hip", "dfusion_warp_points.hip", "dfusion_warp_index.hip",
-           "dfusion_raycast.hip", "dfusion_frontend.hip", "dfusion_solver.hip", "dfusion_selftest.hip", "dfusion_warp_extend.hip", "dfusion_mesh.hip", "dfusion_associate.hip", "dfusion_color.hip"]
+           "dfusion_raycast.hip", "dfusion_frontend.hip", "dfusion_solver.hip", "dfusion_selftest.hip", "dfusion_warp_extend.hip", "dfusion_mesh.hip", "dfusion_associate.hip", "dfusion_color.hip", "dfusion_render.hip"]
 HEADERS = ["dfusion_device.h", "dfusion_internal.h", "dfusion_nanoflann.h", "dfusion_pyramid.h", "dfusion_warp_topk.h", "dfusion_warp_sweep.h",
            "dfusion_warp_blocks.h", "dfusion_warp_pipe.h", "dfusion_plan_halves.h", os.path.join(REPO_DIR, "include", "dfusion.h")]
 
@@ -64,6 +64,7 @@ def kernel_source_sha(kernel):
          else "dfusion_mesh.hip" if k.startswith("df_mesh")
          else "dfusion_associate.hip" if k.startswith("df_assoc")
          else "dfusion_color.hip" if k.startswith("df_color")
+         else "dfusion_render.hip" if k.startswith("df_render")
          else "dfusion_volume.hip")
     h = hashlib.sha256()
     for name in _csrc_includes(f, []):
@@ -96,6 +97,7 @@ HOST_ASSOCIATE = os.path.join(HOST_DIR, "associate")
 HOST_PLANE_SOLVE = os.path.join(HOST_DIR, "plane_solve")
 HOST_COLOR_FRAME = os.path.join(HOST_DIR, "color_frame")
 HOST_RIGID_SOLVE = os.path.join(HOST_DIR, "rigid_solve")
+HOST_RENDER_MESH = os.path.join(HOST_DIR, "render_mesh")
 HOST_ZSLAB_LIB = os.path.join(HOST_DIR, "libkfusion_zslab.so")       # kfusion::cuda::ZSlabComm: the RCCL side of the Z-slab sharding
 HOST_ZSLAB_APP = os.path.join(HOST_DIR, "zslab_frame")
 
@@ -116,8 +118,9 @@ def build_host(force=False, verbose=False):
     app9 = os.path.join(HOST_DIR, "apps", "plane_solve.cpp")
     app10 = os.path.join(HOST_DIR, "apps", "color_frame.cpp")
     app11 = os.path.join(HOST_DIR, "apps", "rigid_solve.cpp")
-    deps = [src, app, app2, app3, app4, zsrc, app5, app6, app7, app8, app9, app10, app11, LIB_PATH] + [os.path.join(r, f) for r, _, fs in os.walk(os.path.join(HOST_DIR, "include")) for f in fs]
-    outs = (HOST_LIB, HOST_APP, HOST_KINFU_APP, HOST_WARP_TESTS, HOST_DEMO_CALLS, HOST_ZSLAB_LIB, HOST_ZSLAB_APP, HOST_REG_SOLVE, HOST_ROBUST_SOLVE, HOST_ASSOCIATE, HOST_PLANE_SOLVE, HOST_COLOR_FRAME, HOST_RIGID_SOLVE)
+    app12 = os.path.join(HOST_DIR, "apps", "render_mesh.cpp")
+    deps = [src, app, app2, app3, app4, zsrc, app5, app6, app7, app8, app9, app10, app11, app12, LIB_PATH] + [os.path.join(r, f) for r, _, fs in os.walk(os.path.join(HOST_DIR, "include")) for f in fs]
+    outs = (HOST_LIB, HOST_APP, HOST_KINFU_APP, HOST_WARP_TESTS, HOST_DEMO_CALLS, HOST_ZSLAB_LIB, HOST_ZSLAB_APP, HOST_REG_SOLVE, HOST_ROBUST_SOLVE, HOST_ASSOCIATE, HOST_PLANE_SOLVE, HOST_COLOR_FRAME, HOST_RIGID_SOLVE, HOST_RENDER_MESH)
     if not force and all(os.path.exists(f) for f in outs) and min(os.path.getmtime(f) for f in outs) >= max(os.path.getmtime(d) for d in deps):
         return HOST_LIB, HOST_APP
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
@@ -135,6 +138,7 @@ def build_host(force=False, verbose=False):
             common + [app9, "-o", HOST_PLANE_SOLVE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + [app10, "-o", HOST_COLOR_FRAME, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + [app11, "-o", HOST_RIGID_SOLVE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
+            common + [app12, "-o", HOST_RENDER_MESH, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + ["-fPIC", "-shared", zsrc, "-o", HOST_ZSLAB_LIB, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-lrccl", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
             common + [app5, "-o", HOST_ZSLAB_APP, "-L", HOST_DIR, "-lkfusion_zslab", "-lkfusion_hip"] + link + ["-lrccl", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."]]
     for c in cmds:

@@ -63,7 +63,7 @@ SYMBOLS = [
     "dfusion_render_image_points", "dfusion_render_image_depth", "dfusion_render_tangent_colors", "dfusion_cloud_to_depth",
     "dfusion_warp_extend", "dfusion_warp_solve", "dfusion_warp_node_graph", "dfusion_extract_mesh",
     "dfusion_warp_solve_robust", "dfusion_associate_projective", "dfusion_warp_solve_plane",
-    "dfusion_color_clear", "dfusion_color_integrate", "dfusion_color_fetch", "dfusion_warp_solve_rigid",
+    "dfusion_color_clear", "dfusion_color_integrate", "dfusion_color_fetch", "dfusion_warp_solve_rigid", "dfusion_render_mesh",
 ]
 
 
@@ -159,6 +159,8 @@ def load(path, strict=True):
                                            C.c_float, vp, vp, vp, vp, vp]
     L.dfusion_associate_projective.argtypes = [vp, vp, C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, fp, C.c_float, C.c_float, C.c_float,
                                                vp, vp, vp, vp]
+    L.dfusion_render_mesh.argtypes = [vp, C.c_ulonglong, vp, C.c_ulonglong, fp, vp, vp, vp, C.c_int, C.c_int, fp, C.c_int, vp, C.c_size_t, vp, C.c_size_t,
+                                      vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
     L.dfusion_warp_extend.argtypes = [vp, C.c_int, vp, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp, C.POINTER(C.c_int),
                                       C.POINTER(C.c_int), vp]
     L.dfusion_warp_index_info.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint), C.POINTER(C.c_int)]

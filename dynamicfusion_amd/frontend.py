@@ -181,6 +181,76 @@ def associateProjective(intr, points, normals, live_points, live_normals, dist_t
     return out[0] if len(out) == 1 else out
 
 
+def renderMesh(intr, vertices, triangles, cols, rows, world2cam=None, normals=None, attr=None, colors=None, max_extent=16,
+               return_tri=False, return_counts=False):
+    """A z-buffered rasteriser (include/dfusion.h dfusion_render_mesh): the mesh `vertices` (float32 [V, 4]) / `triangles` (int32 [T, 3],
+    uint32 bits) -- fetchMesh's, or its vertices after WarpField.warp -- seen by the camera `intr` of cols x rows pixels.  world2cam: a
+    4x4 pose or 12 floats, None = the vertices are in the camera frame.  Per-vertex normals / attr (float32 [V, 4]) and colors
+    (uint8 [V, 4]) are interpolated as given (no rotation).  -> (points, normals, attr, colors): float32 [rows, cols, 4] images and a
+    uint8 [rows, cols, 4] one, None where the input is; a miss is all-NaN (0x7fffffff) / four 0 bytes.  Then, if asked for, tri
+    (int32 [rows, cols], -1 = miss) and counts (int64 [6]: triangles drawn / invalid / degenerate / stretched / off-screen, covered
+    pixels).  Device tensors; nothing synchronises."""
+    def per_vertex(t, dtype, name):
+        if t is None:
+            return None
+        if t.dtype != dtype or tuple(t.shape) != (nv, 4):
+            raise ValueError("%s %s %s, expected %s [%d, 4]" % (name, t.dtype, tuple(t.shape), dtype, nv))
+        return _flat(t) if nv else None
+
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 4:
+        raise ValueError("vertices %s %s, expected float32 [V, 4]" % (vertices.dtype, tuple(vertices.shape)))
+    if triangles.dtype != torch.int32 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise ValueError("triangles %s %s, expected int32 [T, 3]" % (triangles.dtype, tuple(triangles.shape)))
+    nv, nt = int(vertices.shape[0]), int(triangles.shape[0])
+    cols, rows = int(cols), int(rows)
+    if cols <= 0 or rows <= 0:
+        raise ValueError("image of %d x %d pixels" % (cols, rows))
+    dev = vertices.device
+    if world2cam is not None:
+        w = np.asarray(world2cam, np.float32)
+        world2cam = capi.floats(aff12(w) if w.shape == (4, 4) else w.reshape(12))
+    points = _new_image4(rows, cols, dev)
+    out_n = _new_image4(rows, cols, dev) if normals is not None else None
+    out_a = _new_image4(rows, cols, dev) if attr is not None else None
+    out_c = torch.empty((rows, cols, 4), dtype=torch.uint8, device=dev) if colors is not None else None
+    tri = torch.empty((rows, cols), dtype=torch.int32, device=dev) if return_tri else None
+    counts = torch.empty(6, dtype=torch.int64, device=dev) if return_counts else None
+    capi.check(capi.lib().dfusion_render_mesh(
+        _flat(vertices) if nv else None, nv, _flat(triangles) if nt else None, nt, world2cam, per_vertex(normals, torch.float32, "normals"),
+        per_vertex(attr, torch.float32, "attr"), per_vertex(colors, torch.uint8, "colors"), cols, rows, intr.as_proj(), int(max_extent),
+        _ptr(points), cols * 16, _ptr(out_n) if out_n is not None and nv else None, cols * 16, _ptr(out_a) if out_a is not None and nv else None,
+        cols * 16, _ptr(out_c) if out_c is not None and nv else None, cols * 4, _ptr(tri) if return_tri else None, cols * 4,
+        _ptr(counts) if return_counts else None, _stream()), "dfusion_render_mesh")
+    if not nv:                                          # (no per-vertex array has an address: the images are all misses)
+        for t in (out_n, out_a):
+            if t is not None:
+                t.copy_(points)
+        if out_c is not None:
+            out_c.zero_()
+    out = (points, out_n, out_a, out_c) + ((tri,) if return_tri else ()) + ((counts,) if return_counts else ())
+    return out
+
+
+def renderLiveModel(volume, warp_field, camera_pose, intr, cols, rows, color_volume=None, k=None):
+    """The prediction of the live frame: the canonical mesh of `volume` (fetchMesh with normals), coloured by `color_volume`
+    (fetchColors at the canonical vertices; None: no colour image), warped by `warp_field` (copies of the vertices and normals, k
+    nearest nodes, default warp_field.k) and rendered into the camera at `camera_pose` (inverted in f64), with the canonical vertices
+    as the attribute.  -> (points, normals, canonical points, colours) images as renderMesh gives them; the normals stay in the frame
+    the warp leaves them in."""
+    vertices, triangles, normals = volume.fetchMesh(with_normals=True)
+    colors = color_volume.fetchColors(vertices) if color_volume is not None else None
+    nv = int(vertices.shape[0])
+    p3, n3 = vertices[:, :3].contiguous(), normals[:, :3].contiguous()
+    if nv:
+        warp_field.warp(p3, n3, k)
+    warped = torch.zeros((nv, 4), dtype=torch.float32, device=vertices.device)
+    wnormals = torch.zeros((nv, 4), dtype=torch.float32, device=vertices.device)
+    warped[:, :3] = p3
+    wnormals[:, :3] = n3
+    world2cam = np.linalg.inv(np.asarray(camera_pose, np.float64).reshape(4, 4)).astype(np.float32)
+    return renderMesh(intr, warped, triangles, cols, rows, world2cam=world2cam, normals=wnormals, attr=vertices, colors=colors)
+
+
 def unpack_icp_sums(sums):
     """StreamHelper::get (projective_icp.cpp:43-61): 27 floats -> symmetric A (6x6) and b (6)."""
     A = np.zeros((6, 6), F32)

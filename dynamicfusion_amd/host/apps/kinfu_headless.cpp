@@ -5,10 +5,13 @@
 //   warp data-term solve; depth: the reference's USE_DEPTH build -- depth pyramids and masked-depth ICP; assoc: projective data
 //   association in front of the warp solve, KinFuParams::warp_projective_association -- under trace its counts are printed per frame;
 //   plane: the warp solve's point-to-plane data term, KinFuParams::warp_point_to_plane; rigid: the node rotations as unknowns of the warp
-//   solve, KinFuParams::warp_solve_rotations with warp_rot_lambda = 1e-3 and 4 graph neighbours at weight 1)
+//   solve, KinFuParams::warp_solve_rotations with warp_rot_lambda = 1e-3 and 4 graph neighbours at weight 1; renderlive: after the
+//   last frame KinFu::renderLive, and what a caller needs to repeat it appended to out.bin)
 // in.bin : intrinsics fx fy cx cy f32[4], then per frame depth u16[rows*cols] (mm).
 // out.bin: per frame { tracked i32 (operator()'s return value), pose f32[12] (R row-major, t) }, then the extracted surface
-//          count u64 and the volume u32[dims^3].
+//          count u64 and the volume u32[dims^3].  renderlive: then i32[2] M, k; per node pos f32[3], dq f32[8], dg_w f32; world2cam
+//          f32[12] (the last pose, inverted); warp_to_live f32[12]; light pose f32[3]; the live model's point, normal and canonical-point
+//          images f32[rows * cols * 4] each; the shaded image u8[rows * cols * 4].
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -89,6 +92,25 @@ int main(int argc, char** argv)
     std::vector<unsigned int> vol((size_t)dims * dims * dims);
     kinfu.tsdf().data().download(vol.data());
     std::fwrite(vol.data(), 4, vol.size(), out);
+    if (mode.find("renderlive") != std::string::npos) {
+        cuda::Image image;
+        kinfu.renderLive(image);
+        cuda::waitAllDefaultStream();
+        const std::vector<deformation_node>& nodes = *kinfu.getWarp().getNodes();
+        const int hd[2] = {(int)nodes.size(), kinfu.getWarp().k()};
+        std::fwrite(hd, 4, 2, out);
+        for (const deformation_node& n : nodes) { std::fwrite(n.vertex.val, 4, 3, out); std::fwrite(n.transform.raw(), 4, 8, out); std::fwrite(&n.weight, 4, 1, out); }
+        float a12[12];
+        affine_to_aff12(kinfu.getCameraPose().inv(), a12); std::fwrite(a12, 4, 12, out);
+        affine_to_aff12(kinfu.getWarp().getWarpToLive(), a12); std::fwrite(a12, 4, 12, out);
+        std::fwrite(p.light_pose.val, 4, 3, out);
+        std::vector<char> h((size_t)rows * cols * 16);
+        const cuda::RenderMeshOutputs& m = kinfu.liveModel();
+        m.points.download(h.data(), (size_t)cols * 16); std::fwrite(h.data(), 1, h.size(), out);
+        m.normals.download(h.data(), (size_t)cols * 16); std::fwrite(h.data(), 1, h.size(), out);
+        m.attr.download(h.data(), (size_t)cols * 16); std::fwrite(h.data(), 1, h.size(), out);
+        image.download(h.data(), (size_t)cols * 4); std::fwrite(h.data(), 1, (size_t)rows * cols * 4, out);
+    }
     std::fclose(out);
     std::printf("kinfu_headless ok: %d frames, %zu warp nodes, %llu surface points, %.3f ms/frame (KinFu::operator(), frames 2.., wall clock)\n",
                 frames, kinfu.getWarp().getNodes()->size(), cnt, timed ? total_ms / timed : 0.0);

@@ -12,6 +12,7 @@
 #include <kfusion/cuda/projective_icp.hpp>
 #include <kfusion/cuda/tsdf_volume.hpp>
 #include <kfusion/cuda/color_volume.hpp>
+#include <kfusion/cuda/render_mesh.hpp>
 #include <kfusion/warp_field.hpp>
 
 namespace kfusion
@@ -103,6 +104,12 @@ namespace kfusion
         void dynamicfusion(cuda::Depth& depth, cuda::Cloud live_frame, cuda::Normals current_normals);
         /// kinfu.cpp:408-436: the same views of a fresh ray-cast from `pose`
         void renderImage(cuda::Image& image, const Affine3f& pose, int flags = 0);
+        /// No reference counterpart: the same views of the LIVE model -- the canonical mesh (fetchMesh, fetchNormals; the colour volume's
+        /// colours if there is one) warped by the warp field and rendered into the current camera pose (cuda::renderMesh), shaded by
+        /// cuda::renderImage(points, normals).  A viewer call outside the frame loop: it allocates, and changes nothing the frames use.
+        /// liveModel() is what the last renderLive rendered (point, normal, canonical-point and colour images).
+        void renderLive(cuda::Image& image, int flags = 0);
+        const cuda::RenderMeshOutputs& liveModel() const { return live_model_; }
         Affine3f getCameraPose(int time = -1) const;
         /// the last frame's association: points per status (0 paired, 1 invalid, 2 behind, 3 outside, 4 occluded, 5 hole, 6 far,
         /// 7 normal); all zero until a frame ran with warp_projective_association.  Waits for the device.
@@ -122,6 +129,7 @@ namespace kfusion
         cuda::Dists dists_;
         cuda::Frame curr_, prev_, first_;
         cuda::Cloud points_; cuda::Normals normals_; cuda::Depth depths_;   // renderImage(image, pose, flags)
+        cuda::RenderMeshOutputs live_model_;                                // renderLive(image, flags)
         std::unique_ptr<cuda::TsdfVolume> volume_;
         std::unique_ptr<cuda::ProjectiveICP> icp_;
         std::unique_ptr<WarpField> warp_;

@@ -10,6 +10,7 @@
 #include <kfusion/cuda/tsdf_volume.hpp>
 #include <kfusion/cuda/color_volume.hpp>
 #include <kfusion/cuda/imgproc.hpp>
+#include <kfusion/cuda/render_mesh.hpp>
 #include <kfusion/warp_field.hpp>
 #include <kfusion/cuda/projective_icp.hpp>
 #include <kfusion/kinfu.hpp>
@@ -821,6 +822,33 @@ void kfusion::cuda::associateProjective(const Intr& intr, const DeviceArray<floa
                                        status ? status->ptr() : nullptr, counts ? counts->ptr() : nullptr, nullptr));
 }
 
+// ------------------------------------------------------------------------------------------ renderMesh (include/dfusion.h dfusion_render_mesh)
+void kfusion::cuda::renderMesh(const Intr& intr, const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, int cols, int rows,
+                               const Affine3f* world2cam, const DeviceArray<Normal>& normals, const DeviceArray<Point>& attr,
+                               const DeviceArray<RGB>& colors, RenderMeshOutputs& out, int max_extent)
+{
+    const size_t nv = vertices.size(), nt = triangles.size() / 3;
+    if ((normals.size() && normals.size() < nv) || (attr.size() && attr.size() < nv) || (colors.size() && colors.size() < nv))
+        kfusion::cuda::error("a per-vertex array holds fewer entries than there are vertices", __FILE__, __LINE__, "renderMesh");
+    if (cols <= 0 || rows <= 0) kfusion::cuda::error("empty image", __FILE__, __LINE__, "renderMesh");
+    const bool wn = normals.size() != 0, wa = attr.size() != 0, wc = colors.size() != 0;
+    out.points.create(rows, cols);
+    if (wn) out.normals.create(rows, cols);
+    if (wa) out.attr.create(rows, cols);
+    if (wc) out.colors.create(rows, cols);
+    if (out.tri) out.tri->create(rows, cols);
+    if (out.counts && out.counts->size() < 6) out.counts->create(6);
+    float w2c[12];
+    if (world2cam) affine_to_aff12(*world2cam, w2c);
+    const float iv[4] = {intr.fx, intr.fy, intr.cx, intr.cy};
+    KF_DF(dfusion_render_mesh(nv ? (const float*)vertices.ptr() : nullptr, nv, nt ? (const unsigned int*)triangles.ptr() : nullptr, nt,
+                              world2cam ? w2c : nullptr, wn ? (const float*)normals.ptr() : nullptr, wa ? (const float*)attr.ptr() : nullptr,
+                              wc ? (const unsigned char*)colors.ptr() : nullptr, cols, rows, iv, max_extent, (float*)out.points.ptr(), out.points.step(),
+                              wn ? (float*)out.normals.ptr() : nullptr, wn ? out.normals.step() : 0, wa ? (float*)out.attr.ptr() : nullptr,
+                              wa ? out.attr.step() : 0, wc ? (unsigned char*)out.colors.ptr() : nullptr, wc ? out.colors.step() : 0,
+                              out.tri ? out.tri->ptr() : nullptr, out.tri ? out.tri->step() : 0, out.counts ? out.counts->ptr() : nullptr, nullptr));
+}
+
 // ------------------------------------------------------------------------------------------ views (imgproc.cpp:152-201)
 void kfusion::cuda::renderImage(const Depth& depth, const Normals& normals, const Intr& intr, const Vec3f& light_pose, Image& image)
 {
@@ -1098,6 +1126,33 @@ void KinFu::renderImage(cuda::Image& image, const Affine3f& pose, int flag)
         volume_->raycast(pose, p.intr, points_, normals_);
         render_views(p, nullptr, &points_, normals_, image, flag);
     }
+}
+
+// The live model (no reference counterpart): frontend.renderLiveModel's composition at the current camera pose, then the views above.
+// float4 <-> packed float3 go through dfusion_transform_points without a pose (plain re-striding), so nothing is staged on the host.
+void KinFu::renderLive(cuda::Image& image, int flag)
+{
+    if (poses_.empty()) kfusion::cuda::error("no frame has run yet", __FILE__, __LINE__, "KinFu::renderLive");
+    cuda::DeviceArray<Point> vertices, warped; cuda::DeviceArray<Normal> normals, wnormals; cuda::DeviceArray<int> triangles;
+    cuda::DeviceArray<cuda::RGB> colors;
+    volume_->fetchMesh(vertices, triangles);
+    volume_->fetchNormals(vertices, normals);
+    if (color_) color_->fetchColors(vertices, colors);
+    const size_t nv = vertices.size();
+    if (nv) {
+        cuda::DeviceArray<float> p3(3 * nv), n3(3 * nv);
+        warped.create(nv); wnormals.create(nv);
+        KF_DF(dfusion_transform_points((const float*)vertices.ptr(), nv * 16, 4, p3.ptr(), nv * 12, 3, (int)nv, 1, nullptr, nullptr));
+        KF_DF(dfusion_transform_points((const float*)normals.ptr(), nv * 16, 4, n3.ptr(), nv * 12, 3, (int)nv, 1, nullptr, nullptr));
+        warp_->warp(p3, n3, (int)nv);
+        KF_DF(dfusion_transform_points(p3.ptr(), nv * 12, 3, (float*)warped.ptr(), nv * 16, 4, (int)nv, 1, nullptr, nullptr));
+        KF_DF(dfusion_transform_points(n3.ptr(), nv * 12, 3, (float*)wnormals.ptr(), nv * 16, 4, (int)nv, 1, nullptr, nullptr));
+    }
+    const Affine3f world2cam = getCameraPose().inv();
+    cuda::renderMesh(params_.intr, warped, triangles, params_.cols, params_.rows, &world2cam, wnormals, vertices, colors, live_model_);
+    cuda::waitAllDefaultStream();                                      // the arrays above are freed on return
+    if (!nv) live_model_.normals.create(params_.rows, params_.cols);   // (no normals were given: the shading reads all-NaN points only)
+    render_views(params_, nullptr, &live_model_.points, live_model_.normals, image, flag);
 }
 
 Affine3f KinFu::getCameraPose(int time) const                          // kinfu.cpp:213-218

@@ -641,6 +641,48 @@ int dfusion_associate_projective(const float *points_dev, const float *normals_d
                                  const float intr[4], float dist_thres, float min_cosine, float occlusion_margin, float *live_out_dev,
                                  unsigned char *status_dev, unsigned long long *counts_dev, dfStream stream);
 
+/* A z-buffered rasteriser: the vertex map, normal map, colour image and an interpolated per-vertex attribute of a triangle mesh seen by a
+ * pinhole camera (no reference counterpart; additive, ABI 7).  Every output point lies on its pixel's ray, so pairing it by pixel index
+ * with a depth frame IS projective association.  vertices_dev float4 [V] (dfusion_extract_mesh / dfusion_warp_points), triangles_dev
+ * u32 [3 T], world2cam (nullable: vertices as given) 12 floats, per-vertex normals_dev float4 [V], attr_dev float4 [V] (interpolated
+ * plainly, e.g. the canonical positions), colors_dev 4 bytes [V] -- each nullable; intr = {fx, fy, cx, cy}; max_extent 1..64 pixels.
+ * Arithmetic is f32 without contraction; the sample point of pixel (x, y) is its integer coordinate (the ray of the ray-cast).
+ *   vertex     pc = aff_mul(world2cam, v); u = fmaf(fx, pc.x / pc.z, cx), v = fmaf(fy, pc.y / pc.z, cy).  Valid iff pc is finite,
+ *              pc.z > 0, fabsf(u) < 65536 and fabsf(v) < 65536.  X = (int)rintf(16 u), Y = (int)rintf(16 v) (1/16 pixel, half-even),
+ *              iz = 1 / pc.z
+ *   triangle t = (i0, i1, i2); the FIRST failing test names its status:
+ *     1 invalid     an index >= V (tested before any vertex is read) or an invalid vertex
+ *     2 degenerate  area2 = (X1 - X0)(Y2 - Y0) - (X2 - X0)(Y1 - Y0), an exact integer, is 0
+ *     3 stretched   maxX - minX > 16 max_extent or maxY - minY > 16 max_extent (a tear of the warp, not surface)
+ *     4 off-screen  x0 = max(ceil(minX / 16), 0), x1 = min(floor(maxX / 16), cols - 1), y0, y1 alike: the box is empty
+ *     0 drawn       (it may still cover no sample point)
+ *   orientation  area2 < 0: vertices 1 and 2 swap, with their attributes, and area2 is negated; no back-face culling, no clipping
+ *   coverage     P = (16 x, 16 y); w0 = (X2 - X1)(Py - Y1) - (Y2 - Y1)(Px - X1), w1 of vertices (2, 0), w2 of (0, 1); covered iff
+ *                w0 >= 0 && w1 >= 0 && w2 >= 0 (inclusive, no fill rule: shared edges are drawn twice); w0 + w1 + w2 == area2
+ *   depth        b_i = (float)w_i / (float)area2; iz = (b0 iz0 + b1 iz1) + b2 iz2; z = 1 / iz; dropped unless z > 0 and finite; else a
+ *                64-bit integer atomic min of (bits(z) << 32) | t at the pixel: the nearest sample wins, an exact tie in z goes to the
+ *                lower triangle index
+ *   resolve      an untouched pixel is a miss: the float4 outputs get four 0x7fffffff words (what dfusion_raycast_points writes), the
+ *                colour four 0 bytes, tri_out -1.  Else, with c_i = (b_i iz_i) z:
+ *                  point  = (((float)x - cx) / fx * z, ((float)y - cy) / fy * z, z, 0)
+ *                  attr   = (c0 a0 + c1 a1) + c2 a2 per component, w = 0
+ *                  normal = m / sqrtf(l2) per component, w = 0, with m formed as attr and l2 = dot(m, m); four NaN words unless l2 > 0
+ *                  colour = min(255, (int)floorf(((c0 k0 + c1 k1) + c2 k2) + 0.5f)) per channel, the 4th byte 255
+ *                  tri    = t
+ * All outputs are pitched images (byte pitches; float4 16-byte, colour and tri 4-byte aligned); all but points_out are nullable.
+ * counts_dev (nullable) u64 [6] is OVERWRITTEN: [0..4] triangles per status, [5] covered pixels.  T == 0 or V == 0 draws nothing: all
+ * misses, zero counts.  DF_E_INVALID: vertices_dev NULL with V > 0, triangles_dev NULL with T > 0, V or T > 2^32 - 1, intr or
+ * points_out NULL, cols <= 0, rows <= 0, a pitch shorter than a row or misaligned, max_extent outside 1..64, a non-finite intr,
+ * fx == 0 or fy == 0, and -- with V, T > 0 -- an output image whose per-vertex input is NULL.  Three launches (key fill, raster with
+ * one lane per triangle, resolve with one lane per pixel); the key buffer (8 bytes per pixel) lives in the per-(device, stream)
+ * scratch dfusion_integrate uses, so dfusion_release_scratch() frees it.  No float atomics, no device-to-host copy: the output does
+ * not depend on scheduling.                                                                                                          */
+int dfusion_render_mesh(const float *vertices_dev, unsigned long long V, const unsigned int *triangles_dev, unsigned long long T,
+                        const float world2cam[12], const float *normals_dev, const float *attr_dev, const unsigned char *colors_dev,
+                        int cols, int rows, const float intr[4], int max_extent, float *points_out, size_t points_pitch,
+                        float *normals_out, size_t normals_pitch, float *attr_out, size_t attr_pitch, unsigned char *colors_out,
+                        size_t colors_pitch, int *tri_out, size_t tri_pitch, unsigned long long *counts_dev, dfStream stream);
+
 /* device::ComputeIcpHelper::operator() (internal.hpp:91-92; kfusion/src/cuda/proj_icp.cu:30-441): one Gauss-Newton
  * accumulation of point-to-plane ICP.  aff = current estimate curr -> prev; dist2_thres = dist_thres^2 and
  * min_cosine = cos(angle_thres) (projective_icp.cpp:11-15).  sums_dev[27] = the upper triangle of A (6x6) interleaved
