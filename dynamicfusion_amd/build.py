@@ -91,56 +91,38 @@ HOST_APP = os.path.join(HOST_DIR, "headless_frame")
 HOST_KINFU_APP = os.path.join(HOST_DIR, "kinfu_headless")
 HOST_WARP_TESTS = os.path.join(HOST_DIR, "warp_tests")
 HOST_DEMO_CALLS = os.path.join(HOST_DIR, "demo_calls")
-HOST_REG_SOLVE = os.path.join(HOST_DIR, "reg_solve")
-HOST_ROBUST_SOLVE = os.path.join(HOST_DIR, "robust_solve")
+HOST_WARP_SOLVE = os.path.join(HOST_DIR, "warp_solve")
 HOST_ASSOCIATE = os.path.join(HOST_DIR, "associate")
-HOST_PLANE_SOLVE = os.path.join(HOST_DIR, "plane_solve")
 HOST_COLOR_FRAME = os.path.join(HOST_DIR, "color_frame")
-HOST_RIGID_SOLVE = os.path.join(HOST_DIR, "rigid_solve")
 HOST_RENDER_MESH = os.path.join(HOST_DIR, "render_mesh")
 HOST_ZSLAB_LIB = os.path.join(HOST_DIR, "libkfusion_zslab.so")       # kfusion::cuda::ZSlabComm: the RCCL side of the Z-slab sharding
 HOST_ZSLAB_APP = os.path.join(HOST_DIR, "zslab_frame")
+# the apps over libkfusion_hip.so, in build order: host/<name> from host/apps/<name>.cpp (zslab_frame also links libkfusion_zslab.so and rccl)
+HOST_APPS = [HOST_APP, HOST_KINFU_APP, HOST_WARP_TESTS, HOST_DEMO_CALLS, HOST_WARP_SOLVE, HOST_ASSOCIATE, HOST_COLOR_FRAME, HOST_RENDER_MESH, HOST_ZSLAB_APP]
 
 
 def build_host(force=False, verbose=False):
     """C++ host mirror (kfusion::cuda::TsdfVolume / WarpField over the C-ABI) + the headless harness, with g++."""
     build_library(force=False)
     src = os.path.join(HOST_DIR, "src", "kfusion_hip.cpp")
-    app = os.path.join(HOST_DIR, "apps", "headless_frame.cpp")
-    app2 = os.path.join(HOST_DIR, "apps", "kinfu_headless.cpp")
-    app3 = os.path.join(HOST_DIR, "apps", "warp_tests.cpp")
-    app4 = os.path.join(HOST_DIR, "apps", "demo_calls.cpp")
     zsrc = os.path.join(HOST_DIR, "src", "zslab_rccl.cpp")
-    app5 = os.path.join(HOST_DIR, "apps", "zslab_frame.cpp")
-    app6 = os.path.join(HOST_DIR, "apps", "reg_solve.cpp")
-    app7 = os.path.join(HOST_DIR, "apps", "robust_solve.cpp")
-    app8 = os.path.join(HOST_DIR, "apps", "associate.cpp")
-    app9 = os.path.join(HOST_DIR, "apps", "plane_solve.cpp")
-    app10 = os.path.join(HOST_DIR, "apps", "color_frame.cpp")
-    app11 = os.path.join(HOST_DIR, "apps", "rigid_solve.cpp")
-    app12 = os.path.join(HOST_DIR, "apps", "render_mesh.cpp")
-    deps = [src, app, app2, app3, app4, zsrc, app5, app6, app7, app8, app9, app10, app11, app12, LIB_PATH] + [os.path.join(r, f) for r, _, fs in os.walk(os.path.join(HOST_DIR, "include")) for f in fs]
-    outs = (HOST_LIB, HOST_APP, HOST_KINFU_APP, HOST_WARP_TESTS, HOST_DEMO_CALLS, HOST_ZSLAB_LIB, HOST_ZSLAB_APP, HOST_REG_SOLVE, HOST_ROBUST_SOLVE, HOST_ASSOCIATE, HOST_PLANE_SOLVE, HOST_COLOR_FRAME, HOST_RIGID_SOLVE, HOST_RENDER_MESH)
+    apps = [(os.path.join(HOST_DIR, "apps", os.path.basename(out) + ".cpp"), out) for out in HOST_APPS]
+    deps = [src, zsrc, LIB_PATH] + [a for a, _ in apps] + [os.path.join(r, f) for r, _, fs in os.walk(os.path.join(HOST_DIR, "include")) for f in fs]
+    outs = [HOST_LIB, HOST_ZSLAB_LIB] + [o for _, o in apps]
     if not force and all(os.path.exists(f) for f in outs) and min(os.path.getmtime(f) for f in outs) >= max(os.path.getmtime(d) for d in deps):
         return HOST_LIB, HOST_APP
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     common = ["g++", "-std=c++17", "-O2", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(HOST_DIR, "include"),
               "-I", os.path.join(REPO_DIR, "include"), "-I", os.path.join(rocm, "include")]
     link = ["-L", PKG_DIR, "-ldfusion_hip", "-L", os.path.join(rocm, "lib"), "-lamdhip64"]
-    cmds = [common + ["-fPIC", "-shared", src, "-o", HOST_LIB] + link + ["-Wl,-rpath,$ORIGIN/.."],
-            common + [app, "-o", HOST_APP, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
-            common + [app2, "-o", HOST_KINFU_APP, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
-            common + [app3, "-o", HOST_WARP_TESTS, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
-            common + [app4, "-o", HOST_DEMO_CALLS, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
-            common + [app6, "-o", HOST_REG_SOLVE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
-            common + [app7, "-o", HOST_ROBUST_SOLVE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
-            common + [app8, "-o", HOST_ASSOCIATE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
-            common + [app9, "-o", HOST_PLANE_SOLVE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
-            common + [app10, "-o", HOST_COLOR_FRAME, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
-            common + [app11, "-o", HOST_RIGID_SOLVE, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
-            common + [app12, "-o", HOST_RENDER_MESH, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
-            common + ["-fPIC", "-shared", zsrc, "-o", HOST_ZSLAB_LIB, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-lrccl", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."],
-            common + [app5, "-o", HOST_ZSLAB_APP, "-L", HOST_DIR, "-lkfusion_zslab", "-lkfusion_hip"] + link + ["-lrccl", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."]]
+    rpaths = ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/.."]
+    cmds = [common + ["-fPIC", "-shared", src, "-o", HOST_LIB] + link + ["-Wl,-rpath,$ORIGIN/.."]]
+    for app, out in apps:
+        if out == HOST_ZSLAB_APP:
+            cmds.append(common + ["-fPIC", "-shared", zsrc, "-o", HOST_ZSLAB_LIB, "-L", HOST_DIR, "-lkfusion_hip"] + link + ["-lrccl"] + rpaths)
+            cmds.append(common + [app, "-o", out, "-L", HOST_DIR, "-lkfusion_zslab", "-lkfusion_hip"] + link + ["-lrccl"] + rpaths)
+        else:
+            cmds.append(common + [app, "-o", out, "-L", HOST_DIR, "-lkfusion_hip"] + link + rpaths)
     for c in cmds:
         if verbose:
             print(" ".join(c))

@@ -17,11 +17,12 @@
 //   dot products / vector updates     : one 1024-thread workgroup (M <= 65535), fixed tree.
 // dfusion_warp_solve adds DynamicFusion's regularisation term over a node graph, dfusion_warp_solve_robust a Tukey
 // penalty on the data term and a Huber penalty on the edges by re-weighted rounds, dfusion_warp_solve_plane takes the
-// data term along the model normals (point-to-plane).  The four entry points share one
-// host pipeline at the end of this file: one workspace (SvWorkspace), one preparation (df_sv_prepare: what depends only on the
-// canonical points and the node positions) and one round loop (df_sv_rounds), in which a term that is switched off launches nothing.
-// dfusion_warp_solve_rigid makes the node rotations unknowns too, against the warp dfusion_warp_points applies: its own
-// round loop (df_sv_rigid_rounds) on the same workspace, graph, sort, lists, penalty and coupled step kernels.
+// data term along the model normals (point-to-plane), and dfusion_warp_solve_rigid makes the node rotations
+// unknowns too, against the warp dfusion_warp_points applies.  The host pipeline is at the end of this file.  Every entry point fills one
+// description of its solve (SvSolve), checked by df_sv_check; df_sv_context makes of it what a solve works with (SvContext: flags, grids,
+// one workspace, the graph, the CG kernels) and holds every stage the solves share -- the preparation, the penalty weights, the energies,
+// the CG skeleton, the outputs -- in which a term that is switched off launches nothing.  What is left in the two round loops is their
+// difference: df_sv_rounds (translations: W, W^T, a linear final residual) and df_sv_rigid_rounds (six unknowns a node: warp, J, J^T).
 // Nothing returns to the host between iterations: once every component has converged (scal[SV_ACTIVE] == 0) the kernels of the
 // remaining steps return at once.
 #include <hipcub/hipcub.hpp>
@@ -136,9 +137,33 @@ __global__ __launch_bounds__(256) void df_sv_sorted_kernel(const unsigned int* _
     sorted_w[i] = w[e];
 }
 
+// ---- the node tree of the two apply^T kernels: S sums a thread, 256 threads; the partials are combined by the tree (t, t + s),
+// s = 128 .. 1 (s >= 64 through LDS, s <= 32 with __shfl_down inside wave 0) -- a fixed order, restated in the oracle.  Lane 0 of wave 0
+// ends with the totals in s and runs `done`.
+template <int S, typename Done>
+__device__ __forceinline__ void sv_node_tree(float (&s)[S], float* lds /* [S][128] */, Done done)
+{
+    const int t = threadIdx.x, wv = t >> 6, l = t & 63;
+    if (wv >= 2) { for (int c = 0; c < S; ++c) lds[c * 128 + (t - 128)] = s[c]; }
+    __syncthreads();
+    if (wv < 2) { for (int c = 0; c < S; ++c) s[c] = s[c] + lds[c * 128 + t]; }
+    __syncthreads();
+    if (wv == 1) { for (int c = 0; c < S; ++c) lds[c * 128 + l] = s[c]; }
+    __syncthreads();
+    if (wv == 0) {
+#pragma unroll
+        for (int c = 0; c < S; ++c) {
+            float a = s[c] + lds[c * 128 + l];
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) a = a + __shfl_down(a, o, 64);
+            s[c] = a;
+        }
+        if (l == 0) done();
+    }
+}
+
 // ---- out = W^T u (+ lambda * p) : one 256-thread workgroup per node over its (ascending-point-order) entry list.
-// Thread t sums entries t, t + 256, ... ; the 256 partials are combined by the tree (t, t + s), s = 128 .. 1 (s >= 64 through
-// LDS, s <= 32 with __shfl_down inside wave 0) -- a fixed order, restated in the oracle.
+// Thread t sums entries t, t + 256, ... ; then sv_node_tree.
 __global__ __launch_bounds__(256) void df_sv_wt_apply_kernel(const unsigned int* __restrict__ off, const unsigned int* __restrict__ sorted_pt,
                                                              const float* __restrict__ sorted_w, int M, const float* __restrict__ u,
                                                              float lambda, const float* __restrict__ p, float* __restrict__ out,
@@ -146,7 +171,7 @@ __global__ __launch_bounds__(256) void df_sv_wt_apply_kernel(const unsigned int*
 {
     __shared__ float lds[3 * 128];
     if (active && *active == 0.f) return;                               // see df_sv_w_apply_kernel
-    const int n = blockIdx.x, t = threadIdx.x, wv = t >> 6, l = t & 63;
+    const int n = blockIdx.x, t = threadIdx.x;
     const unsigned int b = off[n], e_end = off[n + 1];
     float s[3] = {0.f, 0.f, 0.f};
     // the entry's point id and weight sit in list order (df_sv_sorted_kernel), so a trip is one coalesced read + the u gather
@@ -155,25 +180,10 @@ __global__ __launch_bounds__(256) void df_sv_wt_apply_kernel(const unsigned int*
         const float we = sorted_w[i];
         s[0] = s[0] + we * u[3 * v]; s[1] = s[1] + we * u[3 * v + 1]; s[2] = s[2] + we * u[3 * v + 2];
     }
-    if (wv >= 2) { for (int c = 0; c < 3; ++c) lds[c * 128 + (t - 128)] = s[c]; }
-    __syncthreads();
-    if (wv < 2) { for (int c = 0; c < 3; ++c) s[c] = s[c] + lds[c * 128 + t]; }
-    __syncthreads();
-    if (wv == 1) { for (int c = 0; c < 3; ++c) lds[c * 128 + l] = s[c]; }
-    __syncthreads();
-    if (wv == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float a = s[c] + lds[c * 128 + l];
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) a = a + __shfl_down(a, o, 64);
-            s[c] = a;
-        }
-        if (l == 0) {
-            if (p) { s[0] = s[0] + lambda * p[3 * n]; s[1] = s[1] + lambda * p[3 * n + 1]; s[2] = s[2] + lambda * p[3 * n + 2]; }
-            out[3 * n] = s[0]; out[3 * n + 1] = s[1]; out[3 * n + 2] = s[2];
-        }
-    }
+    sv_node_tree(s, lds, [&]() {
+        if (p) { s[0] = s[0] + lambda * p[3 * n]; s[1] = s[1] + lambda * p[3 * n + 1]; s[2] = s[2] + lambda * p[3 * n + 2]; }
+        out[3 * n] = s[0]; out[3 * n + 1] = s[1]; out[3 * n + 2] = s[2];
+    });
 }
 
 // ---- single-workgroup vector algebra: three independent CG recurrences (x, y, z components share the matrix), or ONE over all three
@@ -368,14 +378,18 @@ __global__ __launch_bounds__(256) void df_sv_residual_kernel(const float* __rest
     if (i < n3) e1[i] = e0[i] - wx[i];
 }
 
+// ---- a node's rot / dual float4 as a quaternion, and node n's transform applied to a point
+__device__ __forceinline__ quat sv_quat(float4 v) { quat q; q.w = v.x; q.x = v.y; q.y = v.z; q.z = v.w; return q; }
+__device__ __forceinline__ f3 sv_node_transform(const float4* __restrict__ rot, const float4* __restrict__ dual, int n, float4 p) { return dq_transform(sv_quat(rot[n]), sv_quat(dual[n]), mk3(p.x, p.y, p.z)); }
+
 // ---- write back: T = T0 + x ; translation_ = 0.5 * (0, T) * rotation_ (encodeTranslation, dual_quaternion.hpp:82-85)
 __global__ __launch_bounds__(256) void df_sv_writeback_kernel(const float4* __restrict__ rot, const float4* __restrict__ node_t,
                                                               const float* __restrict__ x, int M, float* __restrict__ dq_out)
 {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= M) return;
-    const float4 r4 = rot[n], t4 = node_t[n];
-    quat r; r.w = r4.x; r.x = r4.y; r.y = r4.z; r.z = r4.w;
+    const float4 t4 = node_t[n];
+    const quat r = sv_quat(rot[n]);
     quat T; T.w = 0.f; T.x = t4.y + x[3 * n]; T.y = t4.z + x[3 * n + 1]; T.z = t4.w + x[3 * n + 2];
     const quat d = q_mul(q_scale(0.5f, T), r);
     float* o = dq_out + 8 * (size_t)n;
@@ -421,12 +435,8 @@ __global__ __launch_bounds__(256) void df_sv_reg_edge_kernel(const int* __restri
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= E) return;
     const int i = e / kg, j = nbr[e];
-    const float4 pj = pos_sigma[j], ri = rot[i], di = dual[i], rj = rot[j], dj = dual[j];
-    quat a, b;
-    a.w = ri.x; a.x = ri.y; a.y = ri.z; a.z = ri.w; b.w = di.x; b.x = di.y; b.y = di.z; b.z = di.w;
-    const f3 ti = dq_transform(a, b, mk3(pj.x, pj.y, pj.z));
-    a.w = rj.x; a.x = rj.y; a.y = rj.z; a.z = rj.w; b.w = dj.x; b.x = dj.y; b.y = dj.z; b.z = dj.w;
-    const f3 tj = dq_transform(a, b, mk3(pj.x, pj.y, pj.z));
+    const float4 pj = pos_sigma[j];
+    const f3 ti = sv_node_transform(rot, dual, i, pj), tj = sv_node_transform(rot, dual, j, pj);
     g[3 * e] = ti.x - tj.x; g[3 * e + 1] = ti.y - tj.y; g[3 * e + 2] = ti.z - tj.z;
 }
 
@@ -475,7 +485,10 @@ __global__ __launch_bounds__(256) void df_sv_reg_apply_kernel(const int* __restr
     for (int c = 0; c < 3; ++c) q[3 * n + c] = q[3 * n + c] + lambda_reg * acc[c];
 }
 
-// ---- E_reg = sum_e alpha_e |(g_e + x_i) - x_j|^2 (x nullable = 0), reduced like df_sv_energy_kernel over the edges
+// component c of the edge value h_e = (g_e + x_i) - x_j of the edge e = (i -> j), x nullable = 0
+__device__ __forceinline__ float sv_edge_h(const float* __restrict__ g, const float* __restrict__ x, int e, int i, int j, int c) { return x ? (g[3 * e + c] + x[3 * i + c]) - x[3 * j + c] : g[3 * e + c]; }
+
+// ---- E_reg = sum_e alpha_e |h_e|^2, reduced like df_sv_energy_kernel over the edges
 __global__ __launch_bounds__(SV_BLOCK) void df_sv_reg_energy_kernel(const int* __restrict__ nbr, const float* __restrict__ alpha,
                                                                     const float* __restrict__ g, const float* __restrict__ x, int E, int kg,
                                                                     float* __restrict__ out)
@@ -486,7 +499,7 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_reg_energy_kernel(const int* _
         const int i = e / kg, j = nbr[e];
         const float a = alpha[e];
         for (int c = 0; c < 3; ++c) {
-            const float h = x ? (g[3 * e + c] + x[3 * i + c]) - x[3 * j + c] : g[3 * e + c];
+            const float h = sv_edge_h(g, x, e, i, j, c);
             s[c] = s[c] + a * (h * h);
         }
     }
@@ -521,15 +534,26 @@ __global__ __launch_bounds__(256) void df_sv_round_e0_kernel(const float* __rest
     e0[3 * v + 2] = valid ? (live[3 * v + 2] - canonical[3 * v + 2]) - sz : 0.f;
 }
 
-// omega_v = (1 - s / c^2)^2 for s = |e_v|^2 < c^2, else 0 (a NaN s compares false: 0)
+// The Tukey penalty of a point on s, its squared residual: s = |e_v|^2 from the residuals e [3N], or (PLANE) s = rho_v^2
+// from the projected residuals e = rho [N].  The weight is (1 - s / c^2)^2 for s < c^2, else 0 (a NaN s compares false: 0); the
+// energy rho(s) = c^2/3 (1 - (1 - s/c^2)^3) below c^2 and c^2/3 above (third = c^2 / 3).
+template <bool PLANE>
+__device__ __forceinline__ float sv_point_s(const float* __restrict__ e, int v)
+{
+    if constexpr (PLANE) return e[v] * e[v];
+    const float ex = e[3 * v], ey = e[3 * v + 1], ez = e[3 * v + 2];
+    return (ex * ex + ey * ey) + ez * ez;
+}
+__device__ __forceinline__ float sv_tukey_weight(float s, float c2) { const float u = 1.f - s / c2; return (s < c2) ? u * u : 0.f; }
+__device__ __forceinline__ float sv_tukey_rho(float s, float c2, float third) { const float u = 1.f - s / c2; return (s < c2) ? third * (1.f - (u * u) * u) : third; }
+
+// omega_v = the Tukey weight of point v
+template <bool PLANE>
 __global__ __launch_bounds__(256) void df_sv_tukey_kernel(const float* __restrict__ e, int N, float c2, float* __restrict__ omega)
 {
     const int v = blockIdx.x * 256 + threadIdx.x;
     if (v >= N) return;
-    const float ex = e[3 * v], ey = e[3 * v + 1], ez = e[3 * v + 2];
-    const float s = (ex * ex + ey * ey) + ez * ez;
-    const float u = 1.f - s / c2;
-    omega[v] = (s < c2) ? u * u : 0.f;
+    omega[v] = sv_tukey_weight(sv_point_s<PLANE>(e, v), c2);
 }
 
 // sorted_w'[i] = omega_pt(i) * sorted_w[i]: list order, so the two entry reads and the write are coalesced; omega is a gather (ascending
@@ -555,23 +579,6 @@ __global__ __launch_bounds__(256) void df_sv_huber_kernel(const float* __restric
     alpha_w[e] = alpha[e] * om;
 }
 
-// ---- E_data = sum_v rho(|e_v|^2), rho(s) = c^2/3 (1 - (1 - s/c^2)^3) below c^2 and c^2/3 above: one value per point, thread t owns
-// points t, t + 1024, ..., then the 1024-tree (df_sv_energy_kernel's shape)
-__global__ __launch_bounds__(SV_BLOCK) void df_sv_tukey_energy_kernel(const float* __restrict__ e, int N, float c2, float* __restrict__ out)
-{
-    __shared__ float lds[3 * SV_BLOCK];
-    float acc[3] = {0.f, 0.f, 0.f};
-    const float third = c2 / 3.f;
-    for (int v = threadIdx.x; v < N; v += SV_BLOCK) {
-        const float ex = e[3 * v], ey = e[3 * v + 1], ez = e[3 * v + 2];
-        const float s = (ex * ex + ey * ey) + ez * ez;
-        const float u = 1.f - s / c2;
-        acc[0] = acc[0] + ((s < c2) ? third * (1.f - (u * u) * u) : third);
-    }
-    sv_block_sum3(acc, lds);
-    if (threadIdx.x == 0) *out = acc[0];
-}
-
 // ---- E_reg = sum_e alpha_e psi(|h_e|^2), h = (g_e + x_i) - x_j (x nullable = 0), psi(s) = s up to delta^2 and 2 delta sqrt(s) - delta^2 above
 __global__ __launch_bounds__(SV_BLOCK) void df_sv_huber_energy_kernel(const int* __restrict__ nbr, const float* __restrict__ alpha,
                                                                       const float* __restrict__ g, const float* __restrict__ x, int E, int kg,
@@ -583,7 +590,7 @@ __global__ __launch_bounds__(SV_BLOCK) void df_sv_huber_energy_kernel(const int*
     for (int e = threadIdx.x; e < E; e += SV_BLOCK) {
         const int i = e / kg, j = nbr[e];
         float h[3];
-        for (int c = 0; c < 3; ++c) h[c] = x ? (g[3 * e + c] + x[3 * i + c]) - x[3 * j + c] : g[3 * e + c];
+        for (int c = 0; c < 3; ++c) h[c] = sv_edge_h(g, x, e, i, j, c);
         const float s = (h[0] * h[0] + h[1] * h[1]) + h[2] * h[2];
         acc[0] = acc[0] + alpha[e] * ((s <= d2) ? s : two_delta * sqrtf(s) - d2);
     }
@@ -610,30 +617,19 @@ __global__ __launch_bounds__(256) void df_sv_plane_rho_kernel(const float* __res
     if (b) { b[3 * v] = valid ? nx * r : 0.f; b[3 * v + 1] = valid ? ny * r : 0.f; b[3 * v + 2] = valid ? nz * r : 0.f; }
 }
 
-// df_sv_tukey_kernel with s = rho^2
-__global__ __launch_bounds__(256) void df_sv_plane_tukey_kernel(const float* __restrict__ rho, int N, float c2, float* __restrict__ omega)
+// ---- E_data as a sum of ONE value per point: s_v = rho_v^2 (PLANE) or, TUKEY, the Tukey rho(s_v) with s_v as in df_sv_tukey_kernel<PLANE>.
+// Thread t owns points t, t + 1024, ..., then the 1024-tree.  (The quadratic point-to-point energy is df_sv_energy_kernel's: three sums
+// through three trees, another order.)
+template <bool PLANE, bool TUKEY>
+__global__ __launch_bounds__(SV_BLOCK) void df_sv_point_energy_kernel(const float* __restrict__ e, int N, float c2, float* __restrict__ out)
 {
-    const int v = blockIdx.x * 256 + threadIdx.x;
-    if (v >= N) return;
-    const float s = rho[v] * rho[v];
-    const float u = 1.f - s / c2;
-    omega[v] = (s < c2) ? u * u : 0.f;
-}
-
-// ---- E_data = sum_v rho_v^2 (TUKEY: sum_v of df_sv_tukey_energy_kernel's value at s = rho_v^2): one value per point, thread t owns points
-// t, t + 1024, ..., then the 1024-tree
-template <bool TUKEY>
-__global__ __launch_bounds__(SV_BLOCK) void df_sv_plane_energy_kernel(const float* __restrict__ rho, int N, float c2, float* __restrict__ out)
-{
+    static_assert(PLANE || TUKEY, "the quadratic point-to-point energy sums per component: df_sv_energy_kernel");
     __shared__ float lds[3 * SV_BLOCK];
     float acc[3] = {0.f, 0.f, 0.f};
     const float third = c2 / 3.f;
     for (int v = threadIdx.x; v < N; v += SV_BLOCK) {
-        const float s = rho[v] * rho[v];
-        if constexpr (TUKEY) {
-            const float u = 1.f - s / c2;
-            acc[0] = acc[0] + ((s < c2) ? third * (1.f - (u * u) * u) : third);
-        } else acc[0] = acc[0] + s;
+        const float s = sv_point_s<PLANE>(e, v);
+        acc[0] = acc[0] + (TUKEY ? sv_tukey_rho(s, c2, third) : s);
     }
     sv_block_sum3(acc, lds);
     if (threadIdx.x == 0) *out = acc[0];
@@ -689,10 +685,8 @@ __global__ __launch_bounds__(256) void df_sv_rigid_centre_kernel(const float4* _
 {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= M) return;
-    const float4 p = pos_sigma[n], r = rot[n], d = dual[n], nt = node_t[n];
-    quat a, b;
-    a.w = r.x; a.x = r.y; a.y = r.z; a.z = r.w; b.w = d.x; b.x = d.y; b.y = d.z; b.z = d.w;
-    const f3 t = dq_transform(a, b, mk3(p.x, p.y, p.z));
+    const float4 nt = node_t[n];
+    const f3 t = sv_node_transform(rot, dual, n, pos_sigma[n]);
     c[n] = make_float4(t.x, t.y, t.z, 0.f);
     qc[n] = make_float4(t.x - nt.y, t.y - nt.z, t.z - nt.w, 0.f);
 }
@@ -806,7 +800,7 @@ __global__ __launch_bounds__(256) void df_sv_rigid_jt_apply_kernel(const unsigne
 {
     __shared__ float lds[6 * 128];
     if (active && *active == 0.f) return;                               // see df_sv_w_apply_kernel
-    const int n = blockIdx.x, t = threadIdx.x, wv = t >> 6, l = t & 63;
+    const int n = blockIdx.x, t = threadIdx.x;
     const unsigned int b = off[n], e_end = off[n + 1];
     float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (unsigned int i = b + t; i < e_end; i += 256) {
@@ -816,31 +810,16 @@ __global__ __launch_bounds__(256) void df_sv_rigid_jt_apply_kernel(const unsigne
         s[0] = s[0] + we * uv.x; s[1] = s[1] + we * uv.y; s[2] = s[2] + we * uv.z;
         s[3] = s[3] + wne * xv.x; s[4] = s[4] + wne * xv.y; s[5] = s[5] + wne * xv.z;
     }
-    if (wv >= 2) { for (int q = 0; q < 6; ++q) lds[q * 128 + (t - 128)] = s[q]; }
-    __syncthreads();
-    if (wv < 2) { for (int q = 0; q < 6; ++q) s[q] = s[q] + lds[q * 128 + t]; }
-    __syncthreads();
-    if (wv == 1) { for (int q = 0; q < 6; ++q) lds[q * 128 + l] = s[q]; }
-    __syncthreads();
-    if (wv == 0) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            float a = s[q] + lds[q * 128 + l];
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) a = a + __shfl_down(a, o, 64);
-            s[q] = a;
+    sv_node_tree(s, lds, [&]() {
+        const float4 qn = qc[n];
+        float om[3] = {s[3] - (qn.y * s[2] - qn.z * s[1]), s[4] - (qn.z * s[0] - qn.x * s[2]), s[5] - (qn.x * s[1] - qn.y * s[0])};
+        float* const ot = out + 3 * (size_t)M;
+        if (p) {
+            const float* const pt = p + 3 * (size_t)M;
+            for (int q = 0; q < 3; ++q) { om[q] = om[q] + lambda_rot * p[3 * n + q]; s[q] = s[q] + lambda * pt[3 * n + q]; }
         }
-        if (l == 0) {
-            const float4 qn = qc[n];
-            float om[3] = {s[3] - (qn.y * s[2] - qn.z * s[1]), s[4] - (qn.z * s[0] - qn.x * s[2]), s[5] - (qn.x * s[1] - qn.y * s[0])};
-            float* const ot = out + 3 * (size_t)M;
-            if (p) {
-                const float* const pt = p + 3 * (size_t)M;
-                for (int q = 0; q < 3; ++q) { om[q] = om[q] + lambda_rot * p[3 * n + q]; s[q] = s[q] + lambda * pt[3 * n + q]; }
-            }
-            for (int q = 0; q < 3; ++q) { out[3 * n + q] = om[q]; ot[3 * n + q] = s[q]; }
-        }
-    }
+        for (int q = 0; q < 3; ++q) { out[3 * n + q] = om[q]; ot[3 * n + q] = s[q]; }
+    });
 }
 
 // ---- per edge e = (i -> j) and round: g_e = T_i(v_j) - c_j (the regularisation residual) and b_e = T_i(v_j) - c_i (the arm omega_i turns)
@@ -852,10 +831,8 @@ __global__ __launch_bounds__(256) void df_sv_rigid_edge_kernel(const int* __rest
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= E) return;
     const int i = e / kg, j = nbr[e];
-    const float4 pj = pos_sigma[j], ri = rot[i], di = dual[i], ci = c[i], cj = c[j];
-    quat a, b;
-    a.w = ri.x; a.x = ri.y; a.y = ri.z; a.z = ri.w; b.w = di.x; b.x = di.y; b.y = di.z; b.z = di.w;
-    const f3 ti = dq_transform(a, b, mk3(pj.x, pj.y, pj.z));
+    const float4 ci = c[i], cj = c[j];
+    const f3 ti = sv_node_transform(rot, dual, i, pos_sigma[j]);
     g[3 * e] = ti.x - cj.x; g[3 * e + 1] = ti.y - cj.y; g[3 * e + 2] = ti.z - cj.z;
     arm[3 * e] = ti.x - ci.x; arm[3 * e + 1] = ti.y - ci.y; arm[3 * e + 2] = ti.z - ci.z;
 }
@@ -933,7 +910,7 @@ __global__ __launch_bounds__(256) void df_sv_rigid_writeback_kernel(const float4
         o[0] = r4.x; o[1] = r4.y; o[2] = r4.z; o[3] = r4.w; o[4] = d4.x; o[5] = d4.y; o[6] = d4.z; o[7] = d4.w;
         return;
     }
-    quat r; r.w = r4.x; r.x = r4.y; r.y = r4.z; r.z = r4.w;
+    const quat r = sv_quat(r4);
     quat qo; qo.w = 1.f; qo.x = 0.5f * ox; qo.y = 0.5f * oy; qo.z = 0.5f * oz;
     qo = q_normalize(qo);
     const quat r1 = q_mul(qo, q_normalize(r));
@@ -1052,9 +1029,6 @@ static int df_sv_workspace(DfWarpField* wf, int N, int k, int M, int Eg, bool pl
     return DF_OK;
 }
 
-// Once per call, what depends only on the canonical points and the node positions: the graph (kg > 0), the k-NN, the entries' weights
-// and node ids (with e0 at the transforms the handle holds now), the node offsets and the node-major lists.  `normals` (nullable: the
-// point-to-plane solve's) only add to what makes a point invalid.
 // The node-major side of the entries, from the point-major keys / vals the setup kernel wrote: the stable sort by node id, the node
 // offsets, and the node-major copy of the point ids with the weights `w` (and, for the solve with rotations, of a second weight list).
 static int df_sv_lists(const SvWorkspace& ws, int E, int k, int M, const float* w, float* sw, const float* w2, float* sw2, hipStream_t st)
@@ -1070,301 +1044,321 @@ static int df_sv_lists(const SvWorkspace& ws, int E, int k, int M, const float* 
     return DF_OK;
 }
 
-// What a solve hands back besides the transforms it set: the energies (a call without the regularisation term reports 0 for it), the
-// last round's transforms and weights (1 everywhere for a penalty that is off).
-static int df_sv_outputs(const SvWorkspace& ws, int N, int M, int Eg, bool reg, bool tukey, bool huber, float* dq_out, float* energy, int n_energy,
-                         float* point_weights, float* edge_weights, hipStream_t st)
-{
-    if (energy) {
-        DF_HIP(hipMemcpyAsync(energy, ws.scal + SV_ENERGY, (reg ? n_energy : 2) * sizeof(float), hipMemcpyDeviceToDevice, st));
-        static const float zeros[2] = {0.f, 0.f};                       // (a copy from the host, not a fill: no kernel of any kind is added)
-        if (!reg && n_energy == 4) DF_HIP(hipMemcpyAsync(energy + 2, zeros, sizeof(zeros), hipMemcpyHostToDevice, st));
-    }
-    if (dq_out) DF_HIP(hipMemcpyAsync(dq_out, ws.dq, (size_t)M * 32, hipMemcpyDeviceToDevice, st));
-    if (point_weights) {
-        if (tukey) DF_HIP(hipMemcpyAsync(point_weights, ws.omega, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-        else DF_HIP(hipMemsetD32Async((hipDeviceptr_t)point_weights, 0x3f800000, (size_t)N, st));
-    }
-    if (edge_weights) {
-        if (huber) DF_HIP(hipMemcpyAsync(edge_weights, ws.omega_e, (size_t)Eg * 4, hipMemcpyDeviceToDevice, st));
-        else DF_HIP(hipMemsetD32Async((hipDeviceptr_t)edge_weights, 0x3f800000, (size_t)Eg, st));
-    }
-    return DF_OK;
-}
-
-static int df_sv_prepare(DfWarpField* wf, int k, const float* canonical, const float* live, const float* normals, int N, int kg,
-                         const SvWorkspace& ws, dfStream stream)
-{
-    hipStream_t st = (hipStream_t)stream;
-    const int M = wf->M, E = N * k;
-    int rc;
-    if (kg && (rc = df_sv_graph(wf, kg, stream))) return rc;
-    if ((rc = dfusion_knn(wf, k, canonical, N, ws.idx, ws.d2, stream))) return rc;   // getWeightsAndUpdateKNN's k-NN (NaN queries are masked below)
-    hipLaunchKernelGGL(normals ? df_sv_setup_kernel<true> : df_sv_setup_kernel<false>, dim3((N + 255) / 256), dim3(256), 0, st, canonical, live, normals,
-                       N, k, ws.idx, ws.d2, wf->pos_sigma, wf->node_t, M, ws.w, ws.keys, ws.vals, ws.e0);
-    DF_LAUNCH_CHECK();
-    return df_sv_lists(ws, E, k, M, ws.w, ws.sw, nullptr, nullptr, st);
-}
-
-// The solve behind the four entry points (arguments checked and normalised by df_sv_check: kg = 0 means no regularisation).
+// One solve, as its entry point describes it and df_sv_check has checked and normalised it (kg = 0 means no regularisation).
 // `rounds` solves, each from the transforms the one before wrote; tukey_c / huber_delta = 0: that penalty is quadratic and its kernels
 // are not launched, so rounds = 1 with both 0 is the plain solve, launch for launch.  `energy` (nullable) holds n_energy floats:
 // 2 = {E_data before, after}, 4 = with {E_reg before, after}, which are 0 without the term.  `normals` (nullable) switches the data term
-// to point-to-plane: the residual a round starts at becomes rho = n . e0 (the energies and the Tukey weights read it), the right-hand
-// side W^T (n rho), W p is projected, and the three CG recurrences become one.
-static int df_sv_rounds(DfWarpField* wf, int k, const float* canonical, const float* live, const float* normals, int N, int iters, float lambda, int kg, float lambda_reg,
-                        int rounds, float tukey_c, float huber_delta, float* dq_out, float* energy, int n_energy, float* point_weights,
-                        float* edge_weights, dfStream stream)
+// to point-to-plane; lambda_rot is the solve with rotations' alone.
+struct SvSolve {
+    DfWarpField* wf; int k; const float *canonical, *live, *normals; int N;
+    int iters; float lambda, lambda_rot; int kg; float lambda_reg; int rounds; float tukey_c, huber_delta;
+    float *dq_out, *energy; int n_energy; float *point_weights, *edge_weights; dfStream stream;
+};
+
+// The CG kernels by the number of unknown entries X (x, r, p, q stay in registers up to 8 * SV_BLOCK of them), and an apply kernel
+// template <K, PLANE> by the neighbour count (compile-time for 8 and 4).
+typedef void (*SvInitKernel)(const float*, int, float*, float*, float*);
+typedef void (*SvStepKernel)(const float*, int, float*, float*, float*, float*);
+template <bool COUPLED> static SvStepKernel df_sv_step_for(int X)
 {
-    hipStream_t st = (hipStream_t)stream;
-    const bool reg = kg > 0, tukey = tukey_c != 0.f, huber = reg && huber_delta != 0.f, plane = normals != nullptr;
-    const int M = wf->M, E = N * k, Eg = M * kg;
-    const float c2 = tukey_c * tukey_c, dd2 = huber_delta * huber_delta;
+    return X <= 2 * SV_BLOCK ? df_sv_step_reg_kernel<2, COUPLED> : X <= 5 * SV_BLOCK ? df_sv_step_reg_kernel<5, COUPLED>
+         : X <= 8 * SV_BLOCK ? df_sv_step_reg_kernel<8, COUPLED> : df_sv_step_kernel<COUPLED>;
+}
+#define SV_APPLY_FOR(kernel, PLANE, k) ((k) == 8 ? kernel<8, PLANE> : (k) == 4 ? kernel<4, PLANE> : kernel<0, PLANE>)
+
+// What both round loops work with, made once per call by df_sv_context: the flags, the sizes and grids, the workspace, the pointers to
+// what W^T / J^T and the regularisation read (the scaled copies, or the lists as they are; the handle's cached alpha is only read), the CG
+// kernels -- and the stages both loops launch, in which a term that is switched off launches nothing.
+struct SvContext {                                          // (df_sv_context fills the members in this order)
+    SvSolve s; hipStream_t st;
+    bool rigid, reg, tukey, huber, plane;
+    int M, X, E, Eg;                                        // X: the unknown entries, M or (rigid) 2M
+    float c2, dd2;
+    dim3 gN, gM, gE, gG, gW, one;
     SvWorkspace ws;
-    int rc;
-    if ((rc = df_sv_workspace(wf, N, k, M, Eg, plane, tukey, huber, false, st, &ws))) return rc;
-    if ((rc = df_sv_prepare(wf, k, canonical, live, normals, N, kg, ws, stream))) return rc;
-    const float* const sw_use = tukey ? ws.sw_scaled : ws.sw;           // what W^T reads: the scaled copy, or the list as it is
-    const float* const alpha_use = huber ? ws.alpha_scaled : wf->graph_alpha.p;   // the handle's cached alpha is only read
-    const float* const active = ws.scal + SV_ACTIVE; float* const en = ws.scal + SV_ENERGY;
-    const dim3 gN((N + 255) / 256), gM((M + 255) / 256), gE((unsigned)(((size_t)E + 255) / 256)), gG((Eg + 255) / 256), gW(M), one(1);
-    auto step = M <= 2 * SV_BLOCK ? df_sv_step_reg_kernel<2, false> : M <= 5 * SV_BLOCK ? df_sv_step_reg_kernel<5, false> : M <= 8 * SV_BLOCK ? df_sv_step_reg_kernel<8, false> : df_sv_step_kernel<false>;
-    auto w_apply = k == 8 ? df_sv_w_apply_kernel<8, false> : k == 4 ? df_sv_w_apply_kernel<4, false> : df_sv_w_apply_kernel<0, false>;
-    auto wp_apply = w_apply;                                            // W p inside the CG loop: projected on the normals with `plane`
-    auto init = df_sv_init_kernel<false>;
-    if (plane) {
-        step = M <= 2 * SV_BLOCK ? df_sv_step_reg_kernel<2, true> : M <= 5 * SV_BLOCK ? df_sv_step_reg_kernel<5, true> : M <= 8 * SV_BLOCK ? df_sv_step_reg_kernel<8, true> : df_sv_step_kernel<true>;
-        wp_apply = k == 8 ? df_sv_w_apply_kernel<8, true> : k == 4 ? df_sv_w_apply_kernel<4, true> : df_sv_w_apply_kernel<0, true>;
-        init = df_sv_init_kernel<true>;
+    const float *sw_use, *swn_use, *alpha_use, *active; float* en;
+    SvInitKernel init; SvStepKernel step;
+    // Once per call, what depends only on the canonical points and the node positions (the graph is the context's already): the k-NN,
+    // `setup` (the entries' weights and node ids, point-major), the node offsets and the node-major lists (w2 / sw2: see df_sv_lists)
+    template <typename Setup> int prepare(Setup setup, const float* w2, float* sw2) const
+    {
+        int rc;
+        if ((rc = dfusion_knn(s.wf, s.k, s.canonical, s.N, ws.idx, ws.d2, s.stream))) return rc;   // getWeightsAndUpdateKNN's k-NN (NaN queries are masked by `setup`)
+        if ((rc = setup())) return rc;
+        DF_LAUNCH_CHECK();
+        return df_sv_lists(ws, E, s.k, M, ws.w, ws.sw, w2, sw2, st);
     }
-    // the data energy of the residual e (plane: of rho = n . e, which lands in ws.rho)
-    auto data_energy = [&](const float* e, float* out) {
-        if (plane) {
-            if (e != ws.e0) hipLaunchKernelGGL(df_sv_plane_rho_kernel, gN, dim3(256), 0, st, e, normals, ws.keys, N, k, M, ws.rho, (float*)nullptr);
-            hipLaunchKernelGGL(tukey ? df_sv_plane_energy_kernel<true> : df_sv_plane_energy_kernel<false>, one, dim3(SV_BLOCK), 0, st, ws.rho, N, c2, out);
+    // rho = n . e in ws.rho and, with b, b = n rho
+    void plane_rho(const float* e, const float* n, float* b) const { hipLaunchKernelGGL(df_sv_plane_rho_kernel, gN, dim3(256), 0, st, e, n, ws.keys, s.N, s.k, M, ws.rho, b); }
+    // Tukey: omega from the residual the round starts at (ws.e0; plane: ws.rho), multiplied into copies of the node-major lists
+    int tukey_weights() const
+    {
+        hipLaunchKernelGGL(plane ? df_sv_tukey_kernel<true> : df_sv_tukey_kernel<false>, gN, dim3(256), 0, st, plane ? ws.rho : ws.e0, s.N, c2, ws.omega);
+        hipLaunchKernelGGL(df_sv_scale_list_kernel, gE, dim3(256), 0, st, ws.spt, ws.sw, ws.omega, E, ws.sw_scaled);
+        if (rigid) hipLaunchKernelGGL(df_sv_scale_list_kernel, gE, dim3(256), 0, st, ws.spt, ws.swn, ws.omega, E, ws.swn_scaled);
+        DF_LAUNCH_CHECK();
+        return DF_OK;
+    }
+    // Huber: omega_e from the round's g_e, multiplied into a copy of alpha
+    void huber_weights() const { hipLaunchKernelGGL(df_sv_huber_kernel, gG, dim3(256), 0, st, ws.g, s.wf->graph_alpha.p, Eg, s.huber_delta, dd2, ws.omega_e, ws.alpha_scaled); }
+    // the data energy of the residual e (plane: of ws.rho, which holds n . e)
+    void data_energy(const float* e, float* out) const
+    {
+        if (plane || tukey) {
+            const auto one_value = !plane ? df_sv_point_energy_kernel<false, true> : tukey ? df_sv_point_energy_kernel<true, true> : df_sv_point_energy_kernel<true, false>;
+            hipLaunchKernelGGL(one_value, one, dim3(SV_BLOCK), 0, st, plane ? ws.rho : e, s.N, c2, out);
         }
-        else if (tukey) hipLaunchKernelGGL(df_sv_tukey_energy_kernel, one, dim3(SV_BLOCK), 0, st, e, N, c2, out);
-        else hipLaunchKernelGGL(df_sv_energy_kernel, one, dim3(SV_BLOCK), 0, st, e, N, out);
-    };
-    auto reg_energy = [&](const float* xv, float* out) {                // (the energies weigh an edge with alpha_e itself, not alpha'_e)
-        if (huber) hipLaunchKernelGGL(df_sv_huber_energy_kernel, one, dim3(SV_BLOCK), 0, st, wf->graph_nbr.p, wf->graph_alpha.p, ws.g, xv, Eg, kg, huber_delta, dd2, out);
-        else hipLaunchKernelGGL(df_sv_reg_energy_kernel, one, dim3(SV_BLOCK), 0, st, wf->graph_nbr.p, wf->graph_alpha.p, ws.g, xv, Eg, kg, out);
-    };
-    for (int round = 0; round < rounds; ++round) {
-        const bool first = round == 0, last = round == rounds - 1;
+        else hipLaunchKernelGGL(df_sv_energy_kernel, one, dim3(SV_BLOCK), 0, st, e, s.N, out);
+    }
+    // the regularisation energy of ws.g at the update x (nullable = 0); the energies weigh an edge with alpha_e itself, not alpha'_e
+    void reg_energy(const float* x, float* out) const
+    {
+        const DfWarpField* wf = s.wf;
+        if (huber) hipLaunchKernelGGL(df_sv_huber_energy_kernel, one, dim3(SV_BLOCK), 0, st, wf->graph_nbr.p, wf->graph_alpha.p, ws.g, x, Eg, s.kg, s.huber_delta, dd2, out);
+        else hipLaunchKernelGGL(df_sv_reg_energy_kernel, one, dim3(SV_BLOCK), 0, st, wf->graph_nbr.p, wf->graph_alpha.p, ws.g, x, Eg, s.kg, out);
+    }
+    // conjugate gradients from the right-hand side in ws.r: x0 = 0, p0 = r0, then `iters` steps of q = A p by the caller's launches
+    // (apply: ws.p -> the point side ; apply_t: the point side -> ws.q, damping included ; reg_apply: ws.q += lambda_reg L ws.p)
+    template <typename Apply, typename ApplyT, typename RegApply> int cg(Apply apply, ApplyT apply_t, RegApply reg_apply) const
+    {
+        hipLaunchKernelGGL(init, one, dim3(SV_BLOCK), 0, st, ws.r, X, ws.x, ws.p, ws.scal);
+        DF_LAUNCH_CHECK();
+        for (int it = 0; it < s.iters; ++it) {
+            apply();
+            apply_t();
+            if (reg) reg_apply();
+            hipLaunchKernelGGL(step, one, dim3(SV_BLOCK), 0, st, ws.q, X, ws.x, ws.r, ws.p, ws.scal);
+            DF_LAUNCH_CHECK();
+        }
+        return DF_OK;
+    }
+    // What a solve hands back besides the transforms it set: the energies (a call without the regularisation term reports 0 for it),
+    // the last round's transforms and weights (1 everywhere for a penalty that is off).
+    int outputs() const
+    {
+        if (s.energy) {
+            DF_HIP(hipMemcpyAsync(s.energy, en, (reg ? s.n_energy : 2) * sizeof(float), hipMemcpyDeviceToDevice, st));
+            static const float zeros[2] = {0.f, 0.f};                   // (a copy from the host, not a fill: no kernel of any kind is added)
+            if (!reg && s.n_energy == 4) DF_HIP(hipMemcpyAsync(s.energy + 2, zeros, sizeof(zeros), hipMemcpyHostToDevice, st));
+        }
+        if (s.dq_out) DF_HIP(hipMemcpyAsync(s.dq_out, ws.dq, (size_t)M * 32, hipMemcpyDeviceToDevice, st));
+        if (s.point_weights) {
+            if (tukey) DF_HIP(hipMemcpyAsync(s.point_weights, ws.omega, (size_t)s.N * 4, hipMemcpyDeviceToDevice, st));
+            else DF_HIP(hipMemsetD32Async((hipDeviceptr_t)s.point_weights, 0x3f800000, (size_t)s.N, st));
+        }
+        if (s.edge_weights) {
+            if (huber) DF_HIP(hipMemcpyAsync(s.edge_weights, ws.omega_e, (size_t)Eg * 4, hipMemcpyDeviceToDevice, st));
+            else DF_HIP(hipMemsetD32Async((hipDeviceptr_t)s.edge_weights, 0x3f800000, (size_t)Eg, st));
+        }
+        return DF_OK;
+    }
+};
+
+static int df_sv_context(const SvSolve& s, bool rigid, SvContext* cx)
+{
+    DfWarpField* const wf = s.wf;
+    SvWorkspace ws;
+    const bool reg = s.kg > 0, tukey = s.tukey_c != 0.f, huber = reg && s.huber_delta != 0.f, plane = s.normals != nullptr;
+    const int M = wf->M, X = rigid ? 2 * M : M, E = s.N * s.k, Eg = M * s.kg;
+    int rc;
+    if ((rc = df_sv_workspace(wf, s.N, s.k, M, Eg, plane, tukey, huber, rigid, (hipStream_t)s.stream, &ws))) return rc;
+    if (reg && (rc = df_sv_graph(wf, s.kg, s.stream))) return rc;     // (the first call on a handle allocates graph_alpha, read just below)
+    // one recurrence over all components where the matrix mixes them: point-to-plane, and the six unknowns of a node
+    const bool coupled = plane || rigid;
+    *cx = SvContext{s, (hipStream_t)s.stream, rigid, reg, tukey, huber, plane, M, X, E, Eg, s.tukey_c * s.tukey_c, s.huber_delta * s.huber_delta,
+                    dim3((s.N + 255) / 256), dim3((M + 255) / 256), dim3((unsigned)(((size_t)E + 255) / 256)), dim3((Eg + 255) / 256), dim3(M), dim3(1), ws,
+                    tukey ? ws.sw_scaled : ws.sw, tukey ? ws.swn_scaled : ws.swn, huber ? ws.alpha_scaled : wf->graph_alpha.p,
+                    ws.scal + SV_ACTIVE, ws.scal + SV_ENERGY, coupled ? df_sv_init_kernel<true> : df_sv_init_kernel<false>,
+                    coupled ? df_sv_step_for<true>(X) : df_sv_step_for<false>(X)};
+    return DF_OK;
+}
+
+// The translation solve behind the first four entry points.  With `normals` the residual a round starts at becomes rho = n . e0 (the
+// energies and the Tukey weights read it), the right-hand side W^T (n rho), W p is projected, and the three CG recurrences become one.
+static int df_sv_rounds(const SvSolve& s)
+{
+    SvContext cx;
+    int rc;
+    if ((rc = df_sv_context(s, false, &cx))) return rc;
+    DfWarpField* const wf = s.wf; const SvWorkspace& ws = cx.ws; hipStream_t st = cx.st;
+    const int N = s.N, k = s.k, kg = s.kg, M = cx.M; const bool plane = cx.plane; const dim3 gN = cx.gN, gM = cx.gM, gW = cx.gW;
+    const auto w_apply = SV_APPLY_FOR(df_sv_w_apply_kernel, false, k);
+    const auto wp_apply = plane ? SV_APPLY_FOR(df_sv_w_apply_kernel, true, k) : w_apply;   // W p inside the CG loop: projected on the normals
+    // the entries' weights and node ids, with e0 at the transforms the handle holds now; the normals only add to what makes a point invalid
+    if ((rc = cx.prepare([&]() {
+            hipLaunchKernelGGL(plane ? df_sv_setup_kernel<true> : df_sv_setup_kernel<false>, gN, dim3(256), 0, st, s.canonical, s.live, s.normals, N, k, ws.idx, ws.d2,
+                               wf->pos_sigma, wf->node_t, M, ws.w, ws.keys, ws.vals, ws.e0);
+            return DF_OK;
+        }, nullptr, nullptr))) return rc;
+    for (int round = 0; round < s.rounds; ++round) {
+        const bool first = round == 0, last = round == s.rounds - 1;
         if (!first) {                                                   // e0 at the transforms the previous round wrote
-            hipLaunchKernelGGL(df_sv_round_e0_kernel, gN, dim3(256), 0, st, canonical, live, N, k, ws.keys, ws.w, wf->node_t.p, M, ws.e0);
+            hipLaunchKernelGGL(df_sv_round_e0_kernel, gN, dim3(256), 0, st, s.canonical, s.live, N, k, ws.keys, ws.w, wf->node_t.p, M, ws.e0);
             DF_LAUNCH_CHECK();
         }
         if (plane) {                                                    // rho of e0, and b = n rho in u
-            hipLaunchKernelGGL(df_sv_plane_rho_kernel, gN, dim3(256), 0, st, ws.e0, normals, ws.keys, N, k, M, ws.rho, ws.u);
+            cx.plane_rho(ws.e0, s.normals, ws.u);
             DF_LAUNCH_CHECK();
         }
-        if (tukey) {
-            if (plane) hipLaunchKernelGGL(df_sv_plane_tukey_kernel, gN, dim3(256), 0, st, ws.rho, N, c2, ws.omega);
-            else hipLaunchKernelGGL(df_sv_tukey_kernel, gN, dim3(256), 0, st, ws.e0, N, c2, ws.omega);
-            hipLaunchKernelGGL(df_sv_scale_list_kernel, gE, dim3(256), 0, st, ws.spt, ws.sw, ws.omega, E, ws.sw_scaled);
-            DF_LAUNCH_CHECK();
-        }
-        if (energy && first) { data_energy(ws.e0, en); DF_LAUNCH_CHECK(); }
-        // r0 = W^T Omega e0 - lambda_reg * b' (plane: W^T Omega n rho) ; p0 = r0 ; x0 = 0
-        hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, sw_use, M, plane ? ws.u : ws.e0, 0.f, (const float*)nullptr, ws.r, (const float*)nullptr);
+        if (cx.tukey && (rc = cx.tukey_weights())) return rc;
+        if (s.energy && first) { cx.data_energy(ws.e0, cx.en); DF_LAUNCH_CHECK(); }
+        // r0 = W^T Omega e0 - lambda_reg * b' (plane: W^T Omega n rho)
+        hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, cx.sw_use, M, plane ? ws.u : ws.e0, 0.f, (const float*)nullptr, ws.r, (const float*)nullptr);
         DF_LAUNCH_CHECK();
-        if (reg) {
-            hipLaunchKernelGGL(df_sv_reg_edge_kernel, gG, dim3(256), 0, st, wf->graph_nbr.p, wf->pos_sigma.p, wf->rot.p, wf->dual.p, Eg, kg, ws.g);
-            if (huber) hipLaunchKernelGGL(df_sv_huber_kernel, gG, dim3(256), 0, st, ws.g, wf->graph_alpha.p, Eg, huber_delta, dd2, ws.omega_e, ws.alpha_scaled);
-            hipLaunchKernelGGL(df_sv_reg_rhs_kernel, gM, dim3(256), 0, st, alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg, ws.g, lambda_reg, ws.r);
-            if (energy && first) reg_energy(nullptr, en + 2);
+        if (cx.reg) {
+            hipLaunchKernelGGL(df_sv_reg_edge_kernel, cx.gG, dim3(256), 0, st, wf->graph_nbr.p, wf->pos_sigma.p, wf->rot.p, wf->dual.p, cx.Eg, kg, ws.g);
+            if (cx.huber) cx.huber_weights();
+            hipLaunchKernelGGL(df_sv_reg_rhs_kernel, gM, dim3(256), 0, st, cx.alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg, ws.g, s.lambda_reg, ws.r);
+            if (s.energy && first) cx.reg_energy(nullptr, cx.en + 2);
             DF_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(init, one, dim3(SV_BLOCK), 0, st, ws.r, M, ws.x, ws.p, ws.scal);
-        DF_LAUNCH_CHECK();
-        for (int it = 0; it < iters; ++it) {
-            hipLaunchKernelGGL(wp_apply, gN, dim3(256), 0, st, ws.w, ws.keys, N, k, M, ws.p, ws.u, active, normals);
-            hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, sw_use, M, ws.u, lambda, ws.p, ws.q, active);
-            if (reg) hipLaunchKernelGGL(df_sv_reg_apply_kernel, gM, dim3(256), 0, st, wf->graph_nbr.p, alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg, ws.p,
-                                        lambda_reg, ws.q, active);
-            hipLaunchKernelGGL(step, one, dim3(SV_BLOCK), 0, st, ws.q, M, ws.x, ws.r, ws.p, ws.scal);
-            DF_LAUNCH_CHECK();
-        }
-        if (energy && last) {
+        rc = cx.cg([&]() { hipLaunchKernelGGL(wp_apply, gN, dim3(256), 0, st, ws.w, ws.keys, N, k, M, ws.p, ws.u, cx.active, s.normals); },
+                   [&]() { hipLaunchKernelGGL(df_sv_wt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, cx.sw_use, M, ws.u, s.lambda, ws.p, ws.q, cx.active); },
+                   [&]() { hipLaunchKernelGGL(df_sv_reg_apply_kernel, gM, dim3(256), 0, st, wf->graph_nbr.p, cx.alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg,
+                                              ws.p, s.lambda_reg, ws.q, cx.active); });
+        if (rc) return rc;
+        if (s.energy && last) {                                         // the energies of the final residual e0 - W x, which is linear in x
             hipLaunchKernelGGL(w_apply, gN, dim3(256), 0, st, ws.w, ws.keys, N, k, M, ws.x, ws.u, (const float*)nullptr, (const float*)nullptr);
             hipLaunchKernelGGL(df_sv_residual_kernel, dim3((unsigned)((3 * (size_t)N + 255) / 256)), dim3(256), 0, st, ws.e0, ws.u, 3 * N, ws.u);
-            data_energy(ws.u, en + 1);
-            if (reg) reg_energy(ws.x, en + 3);
+            if (plane) cx.plane_rho(ws.u, s.normals, nullptr);
+            cx.data_energy(ws.u, cx.en + 1);
+            if (cx.reg) cx.reg_energy(ws.x, cx.en + 3);
             DF_LAUNCH_CHECK();
         }
         hipLaunchKernelGGL(df_sv_writeback_kernel, gM, dim3(256), 0, st, wf->rot.p, wf->node_t.p, ws.x, M, ws.dq);
         DF_LAUNCH_CHECK();
-        if ((rc = dfusion_warp_set_transforms(wf, ws.dq, stream))) return rc;   // (the handle's rot / dual / node_t are the new ones from here on)
+        if ((rc = dfusion_warp_set_transforms(wf, ws.dq, s.stream))) return rc;   // (the handle's rot / dual / node_t are the new ones from here on)
     }
-    return df_sv_outputs(ws, N, M, Eg, reg, tukey, huber, dq_out, energy, n_energy, point_weights, edge_weights, st);
+    return cx.outputs();
 }
 
 // The solve behind dfusion_warp_solve_rigid (arguments checked by df_sv_check and the entry point).  df_sv_rounds'
 // shape: one workspace, one preparation, `rounds` rounds, a term that is switched off launches nothing -- but every round starts with the
 // warp of the canonical points (and normals) at the transforms the handle holds, and the unknowns are 2M entries.
-static int df_sv_rigid_rounds(DfWarpField* wf, int k, const float* canonical, const float* live, const float* normals, int N, int iters, float lambda,
-                              float lambda_rot, int kg, float lambda_reg, int rounds, float tukey_c, float huber_delta, float* dq_out, float* energy,
-                              float* point_weights, float* edge_weights, dfStream stream)
+static int df_sv_rigid_rounds(const SvSolve& s)
 {
-    hipStream_t st = (hipStream_t)stream;
-    const bool reg = kg > 0, tukey = tukey_c != 0.f, huber = reg && huber_delta != 0.f, plane = normals != nullptr;
-    const int M = wf->M, M2 = 2 * M, E = N * k, Eg = M * kg;
-    const float c2 = tukey_c * tukey_c, dd2 = huber_delta * huber_delta;
     static const float ident[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
-    SvWorkspace ws;
+    SvContext cx;
     int rc;
-    if ((rc = df_sv_workspace(wf, N, k, M, Eg, plane, tukey, huber, true, st, &ws))) return rc;
-    if (kg && (rc = df_sv_graph(wf, kg, stream))) return rc;           // (before alpha_use below: the first call on a handle allocates the graph)
-    const float* const sw_use = tukey ? ws.sw_scaled : ws.sw;
-    const float* const swn_use = tukey ? ws.swn_scaled : ws.swn;
-    const float* const alpha_use = huber ? ws.alpha_scaled : wf->graph_alpha.p;
-    const float* const active = ws.scal + SV_ACTIVE; float* const en = ws.scal + SV_ENERGY;
-    const dim3 gN((N + 255) / 256), gM((M + 255) / 256), gE((unsigned)(((size_t)E + 255) / 256)), gG((Eg + 255) / 256), gW(M), one(1);
-    auto step = M2 <= 2 * SV_BLOCK ? df_sv_step_reg_kernel<2, true> : M2 <= 5 * SV_BLOCK ? df_sv_step_reg_kernel<5, true> : M2 <= 8 * SV_BLOCK ? df_sv_step_reg_kernel<8, true> : df_sv_step_kernel<true>;
-    auto j_apply = plane ? (k == 8 ? df_sv_rigid_j_apply_kernel<8, true> : k == 4 ? df_sv_rigid_j_apply_kernel<4, true> : df_sv_rigid_j_apply_kernel<0, true>)
-                         : (k == 8 ? df_sv_rigid_j_apply_kernel<8, false> : k == 4 ? df_sv_rigid_j_apply_kernel<4, false> : df_sv_rigid_j_apply_kernel<0, false>);
+    if ((rc = df_sv_context(s, true, &cx))) return rc;
+    DfWarpField* const wf = s.wf; const SvWorkspace& ws = cx.ws; hipStream_t st = cx.st;
+    const int N = s.N, k = s.k, kg = s.kg, M = cx.M; const bool plane = cx.plane; const dim3 gN = cx.gN, gM = cx.gM, gW = cx.gW;
+    const auto j_apply = plane ? SV_APPLY_FOR(df_sv_rigid_j_apply_kernel, true, k) : SV_APPLY_FOR(df_sv_rigid_j_apply_kernel, false, k);
     // y, n' at the transforms the handle holds now: copies through the point path with an identity warp_to_live
     auto warp = [&]() -> int {
-        DF_HIP(hipMemcpyAsync(ws.y, canonical, (size_t)N * 12, hipMemcpyDeviceToDevice, st));
-        if (plane) DF_HIP(hipMemcpyAsync(ws.nw, normals, (size_t)N * 12, hipMemcpyDeviceToDevice, st));
-        return dfusion_warp_points(wf, k, ws.y, plane ? ws.nw : nullptr, N, ident, stream);
+        DF_HIP(hipMemcpyAsync(ws.y, s.canonical, (size_t)N * 12, hipMemcpyDeviceToDevice, st));
+        if (plane) DF_HIP(hipMemcpyAsync(ws.nw, s.normals, (size_t)N * 12, hipMemcpyDeviceToDevice, st));
+        return dfusion_warp_points(wf, k, ws.y, plane ? ws.nw : nullptr, N, ident, s.stream);
     };
     // e = live - y in e0 (plane: rho = n' . e in ws.rho); with b for a round's solve: a_v too, and (plane) n' rho in u
     auto residual = [&](bool b) {
-        hipLaunchKernelGGL(df_sv_rigid_residual_kernel, gN, dim3(256), 0, st, live, ws.y, ws.keys, ws.w, wf->node_t.p, N, k, M, ws.e0, b ? ws.a : (float*)nullptr);
-        if (plane) hipLaunchKernelGGL(df_sv_plane_rho_kernel, gN, dim3(256), 0, st, ws.e0, ws.nw, ws.keys, N, k, M, ws.rho, b ? ws.u : (float*)nullptr);
-    };
-    auto data_energy = [&](float* out) {
-        if (plane) hipLaunchKernelGGL(tukey ? df_sv_plane_energy_kernel<true> : df_sv_plane_energy_kernel<false>, one, dim3(SV_BLOCK), 0, st, ws.rho, N, c2, out);
-        else if (tukey) hipLaunchKernelGGL(df_sv_tukey_energy_kernel, one, dim3(SV_BLOCK), 0, st, ws.e0, N, c2, out);
-        else hipLaunchKernelGGL(df_sv_energy_kernel, one, dim3(SV_BLOCK), 0, st, ws.e0, N, out);
+        hipLaunchKernelGGL(df_sv_rigid_residual_kernel, gN, dim3(256), 0, st, s.live, ws.y, ws.keys, ws.w, wf->node_t.p, N, k, M, ws.e0, b ? ws.a : (float*)nullptr);
+        if (plane) cx.plane_rho(ws.e0, ws.nw, b ? ws.u : nullptr);
     };
     auto centres = [&]() { hipLaunchKernelGGL(df_sv_rigid_centre_kernel, gM, dim3(256), 0, st, wf->pos_sigma.p, wf->rot.p, wf->dual.p, wf->node_t.p, M, ws.c, ws.qc); };
     auto edges = [&]() {
-        hipLaunchKernelGGL(df_sv_rigid_edge_kernel, gG, dim3(256), 0, st, wf->graph_nbr.p, wf->pos_sigma.p, wf->rot.p, wf->dual.p, ws.c, Eg, kg, ws.g, ws.arm);
+        hipLaunchKernelGGL(df_sv_rigid_edge_kernel, cx.gG, dim3(256), 0, st, wf->graph_nbr.p, wf->pos_sigma.p, wf->rot.p, wf->dual.p, ws.c, cx.Eg, kg, ws.g, ws.arm);
     };
-    auto reg_energy = [&](float* out) {                                 // (the energies weigh an edge with alpha_e itself, not alpha'_e)
-        if (huber) hipLaunchKernelGGL(df_sv_huber_energy_kernel, one, dim3(SV_BLOCK), 0, st, wf->graph_nbr.p, wf->graph_alpha.p, ws.g, (const float*)nullptr, Eg, kg, huber_delta, dd2, out);
-        else hipLaunchKernelGGL(df_sv_reg_energy_kernel, one, dim3(SV_BLOCK), 0, st, wf->graph_nbr.p, wf->graph_alpha.p, ws.g, (const float*)nullptr, Eg, kg, out);
-    };
-    // once per call: the graph, the k-NN, the first round's warp (it decides validity too), the entries, the node-major lists
-    {
-        if ((rc = dfusion_knn(wf, k, canonical, N, ws.idx, ws.d2, stream))) return rc;
-        if ((rc = warp())) return rc;
-        hipLaunchKernelGGL(df_sv_rigid_setup_kernel, gN, dim3(256), 0, st, canonical, live, normals, ws.y, ws.nw, N, k, ws.idx, ws.d2, wf->pos_sigma.p, M,
-                           ws.w, ws.wn, ws.keys, ws.vals);
-        DF_LAUNCH_CHECK();
-        if ((rc = df_sv_lists(ws, E, k, M, ws.w, ws.sw, ws.wn, ws.swn, st))) return rc;
-    }
-    for (int round = 0; round < rounds; ++round) {
+    // the first round's warp (it decides validity too), then the entries with their normalised weights as a second list
+    if ((rc = cx.prepare([&]() -> int {
+            const int rw = warp();
+            if (rw) return rw;
+            hipLaunchKernelGGL(df_sv_rigid_setup_kernel, gN, dim3(256), 0, st, s.canonical, s.live, s.normals, ws.y, ws.nw, N, k, ws.idx, ws.d2, wf->pos_sigma.p, M,
+                               ws.w, ws.wn, ws.keys, ws.vals);
+            return DF_OK;
+        }, ws.wn, ws.swn))) return rc;
+    for (int round = 0; round < s.rounds; ++round) {
         const bool first = round == 0;
         if (!first && (rc = warp())) return rc;
         centres();
         residual(true);
         DF_LAUNCH_CHECK();
-        if (tukey) {
-            if (plane) hipLaunchKernelGGL(df_sv_plane_tukey_kernel, gN, dim3(256), 0, st, ws.rho, N, c2, ws.omega);
-            else hipLaunchKernelGGL(df_sv_tukey_kernel, gN, dim3(256), 0, st, ws.e0, N, c2, ws.omega);
-            hipLaunchKernelGGL(df_sv_scale_list_kernel, gE, dim3(256), 0, st, ws.spt, ws.sw, ws.omega, E, ws.sw_scaled);
-            hipLaunchKernelGGL(df_sv_scale_list_kernel, gE, dim3(256), 0, st, ws.spt, ws.swn, ws.omega, E, ws.swn_scaled);
-            DF_LAUNCH_CHECK();
-        }
-        if (energy && first) { data_energy(en); DF_LAUNCH_CHECK(); }
-        // r0 = J^T Omega b - lambda_reg * acc(g) ; p0 = r0 ; x0 = 0
+        if (cx.tukey && (rc = cx.tukey_weights())) return rc;
+        if (s.energy && first) { cx.data_energy(ws.e0, cx.en); DF_LAUNCH_CHECK(); }
+        // r0 = J^T Omega b - lambda_reg * acc(g)
         hipLaunchKernelGGL(df_sv_rigid_pack_kernel, gN, dim3(256), 0, st, plane ? ws.u : ws.e0, ws.a, N, ws.rec);
-        hipLaunchKernelGGL(df_sv_rigid_jt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, sw_use, swn_use, M, ws.rec, ws.qc, 0.f, 0.f,
+        hipLaunchKernelGGL(df_sv_rigid_jt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, cx.sw_use, cx.swn_use, M, ws.rec, ws.qc, 0.f, 0.f,
                            (const float*)nullptr, ws.r, (const float*)nullptr);
         DF_LAUNCH_CHECK();
-        if (reg) {
+        if (cx.reg) {
             edges();
-            if (huber) hipLaunchKernelGGL(df_sv_huber_kernel, gG, dim3(256), 0, st, ws.g, wf->graph_alpha.p, Eg, huber_delta, dd2, ws.omega_e, ws.alpha_scaled);
-            hipLaunchKernelGGL(df_sv_rigid_reg_kernel<true>, gM, dim3(256), 0, st, wf->graph_nbr.p, alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg, ws.g,
-                               ws.arm, (const float*)nullptr, lambda_reg, ws.r, (const float*)nullptr);
-            if (energy && first) reg_energy(en + 2);
+            if (cx.huber) cx.huber_weights();
+            hipLaunchKernelGGL(df_sv_rigid_reg_kernel<true>, gM, dim3(256), 0, st, wf->graph_nbr.p, cx.alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg, ws.g,
+                               ws.arm, (const float*)nullptr, s.lambda_reg, ws.r, (const float*)nullptr);
+            if (s.energy && first) cx.reg_energy(nullptr, cx.en + 2);
             DF_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(df_sv_init_kernel<true>, one, dim3(SV_BLOCK), 0, st, ws.r, M2, ws.x, ws.p, ws.scal);
-        DF_LAUNCH_CHECK();
-        for (int it = 0; it < iters; ++it) {
-            hipLaunchKernelGGL(j_apply, gN, dim3(256), 0, st, ws.w, ws.wn, ws.keys, N, k, M, ws.p, ws.a, ws.qc, ws.rec, active, ws.nw);
-            hipLaunchKernelGGL(df_sv_rigid_jt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, sw_use, swn_use, M, ws.rec, ws.qc, lambda, lambda_rot, ws.p, ws.q,
-                               active);
-            if (reg) hipLaunchKernelGGL(df_sv_rigid_reg_kernel<false>, gM, dim3(256), 0, st, wf->graph_nbr.p, alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, M, kg,
-                                        ws.g, ws.arm, ws.p, lambda_reg, ws.q, active);
-            hipLaunchKernelGGL(step, one, dim3(SV_BLOCK), 0, st, ws.q, M2, ws.x, ws.r, ws.p, ws.scal);
-            DF_LAUNCH_CHECK();
-        }
+        rc = cx.cg([&]() { hipLaunchKernelGGL(j_apply, gN, dim3(256), 0, st, ws.w, ws.wn, ws.keys, N, k, M, ws.p, ws.a, ws.qc, ws.rec, cx.active, ws.nw); },
+                   [&]() { hipLaunchKernelGGL(df_sv_rigid_jt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, cx.sw_use, cx.swn_use, M, ws.rec, ws.qc, s.lambda,
+                                              s.lambda_rot, ws.p, ws.q, cx.active); },
+                   [&]() { hipLaunchKernelGGL(df_sv_rigid_reg_kernel<false>, gM, dim3(256), 0, st, wf->graph_nbr.p, cx.alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p,
+                                              M, kg, ws.g, ws.arm, ws.p, s.lambda_reg, ws.q, cx.active); });
+        if (rc) return rc;
         hipLaunchKernelGGL(df_sv_rigid_writeback_kernel, gM, dim3(256), 0, st, wf->rot.p, wf->dual.p, wf->node_t.p, ws.c, ws.x, M, ws.dq);
         DF_LAUNCH_CHECK();
-        if ((rc = dfusion_warp_set_transforms(wf, ws.dq, stream))) return rc;   // (the handle's rot / dual / node_t are the new ones from here on)
+        if ((rc = dfusion_warp_set_transforms(wf, ws.dq, s.stream))) return rc;   // (the handle's rot / dual / node_t are the new ones from here on)
     }
-    if (energy) {                                                       // the true energies behind the last write-back
+    if (s.energy) {                                                     // the true energies behind the last write-back
         if ((rc = warp())) return rc;
         residual(false);
-        data_energy(en + 1);
-        if (reg) { centres(); edges(); reg_energy(en + 3); }
+        cx.data_energy(ws.e0, cx.en + 1);
+        if (cx.reg) { centres(); edges(); cx.reg_energy(nullptr, cx.en + 3); }
         DF_LAUNCH_CHECK();
     }
-    return df_sv_outputs(ws, N, M, Eg, reg, tukey, huber, dq_out, energy, 4, point_weights, edge_weights, st);
+    return cx.outputs();
 }
 
-// The arguments the three entry points share.  DF_OK, with *kg = 0 where the regularisation is switched off (kg == 0 or
-// lambda_reg == 0: checked first, so an out-of-range kg is refused whatever lambda_reg is), or DF_E_INVALID.
-static int df_sv_check(const DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int* kg,
-                       float lambda_reg)
+// The arguments of every entry point, in the order they have always been checked: the ones all share, `own_ok` (what only the calling
+// entry point takes: the normals it requires, lambda_rot), the robust ones.  DF_OK, with s->kg = 0 where the regularisation is switched
+// off (kg == 0 or lambda_reg == 0: checked first, so an out-of-range kg is refused whatever lambda_reg is), or DF_E_INVALID.
+static int df_sv_check(SvSolve* s, bool own_ok = true)
 {
-    if (!wf || !canonical || !live || N <= 0 || iters < 0 || !(lambda >= 0.f) || wf->M <= 0 || k < 1 || k > 8 || wf->M < k) return DF_E_INVALID;
-    if ((size_t)N * k > 0x7fffffffu) return DF_E_INVALID;
-    if (*kg < 0 || *kg > 7 || (*kg > 0 && wf->M < *kg + 1) || !(lambda_reg >= 0.f)) return DF_E_INVALID;
-    if (lambda_reg == 0.f) *kg = 0;
+    const DfWarpField* wf = s->wf;
+    if (!wf || !s->canonical || !s->live || s->N <= 0 || s->iters < 0 || !(s->lambda >= 0.f) || wf->M <= 0 || s->k < 1 || s->k > 8 || wf->M < s->k) return DF_E_INVALID;
+    if ((size_t)s->N * s->k > 0x7fffffffu) return DF_E_INVALID;
+    if (s->kg < 0 || s->kg > 7 || (s->kg > 0 && wf->M < s->kg + 1) || !(s->lambda_reg >= 0.f)) return DF_E_INVALID;
+    if (s->lambda_reg == 0.f) s->kg = 0;
+    if (!own_ok) return DF_E_INVALID;
+    if (s->rounds < 1 || !(s->tukey_c >= 0.f) || !(s->huber_delta >= 0.f) || (s->edge_weights && s->kg == 0)) return DF_E_INVALID;
     return DF_OK;
 }
 
 extern "C" int dfusion_warp_solve_data_term(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda,
                                             float* dq_out, float* energy, dfStream stream)
 {
-    int kg = 0;
-    if (df_sv_check(wf, k, canonical, live, N, iters, lambda, &kg, 0.f)) return DF_E_INVALID;
-    return df_sv_rounds(wf, k, canonical, live, nullptr, N, iters, lambda, kg, 0.f, 1, 0.f, 0.f, dq_out, energy, 2, nullptr, nullptr, stream);
+    SvSolve s = {wf, k, canonical, live, nullptr, N, iters, lambda, 0.f, 0, 0.f, 1, 0.f, 0.f, dq_out, energy, 2, nullptr, nullptr, stream};
+    return df_sv_check(&s) ? DF_E_INVALID : df_sv_rounds(s);
 }
 
 extern "C" int dfusion_warp_solve(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int kg,
                                   float lambda_reg, float* dq_out, float* energy, dfStream stream)
 {
-    if (df_sv_check(wf, k, canonical, live, N, iters, lambda, &kg, lambda_reg)) return DF_E_INVALID;
-    return df_sv_rounds(wf, k, canonical, live, nullptr, N, iters, lambda, kg, lambda_reg, 1, 0.f, 0.f, dq_out, energy, 4, nullptr, nullptr, stream);
+    SvSolve s = {wf, k, canonical, live, nullptr, N, iters, lambda, 0.f, kg, lambda_reg, 1, 0.f, 0.f, dq_out, energy, 4, nullptr, nullptr, stream};
+    return df_sv_check(&s) ? DF_E_INVALID : df_sv_rounds(s);
 }
 
 extern "C" int dfusion_warp_solve_robust(DfWarpField* wf, int k, const float* canonical, const float* live, int N, int iters, float lambda, int kg,
                                          float lambda_reg, int rounds, float tukey_c, float huber_delta, float* dq_out, float* energy,
                                          float* point_weights, float* edge_weights, dfStream stream)
 {
-    if (df_sv_check(wf, k, canonical, live, N, iters, lambda, &kg, lambda_reg)) return DF_E_INVALID;
-    if (rounds < 1 || !(tukey_c >= 0.f) || !(huber_delta >= 0.f) || (edge_weights && kg == 0)) return DF_E_INVALID;
-    return df_sv_rounds(wf, k, canonical, live, nullptr, N, iters, lambda, kg, lambda_reg, rounds, tukey_c, huber_delta, dq_out, energy, 4, point_weights,
-                        edge_weights, stream);
+    SvSolve s = {wf, k, canonical, live, nullptr, N, iters, lambda, 0.f, kg, lambda_reg, rounds, tukey_c, huber_delta, dq_out, energy, 4, point_weights, edge_weights, stream};
+    return df_sv_check(&s) ? DF_E_INVALID : df_sv_rounds(s);
 }
 
 extern "C" int dfusion_warp_solve_plane(DfWarpField* wf, int k, const float* canonical, const float* live, const float* normals, int N, int iters,
                                         float lambda, int kg, float lambda_reg, int rounds, float tukey_c, float huber_delta, float* dq_out,
                                         float* energy, float* point_weights, float* edge_weights, dfStream stream)
 {
-    if (df_sv_check(wf, k, canonical, live, N, iters, lambda, &kg, lambda_reg) || !normals) return DF_E_INVALID;
-    if (rounds < 1 || !(tukey_c >= 0.f) || !(huber_delta >= 0.f) || (edge_weights && kg == 0)) return DF_E_INVALID;
-    return df_sv_rounds(wf, k, canonical, live, normals, N, iters, lambda, kg, lambda_reg, rounds, tukey_c, huber_delta, dq_out, energy, 4,
-                        point_weights, edge_weights, stream);
+    SvSolve s = {wf, k, canonical, live, normals, N, iters, lambda, 0.f, kg, lambda_reg, rounds, tukey_c, huber_delta, dq_out, energy, 4, point_weights, edge_weights, stream};
+    return df_sv_check(&s, normals != nullptr) ? DF_E_INVALID : df_sv_rounds(s);
 }
 
 extern "C" int dfusion_warp_solve_rigid(DfWarpField* wf, int k, const float* canonical, const float* live, const float* normals, int N, int iters,
                                         float lambda, float lambda_rot, int kg, float lambda_reg, int rounds, float tukey_c, float huber_delta,
                                         float* dq_out, float* energy, float* point_weights, float* edge_weights, dfStream stream)
 {
-    if (df_sv_check(wf, k, canonical, live, N, iters, lambda, &kg, lambda_reg) || !(lambda_rot >= 0.f)) return DF_E_INVALID;
-    if (rounds < 1 || !(tukey_c >= 0.f) || !(huber_delta >= 0.f) || (edge_weights && kg == 0)) return DF_E_INVALID;
-    return df_sv_rigid_rounds(wf, k, canonical, live, normals, N, iters, lambda, lambda_rot, kg, lambda_reg, rounds, tukey_c, huber_delta, dq_out, energy,
-                              point_weights, edge_weights, stream);
+    SvSolve s = {wf, k, canonical, live, normals, N, iters, lambda, lambda_rot, kg, lambda_reg, rounds, tukey_c, huber_delta, dq_out, energy, 4, point_weights, edge_weights, stream};
+    return df_sv_check(&s, lambda_rot >= 0.f) ? DF_E_INVALID : df_sv_rigid_rounds(s);
 }
 
 extern "C" int dfusion_warp_node_graph(DfWarpField* wf, int kg, int* nbr, float* alpha, dfStream stream)

@@ -624,24 +624,23 @@ void WarpField::energy_data(const cuda::DeviceArray<float>& canonical_vertices, 
     solve_dq_.create(M * 8); solve_energy_.create(4);      // no-ops after the first frame
     const bool reg = reg_neighbours_ != 0 && reg_lambda_ != 0.f;
     const bool with_normals = point_to_plane_ && canonical_normals.size() >= (size_t)3 * n;
+    const int kg = reg ? reg_neighbours_ : 0;
+    const float lreg = reg ? reg_lambda_ : 0.f;
+    const float *c = canonical_vertices.ptr(), *l = live_vertices.ptr(), *normals = with_normals ? canonical_normals.ptr() : nullptr;
+    float *dq = solve_dq_.ptr(), *energy = track_energy_ ? solve_energy_.ptr() : nullptr;
     if (node_rotations_)                                   // rotations as unknowns too, against the warp itself (setNodeRotations)
-        KF_DF(dfusion_warp_solve_rigid(handle_, k_, canonical_vertices.ptr(), live_vertices.ptr(), with_normals ? canonical_normals.ptr() : nullptr, n,
-                                       solver_iters_, solver_lambda_, rot_lambda_, reg ? reg_neighbours_ : 0, reg ? reg_lambda_ : 0.f, robust_rounds_,
-                                       tukey_c_, huber_delta_, solve_dq_.ptr(), track_energy_ ? solve_energy_.ptr() : nullptr, nullptr, nullptr, nullptr));
+        KF_DF(dfusion_warp_solve_rigid(handle_, k_, c, l, normals, n, solver_iters_, solver_lambda_, rot_lambda_, kg, lreg, robust_rounds_, tukey_c_, huber_delta_,
+                                       dq, energy, nullptr, nullptr, nullptr));
     else if (with_normals)                                 // the data term along the normals (setPointToPlane)
-        KF_DF(dfusion_warp_solve_plane(handle_, k_, canonical_vertices.ptr(), live_vertices.ptr(), canonical_normals.ptr(), n, solver_iters_,
-                                       solver_lambda_, reg ? reg_neighbours_ : 0, reg ? reg_lambda_ : 0.f, robust_rounds_, tukey_c_, huber_delta_,
-                                       solve_dq_.ptr(), track_energy_ ? solve_energy_.ptr() : nullptr, nullptr, nullptr, nullptr));
+        KF_DF(dfusion_warp_solve_plane(handle_, k_, c, l, normals, n, solver_iters_, solver_lambda_, kg, lreg, robust_rounds_, tukey_c_, huber_delta_, dq, energy,
+                                       nullptr, nullptr, nullptr));
     else if (robust_rounds_ > 1 || tukey_c_ != 0.f || huber_delta_ != 0.f)   // robust penalties by re-weighted rounds (setRobust)
-        KF_DF(dfusion_warp_solve_robust(handle_, k_, canonical_vertices.ptr(), live_vertices.ptr(), n, solver_iters_, solver_lambda_,
-                                        reg ? reg_neighbours_ : 0, reg ? reg_lambda_ : 0.f, robust_rounds_, tukey_c_, huber_delta_, solve_dq_.ptr(),
-                                        track_energy_ ? solve_energy_.ptr() : nullptr, nullptr, nullptr, nullptr));
+        KF_DF(dfusion_warp_solve_robust(handle_, k_, c, l, n, solver_iters_, solver_lambda_, kg, lreg, robust_rounds_, tukey_c_, huber_delta_, dq, energy, nullptr,
+                                        nullptr, nullptr));
     else if (reg)                                          // with the regularisation term over the node graph
-        KF_DF(dfusion_warp_solve(handle_, k_, canonical_vertices.ptr(), live_vertices.ptr(), n, solver_iters_, solver_lambda_, reg_neighbours_,
-                                 reg_lambda_, solve_dq_.ptr(), track_energy_ ? solve_energy_.ptr() : nullptr, nullptr));
-    else
-        KF_DF(dfusion_warp_solve_data_term(handle_, k_, canonical_vertices.ptr(), live_vertices.ptr(), n, solver_iters_, solver_lambda_, solve_dq_.ptr(),
-                                           track_energy_ ? solve_energy_.ptr() : nullptr, nullptr));
+        KF_DF(dfusion_warp_solve(handle_, k_, c, l, n, solver_iters_, solver_lambda_, kg, lreg, dq, energy, nullptr));
+    else                                                   // (not through the robust entry point: that one copies two zeros from the host)
+        KF_DF(dfusion_warp_solve_data_term(handle_, k_, c, l, n, solver_iters_, solver_lambda_, dq, energy, nullptr));
     if (track_energy_) {
         solve_energy_.download(last_energy_);
         if (!reg) last_energy_[2] = last_energy_[3] = 0.f;   // (the data term wrote two floats)

@@ -138,8 +138,6 @@ class WarpField:
                                                   capi.floats(aff12(self.warp_to_live_)), _stream()),
                    "dfusion_warp_points")
 
-    # ---- WarpField::energy_data (warp_field.cpp:117-163) / WarpFieldOptimiser::optimiseWarpData: the data term, on the GPU
-
     def debug_counters(self, swept_dev=None):
         """Measurement hook (include/dfusion.h dfusion_warp_debug_counters): while set (device int64[1]), every warped integrate through
         THIS field adds the voxels its launch plan keeps; None switches it off."""
@@ -163,31 +161,45 @@ class WarpField:
         processed in 8x8 pixel tiles per wave; 0 = off.  Results do not change."""
         capi.check(capi.lib().dfusion_warp_set_point_tiling(self.handle, int(image_cols)), "dfusion_warp_set_point_tiling")
 
+    # ---- WarpField::energy_data (warp_field.cpp:117-163) / WarpFieldOptimiser::optimiseWarpData: the warp solves, on the GPU
+    def _solve(self, fn, canonical_dev, live_dev, k, iters, damping, reg=None, robust=None, normals=(), return_weights=False):
+        """What the solves below share.  Calls the C function `fn`(handle, k, canonical, live, *normals, n, iters, *damping, *reg, *robust,
+        dq, energy[, point_weights, edge_weights], stream): `normals` is () where fn takes none, else (tensor or None,); `reg` is None or
+        (reg_neighbours, reg_lambda), with which the energy has 4 entries instead of 2; `robust` is None or (rounds, tukey_c, huber_delta),
+        with which fn has the two weight outputs.  Returns (dq, energy) and, with return_weights, (point_weights, edge_weights or None
+        without edges); the transforms the handle holds are dq from here on."""
+        k = self.k if k is None else k
+        n = int(canonical_dev.shape[0])
+        for nrm in normals:
+            if nrm is not None and int(nrm.numel()) != 3 * n:
+                raise ValueError("one normal per point expected (%d points, normals of shape %s)" % (n, tuple(nrm.shape)))
+        reg = () if reg is None else (int(reg[0]), float(reg[1]))
+        dq = torch.empty((self.M, 8), dtype=torch.float32, device=self.device)
+        en = torch.zeros(4 if reg else 2, dtype=torch.float32, device=self.device)
+        pw = ew = None
+        if return_weights:
+            pw = torch.empty(n, dtype=torch.float32, device=self.device)
+            if reg and reg[0] > 0 and reg[1] != 0.0:
+                ew = torch.empty((self.M, reg[0]), dtype=torch.float32, device=self.device)
+        outs = [dq, en] + ([] if robust is None else [pw, ew])
+        robust = () if robust is None else (int(robust[0]), float(robust[1]), float(robust[2]))
+        capi.check(getattr(capi.lib(), fn)(self.handle, k, _flat(canonical_dev), _flat(live_dev), *[None if t is None else _flat(t) for t in normals], n,
+                                           int(iters), *[float(d) for d in damping], *reg, *robust, *[None if t is None else _ptr(t) for t in outs],
+                                           _stream()), fn)
+        self._dq = dq
+        return (dq, en, pw, ew) if return_weights else (dq, en)
+
     def energy_data(self, canonical_dev, live_dev, iters=100, lam=0.0, k=None):
         """Least-squares update of the node translations so that canonical + sum_i w_i T_i meets live (device [N,3] tensors).
         Returns (dq [M,8] device tensor of the updated transforms, energy [before, after] device tensor)."""
-        k = self.k if k is None else k
-        n = int(canonical_dev.shape[0])
-        dq = torch.empty((self.M, 8), dtype=torch.float32, device=self.device)
-        en = torch.zeros(2, dtype=torch.float32, device=self.device)
-        capi.check(capi.lib().dfusion_warp_solve_data_term(self.handle, k, _flat(canonical_dev), _flat(live_dev), n, int(iters), float(lam),
-                                                           _ptr(dq), _ptr(en), _stream()), "dfusion_warp_solve_data_term")
-        self._dq = dq
-        return dq, en
+        return self._solve("dfusion_warp_solve_data_term", canonical_dev, live_dev, k, iters, (lam,))
 
     def solve(self, canonical_dev, live_dev, iters=100, lam=0.0, reg_neighbours=0, reg_lambda=0.0, k=None):
         """energy_data with DynamicFusion's regularisation term over the node graph (include/dfusion.h dfusion_warp_solve): every node
         is tied to its `reg_neighbours` nearest other nodes with weight `reg_lambda`, so that nodes few or no points constrain follow
         their neighbours.  reg_neighbours = 0 or reg_lambda = 0: energy_data's result.  Returns (dq [M,8] device tensor, energy device
         tensor [E_data before, E_data after, E_reg before, E_reg after])."""
-        k = self.k if k is None else k
-        n = int(canonical_dev.shape[0])
-        dq = torch.empty((self.M, 8), dtype=torch.float32, device=self.device)
-        en = torch.zeros(4, dtype=torch.float32, device=self.device)
-        capi.check(capi.lib().dfusion_warp_solve(self.handle, k, _flat(canonical_dev), _flat(live_dev), n, int(iters), float(lam),
-                                                 int(reg_neighbours), float(reg_lambda), _ptr(dq), _ptr(en), _stream()), "dfusion_warp_solve")
-        self._dq = dq
-        return dq, en
+        return self._solve("dfusion_warp_solve", canonical_dev, live_dev, k, iters, (lam,), (reg_neighbours, reg_lambda))
 
     def solve_robust(self, canonical_dev, live_dev, iters=100, lam=0.0, reg_neighbours=0, reg_lambda=0.0, rounds=3, tukey_c=0.0,
                      huber_delta=0.0, k=None, return_weights=False):
@@ -197,24 +209,8 @@ class WarpField:
         transforms the round starts from.  Returns (dq [M,8] device tensor, energy device tensor [E_data before, E_data after, E_reg
         before, E_reg after]) and, with return_weights, (point_weights [N], edge_weights [M, reg_neighbours] or None without edges): the
         last round's weights -- 0 marks a point the solve ignored."""
-        k = self.k if k is None else k
-        n = int(canonical_dev.shape[0])
-        kg = int(reg_neighbours)
-        dq = torch.empty((self.M, 8), dtype=torch.float32, device=self.device)
-        en = torch.zeros(4, dtype=torch.float32, device=self.device)
-        pw = ew = None
-        if return_weights:
-            pw = torch.empty(n, dtype=torch.float32, device=self.device)
-            if kg > 0 and float(reg_lambda) != 0.0:
-                ew = torch.empty((self.M, kg), dtype=torch.float32, device=self.device)
-        capi.check(capi.lib().dfusion_warp_solve_robust(self.handle, k, _flat(canonical_dev), _flat(live_dev), n, int(iters), float(lam), kg,
-                                                        float(reg_lambda), int(rounds), float(tukey_c), float(huber_delta), _ptr(dq), _ptr(en),
-                                                        _ptr(pw) if pw is not None else None, _ptr(ew) if ew is not None else None,
-                                                        _stream()), "dfusion_warp_solve_robust")
-        self._dq = dq
-        if return_weights:
-            return dq, en, pw, ew
-        return dq, en
+        return self._solve("dfusion_warp_solve_robust", canonical_dev, live_dev, k, iters, (lam,), (reg_neighbours, reg_lambda),
+                           (rounds, tukey_c, huber_delta), return_weights=return_weights)
 
     def solve_plane(self, canonical_dev, live_dev, normals_dev, iters=100, lam=0.0, reg_neighbours=0, reg_lambda=0.0, rounds=1, tukey_c=0.0,
                     huber_delta=0.0, k=None, return_weights=False):
@@ -222,26 +218,8 @@ class WarpField:
         taken along its normal (`normals_dev`, device [N,3], in the frame of the points, used as given), so that a live point that slid
         along the surface -- what projective association leaves -- does not pull on the nodes.  A point with a NaN or infinite normal
         is skipped.  Returns what solve_robust returns; the data energies are those of the projected residual."""
-        k = self.k if k is None else k
-        n = int(canonical_dev.shape[0])
-        if int(normals_dev.numel()) != 3 * n:
-            raise ValueError("one normal per point expected (%d points, normals of shape %s)" % (n, tuple(normals_dev.shape)))
-        kg = int(reg_neighbours)
-        dq = torch.empty((self.M, 8), dtype=torch.float32, device=self.device)
-        en = torch.zeros(4, dtype=torch.float32, device=self.device)
-        pw = ew = None
-        if return_weights:
-            pw = torch.empty(n, dtype=torch.float32, device=self.device)
-            if kg > 0 and float(reg_lambda) != 0.0:
-                ew = torch.empty((self.M, kg), dtype=torch.float32, device=self.device)
-        capi.check(capi.lib().dfusion_warp_solve_plane(self.handle, k, _flat(canonical_dev), _flat(live_dev), _flat(normals_dev), n, int(iters),
-                                                       float(lam), kg, float(reg_lambda), int(rounds), float(tukey_c), float(huber_delta),
-                                                       _ptr(dq), _ptr(en), _ptr(pw) if pw is not None else None,
-                                                       _ptr(ew) if ew is not None else None, _stream()), "dfusion_warp_solve_plane")
-        self._dq = dq
-        if return_weights:
-            return dq, en, pw, ew
-        return dq, en
+        return self._solve("dfusion_warp_solve_plane", canonical_dev, live_dev, k, iters, (lam,), (reg_neighbours, reg_lambda),
+                           (rounds, tukey_c, huber_delta), (normals_dev,), return_weights)
 
     def solve_rigid(self, canonical_dev, live_dev, normals_dev=None, iters=100, lam=0.0, lam_rot=0.0, reg_neighbours=0, reg_lambda=0.0, rounds=1,
                     tukey_c=0.0, huber_delta=0.0, k=None, return_weights=False):
@@ -250,27 +228,8 @@ class WarpField:
         damps the translations.  `canonical_dev` and `normals_dev` are the UNWARPED model points and normals (the solve warps them
         itself); normals_dev None: the point-to-point data term, otherwise the residual along the warped normal.  Returns what
         solve_robust returns; the data energy `after` is that of the warp at the transforms written, not of the linearisation."""
-        k = self.k if k is None else k
-        n = int(canonical_dev.shape[0])
-        if normals_dev is not None and int(normals_dev.numel()) != 3 * n:
-            raise ValueError("one normal per point expected (%d points, normals of shape %s)" % (n, tuple(normals_dev.shape)))
-        kg = int(reg_neighbours)
-        dq = torch.empty((self.M, 8), dtype=torch.float32, device=self.device)
-        en = torch.zeros(4, dtype=torch.float32, device=self.device)
-        pw = ew = None
-        if return_weights:
-            pw = torch.empty(n, dtype=torch.float32, device=self.device)
-            if kg > 0 and float(reg_lambda) != 0.0:
-                ew = torch.empty((self.M, kg), dtype=torch.float32, device=self.device)
-        capi.check(capi.lib().dfusion_warp_solve_rigid(self.handle, k, _flat(canonical_dev), _flat(live_dev),
-                                                       _flat(normals_dev) if normals_dev is not None else None, n, int(iters), float(lam),
-                                                       float(lam_rot), kg, float(reg_lambda), int(rounds), float(tukey_c), float(huber_delta),
-                                                       _ptr(dq), _ptr(en), _ptr(pw) if pw is not None else None,
-                                                       _ptr(ew) if ew is not None else None, _stream()), "dfusion_warp_solve_rigid")
-        self._dq = dq
-        if return_weights:
-            return dq, en, pw, ew
-        return dq, en
+        return self._solve("dfusion_warp_solve_rigid", canonical_dev, live_dev, k, iters, (lam, lam_rot), (reg_neighbours, reg_lambda),
+                           (rounds, tukey_c, huber_delta), (normals_dev,), return_weights)
 
     def node_graph(self, kg):
         """The graph solve() regularises over: (nbr int32 [M, kg], alpha float32 [M, kg]) device tensors -- node i's kg nearest other

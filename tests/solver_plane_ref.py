@@ -47,7 +47,7 @@ def tukey_weights(rho, c2):
 
 
 def data_energy(rho, tukey, c2):
-    """df_sv_plane_energy_kernel: one value per point, thread-strided, then the 1024-tree."""
+    """df_sv_point_energy_kernel: one value per point, thread-strided, then the 1024-tree."""
     with np.errstate(invalid="ignore", over="ignore"):
         s = (rho * rho).astype(F32)
         if tukey:

@@ -15,37 +15,12 @@ import torch
 
 import solver_plane_ref as P
 from dynamicfusion_amd import build, capi
-from test_gpu_solver_reg import bits, dev, field, lcg_problem, random_nodes
-from test_gpu_solver_robust import assert_same, outlier_problem
+from solver_cases import (DF_E_INVALID, HUBER_DELTA, ITERS, LAM, LREG, MODES, N, TUKEY_C, assert_same, bits, dev, field, lcg_normals, lcg_problem,
+                          random_nodes, seeded_normals)
+from solver_cases import shared_plane_problem as shared_problem
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-DF_E_INVALID = 100001
-N = 3001
-TUKEY_C, HUBER_DELTA = 0.05, 0.03
-ITERS, LAM, LREG = 6, 1e-3, 1.0
-
-
-def seeded_normals(n=N, marked=True):
-    """Unit normals; with `marked` some with a NaN or an infinite component (the point is skipped) and some zero (the point stays and
-    adds nothing)."""
-    nrm = np.random.default_rng(17).normal(0, 1, (n, 3))
-    nrm = (nrm / np.linalg.norm(nrm, axis=1, keepdims=True)).astype(F32)
-    if marked:
-        nrm[11::203, 0] = np.nan; nrm[13::307, 2] = np.inf; nrm[19::509, 1] = -np.inf; nrm[23::401] = 0
-    return nrm
-
-
-_problems = {}
-
-
-def shared_problem(M):
-    """test_gpu_solver_reg's problem (random twists, a smooth 3 cm displacement, NaN points) with every 7th live point thrown 0.3 m off
-    and the seeded normals."""
-    if M not in _problems:
-        pos = random_nodes(M)
-        _problems[M] = (pos,) + outlier_problem(pos) + (seeded_normals(),)
-    return _problems[M]
 
 
 def run_gpu(wf, src, dst, nrm, k, kg, lreg, rounds, c, delta, iters=ITERS, lam=LAM):
@@ -55,7 +30,6 @@ def run_gpu(wf, src, dst, nrm, k, kg, lreg, rounds, c, delta, iters=ITERS, lam=L
     return [None if t is None else t.cpu().numpy() for t in out]
 
 
-MODES = {"off": (0.0, 0.0), "tukey": (TUKEY_C, 0.0), "huber": (0.0, HUBER_DELTA), "both": (TUKEY_C, HUBER_DELTA)}
 GRID = [
     # M,    k, kg, rounds, mode        step kernel
     (40,    8, 4, 3, "both"),        # register-resident, 2 elements a thread
@@ -252,19 +226,9 @@ def test_invalid_arguments():
 
 
 # ------------------------------------------------------------------------------------------------ the C++ mirror
-def lcg_normals(n):
-    """host/apps/plane_solve.cpp's normals: its second generator, the same float arithmetic."""
-    s = 2463534242
-    out = np.empty(3 * n, np.uint32)
-    for i in range(3 * n):
-        s = (s * 1664525 + 1013904223) & 0xFFFFFFFF
-        out[i] = s >> 8
-    return (F32(2) * (out.astype(F32) * F32(1.0 / 16777216.0)) - F32(1)).reshape(n, 3)
-
-
 def test_cxx_mirror_prints_the_restatements_bits():
     build.build_host()
-    r = subprocess.run([build.HOST_PLANE_SOLVE], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([build.HOST_WARP_SOLVE, "plane"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [[int(w, 16) for w in line.split()] for line in r.stdout.strip().splitlines()]
     got_dq, got_en = np.array(lines[:-1], np.uint32), np.array(lines[-1], np.uint32)

@@ -9,25 +9,11 @@ import pytest
 import torch
 
 import solver_reg_ref as R
-from dynamicfusion_amd import WarpField, build, capi, synth
+from dynamicfusion_amd import build, capi
+from solver_cases import DF_E_INVALID, bits, dev, field, lcg_problem, problem, random_nodes
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-DF_E_INVALID = 100001
-
-
-def bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def field(pos, sigma, dq=None, k=8):
-    wf = WarpField(k=k)
-    wf.init(pos, sigma=sigma, transforms=dq)
-    return wf
 
 
 # ------------------------------------------------------------------------------------------------ node sets
@@ -85,22 +71,6 @@ def test_graph_equals_the_restatement(name):
 
 
 # ------------------------------------------------------------------------------------------------ the solve
-def problem(pos, N, seed=11):
-    """As tests/test_gpu_solver.py's parity test: random twists as transforms, a smooth displacement with noise, NaNs sprinkled."""
-    M = len(pos)
-    rng = np.random.default_rng(seed)
-    sigma = rng.uniform(0.3, 0.6, M).astype(F32)
-    dq = synth.dq_from_twist(rng.uniform(-0.05, 0.05, (M, 3)).astype(F32), rng.uniform(-0.02, 0.02, (M, 3)).astype(F32))
-    src = rng.uniform(-1, 1, (N, 3)).astype(F32)
-    dst = (src + 0.03 * np.sin(4 * src) + rng.normal(0, 1e-3, (N, 3))).astype(F32)
-    src[::97] = np.nan; dst[5::131, 2] = np.nan
-    return sigma, dq, src, dst
-
-
-def random_nodes(M, seed=12):
-    return np.random.default_rng(seed).uniform(-1, 1, (M, 3)).astype(F32)
-
-
 SOLVE_CASES = [
     ("baseline", lambda: random_nodes(100), 5003, 8, 4, 40, 0.0, 0.5),
     ("damped-kg7", lambda: random_nodes(257), 5003, 4, 7, 25, 1e-3, 2.0),
@@ -230,36 +200,10 @@ def test_invalid_arguments():
 
 
 # ------------------------------------------------------------------------------------------------ the C++ mirror
-def lcg_problem():
-    """The inputs of host/apps/reg_solve.cpp: the same 32-bit generator, the same float arithmetic."""
-    state = [12345]
-
-    def unit(n):
-        out = np.empty(n, np.uint32)
-        s = state[0]
-        for i in range(n):
-            s = (s * 1664525 + 1013904223) & 0xFFFFFFFF
-            out[i] = s >> 8
-        state[0] = s
-        return out.astype(F32) * F32(1.0 / 16777216.0)
-    M, N = 50, 1000
-    pos = (F32(2) * unit(3 * M) - F32(1)).reshape(M, 3)
-    dq = np.zeros((M, 8), F32); sigma = np.empty(M, F32)
-    for i in range(M):
-        u = unit(5)
-        dq[i, 0] = 0.96; dq[i, 1 + i % 3] = 0.28
-        dq[i, 4:] = (u[:4] - F32(0.5)) * F32(0.0625)
-        sigma[i] = F32(0.25) + F32(0.25) * u[4]
-    u = unit(6 * N).reshape(N, 3, 2)
-    src = F32(2) * u[:, :, 0] - F32(1)
-    dst = src + (u[:, :, 1] - F32(0.5)) * F32(0.0625)
-    return pos, dq, sigma, np.ascontiguousarray(src, F32), np.ascontiguousarray(dst, F32)
-
-
 @pytest.mark.parametrize("kg,lreg", [(4, 1.0), (0, 0.0)], ids=["regularised", "off"])
 def test_cxx_mirror_prints_the_python_mirrors_bits(kg, lreg):
     build.build_host()
-    r = subprocess.run([build.HOST_REG_SOLVE, str(kg), str(lreg)], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([build.HOST_WARP_SOLVE, "reg", str(kg), str(lreg)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     got = np.array([[int(w, 16) for w in line.split()] for line in r.stdout.strip().splitlines()], np.uint32)
     pos, dq, sigma, src, dst = lcg_problem()

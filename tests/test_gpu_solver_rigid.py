@@ -15,17 +15,13 @@ import solver_plane_ref as P
 import solver_rigid_ref as G
 import solver_robust_ref as RR
 from dynamicfusion_amd import WarpField, capi
-from test_gpu_solver_plane import seeded_normals, shared_problem
-from test_gpu_solver_reg import bits, dev, field, random_nodes
-from test_gpu_solver_robust import assert_same
+from solver_cases import (DF_E_INVALID, HUBER_DELTA, ITERS, LAM, LREG, LROT, MODES, N, TUKEY_C, assert_same, bits, dev, field, lcg_normals, lcg_problem,
+                          random_nodes, seeded_normals)
+from solver_cases import shared_plane_problem as shared_problem
 from test_gpu_ties import index_volume
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-DF_E_INVALID = 100001
-N = 3001
-TUKEY_C, HUBER_DELTA = 0.05, 0.03
-ITERS, LAM, LROT, LREG = 6, 1e-3, 1e-2, 1.0
 
 
 def run_gpu(wf, src, dst, nrm, k, kg, lreg, rounds, c, delta, iters=ITERS, lam=LAM, lrot=LROT):
@@ -39,7 +35,6 @@ def restated(pos, dq, sigma, src, dst, nrm, k, kg, lreg, rounds, c, delta, iters
     return G.solve_rigid(pos, dq, sigma, src, dst, nrm, k, iters, lam, lrot, kg, lreg, rounds, c, delta, details=details)
 
 
-MODES = {"off": (0.0, 0.0), "tukey": (TUKEY_C, 0.0), "huber": (0.0, HUBER_DELTA), "both": (TUKEY_C, HUBER_DELTA)}
 GRID = [
     # M,    k, kg, rounds, mode, normals     step kernel, on 2 M entries
     (40,    8, 4, 3, "both", True),        # register-resident, 2 elements a thread
@@ -246,13 +241,11 @@ def test_invalid_arguments():
 
 # ------------------------------------------------------------------------------------------------ the C++ mirror
 def test_cxx_mirror_prints_the_restatements_bits():
-    """host/apps/rigid_solve.cpp: plane_solve.cpp's seeded problem through WarpField::setNodeRotations + energy_data."""
+    """host/apps/warp_solve.cpp rigid: the plane mode's seeded problem through WarpField::setNodeRotations + energy_data."""
     import subprocess
     from dynamicfusion_amd import build
-    from test_gpu_solver_plane import lcg_normals
-    from test_gpu_solver_reg import lcg_problem
     build.build_host()
-    r = subprocess.run([build.HOST_RIGID_SOLVE], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([build.HOST_WARP_SOLVE, "rigid"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [[int(w, 16) for w in line.split()] for line in r.stdout.strip().splitlines()]
     got_dq, got_en = np.array(lines[:-1], np.uint32), np.array(lines[-1], np.uint32)

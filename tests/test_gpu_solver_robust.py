@@ -13,36 +13,13 @@ import numpy as np
 import pytest
 import torch
 
-import solver_reg_ref as R
 import solver_robust_ref as RR
-from dynamicfusion_amd import WarpField, build, capi
-from test_gpu_solver_reg import bits, dev, field, lcg_problem, problem, random_nodes
+from dynamicfusion_amd import build, capi
+from solver_cases import (DF_E_INVALID, HUBER_DELTA, ITERS, LAM, LREG, MODES, N, TUKEY_C, assert_same, bits, dev, field, lcg_problem, outlier_problem,
+                          problem, random_nodes, shared_problem)
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-DF_E_INVALID = 100001
-N = 3001
-TUKEY_C, HUBER_DELTA = 0.05, 0.03
-ITERS, LAM, LREG = 6, 1e-3, 1.0
-
-
-def outlier_problem(pos, n=N):
-    """test_gpu_solver_reg's problem (random twists, a smooth 3 cm displacement, NaNs) with every 7th live point thrown 0.3 m off."""
-    sigma, dq, src, dst = problem(pos, n)
-    d = np.random.default_rng(5).normal(0, 1, (n, 3))
-    d = (0.3 * d / np.linalg.norm(d, axis=1, keepdims=True)).astype(F32)
-    dst[::7] = dst[::7] + d[::7]
-    return sigma, dq, src, dst
-
-
-_problems = {}
-
-
-def shared_problem(M):
-    if M not in _problems:
-        pos = random_nodes(M)
-        _problems[M] = (pos,) + outlier_problem(pos)
-    return _problems[M]
 
 
 def run_gpu(wf, src, dst, k, kg, lreg, rounds, c, delta, iters=ITERS, lam=LAM):
@@ -52,18 +29,6 @@ def run_gpu(wf, src, dst, k, kg, lreg, rounds, c, delta, iters=ITERS, lam=LAM):
     return [None if t is None else t.cpu().numpy() for t in out]
 
 
-def assert_same(got, want, what):
-    g_dq, g_en, g_pw, g_ew = got
-    r_dq, r_en, r_pw, r_ew = want
-    assert np.array_equal(bits(g_pw), bits(r_pw)), what + ": point weights"
-    assert (g_ew is None) == (r_ew is None)
-    if r_ew is not None:
-        assert np.array_equal(bits(g_ew), bits(r_ew)), what + ": edge weights"
-    assert np.array_equal(bits(g_en), bits(r_en)), what + ": energies %s against %s" % (g_en, r_en)
-    assert np.array_equal(bits(g_dq), bits(r_dq)), what + ": transforms"
-
-
-MODES = {"tukey": (TUKEY_C, 0.0), "huber": (0.0, HUBER_DELTA), "both": (TUKEY_C, HUBER_DELTA)}
 GRID = [
     # M,    k, kg, rounds, mode
     (40,    8, 4, 3, "both"),
@@ -266,7 +231,7 @@ def test_the_data_term_entry_point_writes_two_energies():
 # ------------------------------------------------------------------------------------------------ the C++ mirror
 def test_cxx_mirror_prints_the_python_mirrors_bits():
     build.build_host()
-    r = subprocess.run([build.HOST_ROBUST_SOLVE], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([build.HOST_WARP_SOLVE, "robust"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [[int(w, 16) for w in line.split()] for line in r.stdout.strip().splitlines()]
     got_dq, got_en = np.array(lines[:-1], np.uint32), np.array(lines[-1], np.uint32)

@@ -9,8 +9,7 @@ import nonrigid_loop as NL
 import plane_loop as PL
 import solver_plane_ref as P
 import solver_reg_ref as R
-from dynamicfusion_amd import synth
-from test_solver_reg_rule import bits, random_problem
+from solver_cases import bits, planted_slip, random_problem
 
 F32 = np.float32
 
@@ -35,38 +34,7 @@ def test_normals_along_x_give_the_point_to_point_x_translations():
 
 
 # ------------------------------------------------------------------------------------------------ (2) the planted slip
-LAM, SLIP = 1e-3, 0.01
-
-
-def planted_slip():
-    """M = 60 nodes and N = 1500 points on the 60 degree cap of the unit sphere around +z (k = 8, sigma in [0.3, 0.6], identity
-    transforms, normals = the points).  A smooth radial field T_i = a(pos_i) pos_i is planted, scaled so that no point moves more than
-    9.9 mm; a live point is its canonical point moved by the field's blend and then slipped 1 cm along the surface: the tangential
-    part of the fixed direction t = (1, 0.3, 0) / |.|."""
-    M, N, k = 60, 1500, 8
-    rng = np.random.default_rng(211)
-
-    def cap(n):
-        z = rng.uniform(0.5, 1.0, n)                                     # uniform on the cap: z = cos(theta) in [cos 60, 1]
-        phi = rng.uniform(0, 2 * np.pi, n)
-        s = np.sqrt(1 - z * z)
-        return np.stack([s * np.cos(phi), s * np.sin(phi), z], 1).astype(F32)
-    pos, src = cap(M), cap(N)
-    sigma = rng.uniform(0.3, 0.6, M).astype(F32)
-    dq = synth.identity_dq(M)
-    normals = src.copy()
-    w, keys, _, _ = R.setup(pos, dq, sigma, src, src, k)
-    p64 = pos.astype(np.float64)
-    a = 1.0 + 0.5 * np.sin(2.0 * p64[:, 0] + 0.3) * np.cos(1.5 * p64[:, 1] - 0.2)
-    shape = a[:, None] * p64
-    blend = np.einsum("nk,nkc->nc", w.astype(np.float64), shape[keys])
-    amp = 0.0099 / float(np.linalg.norm(blend, axis=1).max())
-    planted, blend = amp * shape, amp * blend
-    n64 = normals.astype(np.float64)
-    t = np.array([1.0, 0.3, 0.0]); t /= np.linalg.norm(t)
-    slip = SLIP * (t - (n64 @ t)[:, None] * n64)
-    live = (src.astype(np.float64) + blend + slip).astype(F32)
-    return pos, dq, sigma, src, live, normals, planted, blend
+LAM = 1e-3
 
 
 def tangential(v, n):

@@ -7,25 +7,9 @@ import pytest
 import oracle_lib as O
 import solver_reg_ref as R
 from dynamicfusion_amd import synth
+from solver_cases import bits, random_problem
 
 F32 = np.float32
-
-
-def bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
-
-
-def random_problem(M, N, seed=11, nans=True):
-    """The problem of test_gpu_solver.test_matches_oracle_bit_for_bit: random nodes with random twists, a smooth displacement, NaNs."""
-    rng = np.random.default_rng(seed)
-    pos = rng.uniform(-1, 1, (M, 3)).astype(F32)
-    sigma = rng.uniform(0.3, 0.6, M).astype(F32)
-    dq = synth.dq_from_twist(rng.uniform(-0.05, 0.05, (M, 3)).astype(F32), rng.uniform(-0.02, 0.02, (M, 3)).astype(F32))
-    src = rng.uniform(-1, 1, (N, 3)).astype(F32)
-    dst = (src + 0.03 * np.sin(4 * src) + rng.normal(0, 1e-3, (N, 3))).astype(F32)
-    if nans:
-        src[::97] = np.nan; dst[5::131, 2] = np.nan
-    return pos, dq, sigma, src, dst
 
 
 # ------------------------------------------------------------------------------------------------ pinned to the oracle

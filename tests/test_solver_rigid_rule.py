@@ -9,8 +9,7 @@ import solver_plane_ref as P
 import solver_reg_ref as R
 import solver_rigid_ref as G
 from dynamicfusion_amd import synth
-from test_solver_plane_rule import planted_slip
-from test_solver_reg_rule import bits, random_problem
+from solver_cases import bits, planted_slip, random_problem
 
 F32 = np.float32
 

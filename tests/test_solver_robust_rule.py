@@ -6,7 +6,7 @@ import numpy as np
 import solver_reg_ref as R
 import solver_robust_ref as RR
 from dynamicfusion_amd import synth
-from test_solver_reg_rule import bits, random_problem
+from solver_cases import bits, random_problem
 
 F32 = np.float32
 

@@ -6,8 +6,8 @@ Wall times around a device synchronise, medians of REPEATS after two warm-up rou
   the rigid solve (WarpField.solve_rigid, with the normals, one round, quadratic penalties) at 40 and at 0 steps on this tree.
 A conjugate-gradient step is (40 steps - 0 steps) / 40; the 0-step call is what a round costs around its steps (for the rigid solve: two
 warps of the points, the k-NN, the lists, the write-back).  Every measurement runs in a child process of its own (one library per
-process); this tree and the parent library alternate, SESSIONS times each.  The summary says whether this tree's `solve_plane` lies
-within the parent's own range across its processes, and within that range widened by its width on either side, and on which side it
+process); this tree and the parent library alternate, SESSIONS times each.  The summary says whether this tree's `solve_plane` and
+`solve_rigid` lie within the parent's own range across its processes, and within that range widened by its width on either side, and on which side it
 lies when outside; it gives the rigid step as a ratio to the parent's plane step.
 Writes one JSON line to --out (default profiles/solver_rigid_probe.json).
 Usage: tools/solver_rigid_probe.py [REPEATS] [--parent-lib FILE] [--out FILE] [--sessions N]"""
@@ -67,7 +67,7 @@ def child(lib, reps):
 
 
 def summarise(res, parent):
-    """The figures of the run side by side, and for `solve_plane` where this tree's median lies against the parent's processes: inside
+    """The figures of the run side by side, and for `solve_plane` and `solve_rigid` where this tree's median lies against the parent's processes: inside
     their own range [min, max] ("within_parent_range"), inside that range widened by its width on either side (a few sessions are a
     small sample of it; "within_widened_range"), and on which side when outside."""
     med = lambda a: float(np.median(a))  # noqa: E731
@@ -82,7 +82,8 @@ def summarise(res, parent):
         "rigid_step_us_tree": col(res["tree"], "step_us", "rigid"),
     }
     if parent:
-        for name, table, key in (("plane_40_ms", "median_ms", "plane_40"), ("plane_step_us", "step_us", "plane")):
+        for name, table, key in (("plane_40_ms", "median_ms", "plane_40"), ("plane_step_us", "step_us", "plane"),
+                                 ("rigid_40_ms", "median_ms", "rigid_40"), ("rigid_step_us", "step_us", "rigid")):
             p, t = col(res["parent"], table, key), med(col(res["tree"], table, key))
             spread = max(p) - min(p)
             summary[name + "_against_parent"] = {
