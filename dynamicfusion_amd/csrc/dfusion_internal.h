@@ -10,15 +10,12 @@
 #include "dfusion_nanoflann.h"
 
 #define DF_BRICK 8                    // k-NN index brick edge (voxels)
-// Look-ahead margin of the warped sweep's verdict pass (metres): blocks that would be alive with every cull radius widened by this much
-// get their tables / blend models made on the handle's side stream before a sweep needs them.  A camera turning 0.25 degrees per frame
-// moves a voxel 2 m from its axis by 9 mm, the benchmark's warp amplitude moves the cull radii by up to 2 cm per frame: 5 cm is two to
-// five frames of lead, and widens the set that is ever built by a few per cent.
-#define DF_WARP_PREFETCH_MARGIN_M 0.05f
 #define DF_WARP_PREFETCH_CAP 1024u    // look-ahead table builds per frame at most: about one round of the resident build grid (50-80 us beside the sweep)
+#define DF_REPORT_NONE 1u             // the host report words before any plan kernel has reported: assume work (df_side_init, df_block_verdicts)
 
 #define DF_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return (int)e__; } while (0)
 #define DF_LAUNCH_CHECK() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
+#define DF_TRY(expr) do { int rc__ = (expr); if (rc__) return rc__; } while (0)      // a DF_* / HIP code from one of the library's own functions
 
 static inline DfSlab df_slab_or_full(const DfVolume& v, const DfSlab* s)
 {
@@ -77,6 +74,69 @@ struct DfDevBuf {
     }
 };
 
+// The per-block buffers of the warped sweep's verdict pass, in the three groups they are reserved in.  reserve(nblk) zeroes the group's
+// capacity first and sets it last, so cap > 0 says that EVERY buffer of the group holds cap blocks; a failure part-way leaves cap == 0
+// and the next reserve makes all of them again.  Nothing else frees or shrinks them: ready(n) stands for "n <= cap and
+// no pointer of the group is null".
+struct DfBlockState {          // with the tables (df_build_voxel_table)
+    DfDevBuf<uint8_t> state;   // 0 = tables not built (DF_INDEX_TABLES_ON_DEMAND), 1 = built, 2 = built and a blend-model record written
+    DfDevBuf<uint8_t> tie;     // 1 = the block's table build met two exactly equidistant candidates (topk_insert's tie branch): its table
+                               // depends on the tie tree, and a rebuilt tree (dfusion_warp_extend) may reorder them anywhere
+    DfDevBuf<float> wmax;      // max over the block's voxels of the weight sum (0 until built)
+    DfDevBuf<uint8_t> alive, alive_prev;   // this frame's verdicts and those of the pass before (every pass swaps the two)
+    DfDevBuf<uint32_t> work;   // [3][cap] the frame's urgent-build / look-ahead-build / model work lists
+    size_t cap = 0;
+    bool ready(size_t n) const { return n <= cap; }
+    int reserve(size_t n)
+    {
+        if (ready(n)) return DF_OK;
+        cap = 0;
+        DF_TRY(state.reserve(n)); DF_TRY(tie.reserve(n)); DF_TRY(wmax.reserve(n)); DF_TRY(alive.reserve(n)); DF_TRY(alive_prev.reserve(n));
+        DF_TRY(work.reserve(3 * n));
+        cap = n; return DF_OK;
+    }
+};
+#define DF_BM_NU 16                   // entries per block model (dfusion_warp_blocks.h defines the same)
+struct DfBlockModels {         // block blend models, with the first model: entry-major [DF_BM_NU][cap] node ids, {mid, half width} half
+    DfDevBuf<uint16_t> idx; DfDevBuf<uint32_t> lam, w; DfDevBuf<uint8_t> cnt;   // pairs of the normalised and of the raw weights, entry counts
+    size_t cap = 0;
+    bool ready(size_t n) const { return n <= cap; }
+    int reserve(size_t n)
+    {
+        if (ready(n)) return DF_OK;
+        cap = 0;
+        DF_TRY(idx.reserve(n * DF_BM_NU)); DF_TRY(lam.reserve(n * DF_BM_NU)); DF_TRY(w.reserve(n * DF_BM_NU)); DF_TRY(cnt.reserve(n));
+        cap = n; return DF_OK;
+    }
+};
+// 4-bit neighbour codes (k = 8), per 4 x 4 x 4 SUB-block so that they exist at any node density: per voxel of a block the model pass has
+// visited, its k neighbours as positions in the union list of its sub-block (ascending node ids, <= 16).  With them, because the same pass
+// writes them, the sub-blocks' own blend models and this frame's sub-verdicts.
+struct DfBlockCodes {
+    DfDevBuf<uint32_t> ids;    // [block][64] entry q * 16 + e = union entry e of column quadrant q (x >> 2 & 1 | (y >> 2 & 1) << 1), low half word for
+                               // planes 0-3 of the block, high half word for planes 4-7 -- the dword a sweep lane loads to refill its wave's copies
+    DfDevBuf<uint32_t> tab;    // one u32 per voxel, tile-major like the tables but PATCH-major inside a tile plane
+    DfDevBuf<uint8_t> coded;   // [block] 1 = every sub-block's union fits 16 entries and the codes are written
+    DfDevBuf<uint32_t> sub_lam, sub_w;   // [block][DF_BM_NU][sub] the intervals of a sub-block's union entries over its 64 voxels (sub = 4 h + q)
+    DfDevBuf<uint16_t> sub_cnt;          // [block * 8 + sub] entries | reference entry << 8
+    DfDevBuf<uint8_t> sub_ok;            // [block] 1 = the block has sub-block models
+    DfDevBuf<uint8_t> blk_sub;           // [block] bit 4 h + q = the sub-block may update this frame (0xff where not judged)
+    DfDevBuf<uint32_t> sub_list;         // the blocks to judge
+    size_t cap = 0;
+    bool ready(size_t n) const { return n <= cap; }
+    int reserve(size_t n, hipStream_t st)      // coded and sub_ok zeroed on `st`
+    {
+        if (ready(n)) return DF_OK;
+        cap = 0;
+        DF_TRY(ids.reserve(n * 64)); DF_TRY(tab.reserve(n * 512)); DF_TRY(coded.reserve(n));
+        DF_HIP(hipMemsetAsync(coded, 0, n, st));
+        DF_TRY(sub_lam.reserve(n * 8 * DF_BM_NU)); DF_TRY(sub_w.reserve(n * 8 * DF_BM_NU)); DF_TRY(sub_cnt.reserve(n * 8)); DF_TRY(sub_ok.reserve(n));
+        DF_TRY(blk_sub.reserve(n)); DF_TRY(sub_list.reserve(n));
+        DF_HIP(hipMemsetAsync(sub_ok, 0, n, st));
+        cap = n; return DF_OK;
+    }
+};
+
 struct DfPrepared;                             // (dfusion_warp.hip)
 
 struct __attribute__((visibility("hidden"))) DfWarpField {     // (opaque in dfusion.h: the library exports none of its members)
@@ -101,8 +161,8 @@ struct __attribute__((visibility("hidden"))) DfWarpField {     // (opaque in dfu
     // device scalars for the conservative brick cull: [0] max |t_i|, [1] max sin(theta_i/2), [2] max dists
     DfDevBuf<float> bounds_dev;
     int max_phase = 0;                // which of bounds_dev[6], [7] this frame's capped pyramid leaves the image-wide maximum in
-    // dfusion_integrate_warped_prepare / _sweep (round 5): the launch state a prepare call leaves for the sweep call (opaque here: the
-    // argument structs live in dfusion_warp_sweep.h), and the two events that order the halves when they are issued on different streams
+    // dfusion_integrate_warped_prepare / _sweep: the planned launch a prepare call leaves for the sweep call (opaque here: the argument
+    // structs live in dfusion_warp_sweep.h), and the events that order the halves when they are issued on different streams
     std::unique_ptr<DfPrepared> prep; bool prep_valid = false;
     hipEvent_t ev_prep_done = nullptr, ev_sweep_done[2] = {}; bool split_events = false;
     // What a sweep issued through the split API may still be READING when the next frame's set_transforms / prepare arrive on another
@@ -132,35 +192,14 @@ struct __attribute__((visibility("hidden"))) DfWarpField {     // (opaque in dfu
     DfDevBuf<DfNfNode> nf_nodes; DfDevBuf<uint16_t> nf_vpos; bool nf_ok = false; int nf_depth = 0;
     // pipelined warped sweep: the launch plan (verdict masks of the strip items, the alive ones sorted by work), dfusion_warp.hip
     DfDevBuf<unsigned int> plan_hist; size_t plan_cap = 0;
-    // per 8x8x8 block of the table planes (dfusion_warp_blocks.h; block grid blk_nbx x blk_nby x tab_zn / 8, whole table tiles):
-    //   blk_state  0 = tables not built (DF_INDEX_TABLES_ON_DEMAND), 1 = built, 2 = built and a blend-model record written
-    //   blk_wmax   max over the block's voxels of the weight sum (0 until built)
-    //   blk_alive  this frame's verdicts ; blk_work [3][blk_cap] the frame's urgent-build / look-ahead-build / model work lists ;
-    //   blk_cnt [2 sets][8] their lengths and the build passes' cursors (the sets alternate between passes: each pass zeroes the other one)
-    // block blend models: entry-major [DF_BM_NU][blk_cap] node ids, {mid, half width} half pairs of the normalised and of the raw
-    // weights (allocated with the first model), bm_cnt entry counts
-    DfDevBuf<uint8_t> blk_state; DfDevBuf<float> blk_wmax; DfDevBuf<uint8_t> blk_alive; DfDevBuf<uint32_t> blk_work, blk_cnt; size_t blk_cap = 0; int blk_phase = 0;
-    // blk_tie [block] 1 = the block's table build met two exactly equidistant candidates (topk_insert's tie branch): its table depends on
-    // the tie tree, and a rebuilt tree (dfusion_warp_extend) may reorder them anywhere
-    DfDevBuf<uint8_t> blk_tie;
-    DfDevBuf<uint16_t> bm_idx; DfDevBuf<uint32_t> bm_lam, bm_w; DfDevBuf<uint8_t> bm_cnt; size_t bm_cap = 0;
-    // 4-bit neighbour codes (round 5; round 6: per 4 x 4 x 4 SUB-block, so that they exist at any node density): per voxel of a block
-    // the model pass has visited, its k neighbours as positions in the union list of its sub-block (ascending node ids, <= 16).
-    //   bm_ids   [block][64] u32: entry q * 16 + e = union entry e of column quadrant q (x >> 2 & 1 | (y >> 2 & 1) << 1), low half
-    //            word for planes 0-3 of the block, high half word for planes 4-7 -- the dword a sweep lane loads to refill its wave's copies
-    //   bm_coded [block] 1 = every sub-block's union fits 16 entries and the codes are written
-    //   code_tab one u32 per voxel, tile-major like the tables but PATCH-major inside a tile plane
-    DfDevBuf<uint32_t> code_tab; size_t code_cap = 0; DfDevBuf<uint32_t> bm_ids; DfDevBuf<uint8_t> bm_coded;
-    // sub-block blend models (k = 8; reserved and voided with the codes: the same pass writes them) and this frame's sub-verdicts:
-    //   bm_sub_lam, bm_sub_w [block][DF_BM_NU][sub] the intervals of a sub-block's union entries over its 64 voxels (sub = 4 h + q)
-    //   bm_sub_cnt [block * 8 + sub] entries | reference entry << 8 ; bm_sub_ok [block] 1 = the block has them
-    //   blk_sub [block] bit 4 h + q = the sub-block may update this frame (0xff where not judged) ; sub_list the blocks to judge ;
-    //   blk_alive_prev the verdicts of the pass before (the two arrays are swapped by every pass)
-    DfDevBuf<uint32_t> bm_sub_lam, bm_sub_w; DfDevBuf<uint16_t> bm_sub_cnt; DfDevBuf<uint8_t> bm_sub_ok, blk_sub, blk_alive_prev; DfDevBuf<uint32_t> sub_list;
+    // per 8x8x8 block of the table planes (dfusion_warp_blocks.h; block grid over whole table tiles x tab_zn / 8), in three groups that
+    // are reserved -- and, when a reservation fails, voided -- together (above)
+    DfBlockState blk; DfBlockModels bm; DfBlockCodes codes;
+    DfDevBuf<uint32_t> blk_cnt; int blk_phase = 0;   // [2 sets][8] the work lists' lengths and the build passes' cursors (the sets alternate between passes: each pass zeroes the other one)
     bool tab_complete = false;   // every block's tables are built
     int tab_sweeps = 0;          // sweeps over the current tables so far (the models are made from the second one on)
     unsigned long long* dbg_swept = nullptr;   // dfusion_warp_debug_counters: nullable device counter (the caller's) the sweeps through this handle add to
-    bool alive_valid = false;    // blk_alive holds the verdicts of a sweep over the current tables (dfusion_warp_alive_blocks)
+    bool alive_valid = false;    // blk.alive holds the verdicts of a sweep over the current tables (dfusion_warp_alive_blocks)
     // look-ahead work (tables / models of blocks a sweep does not need yet) runs on a side stream the handle owns, beside the sweep on
     // the caller's stream: ev_fork (caller's stream, after the verdict pass) releases it, ev_join (side stream, after its last kernel)
     // is waited for by the next call that touches the tables

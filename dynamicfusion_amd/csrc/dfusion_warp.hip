@@ -1,21 +1,18 @@
 // dfusion_warp.hip -- the north-star kernel's translation unit: per-voxel dual-quaternion blend fused into the projective TSDF update
 // (dfusion_integrate_warped and its prepare / sweep halves), with the per-voxel table build, the verdict pass and the launch plan.
 // The handle and its node arrays are dfusion_warp_nodes.hip, point queries dfusion_warp_points.hip, the brick index and the growth path
-// dfusion_warp_index.hip; the kernels launched here are dfusion_warp_sweep.h, dfusion_warp_blocks.h and dfusion_warp_pipe.h.
+// dfusion_warp_index.hip; the kernels launched here are dfusion_warp_sweep.h, dfusion_warp_blocks.h and dfusion_warp_pipe.h, the two
+// host decisions (which sweep, where the verdict pass's optional work runs) dfusion_warp_decide.h.
 //
 // Replaces (on device) /root/reference/kfusion/src/warp_field.cpp:180-251 (KNN / weighting / DQB /
 // warp), the nanoflann kd-tree it queries (warp_field.cpp:275-282), and composes them with
 // kfusion/src/cuda/tsdf_volume.cu:77-104.
-//
-// MI355X design notes
-//   * integrate_warped: one 256-thread workgroup per brick; candidate positions (+sigma) are
-//     staged in LDS once per brick and read back with broadcast ds_read_b128; each lane keeps the
-//     running top-k of its voxel in registers.
 #include "dfusion_internal.h"
 #include "dfusion_pyramid.h"
 #include "dfusion_warp_sweep.h"
 #include "dfusion_warp_blocks.h"
 #include "dfusion_warp_pipe.h"
+#include "dfusion_warp_decide.h"
 #include <algorithm>
 #include <atomic>
 #include <stdlib.h>
@@ -80,13 +77,13 @@ __global__ __launch_bounds__(256) void df_alive_per_layer_kernel(const uint8_t* 
 static int df_count_verdicts(DfWarpField* wf, unsigned mask, int z0, int zn, unsigned long long* per_layer_dev, int n_layers, dfStream stream)
 {
     if (!wf || !per_layer_dev || n_layers <= 0 || z0 < 0 || zn < 0) return DF_E_INVALID;
-    if (!wf->tab_valid || !wf->alive_valid || !wf->blk_alive) return DF_E_NO_INDEX;
+    if (!wf->tab_valid || !wf->alive_valid || !wf->blk.alive) return DF_E_NO_INDEX;
     const int ntx = (wf->geom_dims[0] + DF_TAB_TX - 1) / DF_TAB_TX, nty = (wf->geom_dims[1] + DF_TAB_TY - 1) / DF_TAB_TY;
     const unsigned per_layer = (unsigned)(ntx * (DF_TAB_TX / 8)) * (unsigned)(nty * (DF_TAB_TY / 8));
     const int nbz = wf->tab_zn / 8, layer0 = wf->tab_z0 / 8;
     const int l_lo = (z0 + 7) / 8, l_hi = min((z0 + zn) / 8, n_layers);                 // layers entirely inside [z0, z0 + zn)
     if (nbz <= 0 || l_hi <= l_lo) return DF_OK;
-    hipLaunchKernelGGL(df_alive_per_layer_kernel, dim3((unsigned)nbz), dim3(256), 0, (hipStream_t)stream, wf->blk_alive, mask, per_layer, layer0, l_lo,
+    hipLaunchKernelGGL(df_alive_per_layer_kernel, dim3((unsigned)nbz), dim3(256), 0, (hipStream_t)stream, wf->blk.alive, mask, per_layer, layer0, l_lo,
                        l_hi, per_layer_dev);
     DF_LAUNCH_CHECK();
     return DF_OK;
@@ -109,7 +106,7 @@ DfWarpedArgs df_table_args(const DfWarpField* wf)
     const int ntx = (wf->geom_dims[0] + DF_TAB_TX - 1) / DF_TAB_TX, nty = (wf->geom_dims[1] + DF_TAB_TY - 1) / DF_TAB_TY;
     a.w_tab = wf->w_tab_valid ? wf->w_tab : nullptr;
     a.tile_wmax = wf->w_tab_valid ? wf->tile_wmax : nullptr;
-    a.blk_wmax = wf->w_tab_valid ? wf->blk_wmax : nullptr;
+    a.blk_wmax = wf->w_tab_valid ? wf->blk.wmax : nullptr;
     a.X = wf->geom_dims[0]; a.Y = wf->geom_dims[1]; a.Z = wf->geom_dims[2];
     a.z_store0 = wf->tab_z0; a.z_own0 = wf->tab_z0; a.z_own_n = wf->tab_zn;        // every voxel of the covered bricks gets an entry
     a.vsx = wf->geom_vs[0]; a.vsy = wf->geom_vs[1]; a.vsz = wf->geom_vs[2];
@@ -118,15 +115,14 @@ DfWarpedArgs df_table_args(const DfWarpField* wf)
     a.tab_nvox = (size_t)ntx * DF_TAB_TX * nty * DF_TAB_TY * wf->tab_zn;
     a.bz0 = wf->tab_z0 / DF_BRICK;
     a.bm_nbx = ntx * (DF_TAB_TX / 8); a.bm_nby = nty * (DF_TAB_TY / 8);
-    a.code_tab = wf->code_tab; a.bm_ids = wf->bm_ids; a.bm_coded = wf->bm_coded;
-    if (wf->bm_sub_lam && wf->bm_sub_w && wf->bm_sub_cnt && wf->bm_sub_ok) {
-        a.bm_sub_lam = wf->bm_sub_lam; a.bm_sub_w = wf->bm_sub_w; a.bm_sub_cnt = wf->bm_sub_cnt; a.bm_sub_ok = wf->bm_sub_ok;
-    }
-    a.blk_tie = wf->blk_tie;
+    const DfBlockCodes& c = wf->codes;
+    a.code_tab = c.tab; a.bm_ids = c.ids; a.bm_coded = c.coded;
+    if (c.sub_lam && c.sub_w && c.sub_cnt && c.sub_ok) { a.bm_sub_lam = c.sub_lam; a.bm_sub_w = c.sub_w; a.bm_sub_cnt = c.sub_cnt; a.bm_sub_ok = c.sub_ok; }
+    a.blk_tie = wf->blk.tie;
     return a;
 }
-// LDS a workgroup may ask for on this device (160 KiB on gfx950), what the node-table kernels' "fits" is decided against (the
-// dynamic-LDS attribute used to be a fixed 160 KiB, which fails on a part with less whatever the launch needs)
+// LDS a workgroup may ask for on this device (160 KiB on gfx950): what the node-table kernels' "fits" is decided against, and the
+// dynamic-LDS attribute of their launches (a fixed 160 KiB fails on a part with less, whatever the launch needs)
 static size_t df_lds_limit()
 {
     static std::atomic<size_t> cached{0};
@@ -156,7 +152,7 @@ static unsigned df_work_grid(const void* kernel)
 static int df_build_listed(DfWarpField* wf, const uint32_t* cnt, hipStream_t st, int list = 0)
 {
     DfWarpedArgs b = df_table_args(wf);
-    b.work = wf->blk_work + (size_t)list * wf->blk_cap; b.work_cnt = cnt + (list ? 3 : 0); b.work_cursor = const_cast<uint32_t*>(cnt) + (list ? 4 : 2);
+    b.work = wf->blk.work + (size_t)list * wf->blk.cap; b.work_cnt = cnt + (list ? 3 : 0); b.work_cursor = const_cast<uint32_t*>(cnt) + (list ? 4 : 2);
     b.work_cap = list ? DF_WARP_PREFETCH_CAP : 0u;
     const DfWarpView W = df_view(wf);
     static unsigned grid[9] = {0};
@@ -176,91 +172,63 @@ int df_tables_complete(DfWarpField* wf, hipStream_t st)
     const DfWarpedArgs b = df_table_args(wf);
     const int nbz = wf->tab_zn / 8;
     const size_t nblk = (size_t)b.bm_nbx * b.bm_nby * nbz;
-    uint32_t* cnt = wf->blk_cnt + 8 * wf->blk_phase;
-    uint32_t* cnt_next = wf->blk_cnt + 8 * (wf->blk_phase ^ 1);
+    uint32_t* cnt = wf->blk_cnt + 8 * wf->blk_phase, *cnt_next = wf->blk_cnt + 8 * (wf->blk_phase ^ 1);
     hipLaunchKernelGGL(df_blocks_unbuilt_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, b.bm_nbx, b.bm_nby, nbz, wf->bx, wf->by,
-                       wf->tab_z0 / 8, wf->blk_state, wf->blk_work, cnt, cnt_next);
+                       wf->tab_z0 / 8, wf->blk.state, wf->blk.work, cnt, cnt_next);
     DF_LAUNCH_CHECK();
     wf->blk_phase ^= 1;
-    int rc = df_build_listed(wf, cnt, st);
-    if (rc) return rc;
+    DF_TRY(df_build_listed(wf, cnt, st));
     wf->tab_complete = true;
     return DF_OK;
 }
 
+// blend models for the blocks on the verdict pass's model list (length cnt[1])
+static int df_model_listed(DfWarpField* wf, int k, int nbx, int nby, int nbz, uint32_t* cnt, hipStream_t st)
+{
+    const DfWarpedArgs b = df_table_args(wf);
+    uint32_t* list_model = wf->blk.work + 2 * wf->blk.cap;
+    static unsigned g8 = 0, g4 = 0;
+    if (!g8) { g8 = df_work_grid((const void*)df_block_model_kernel<8>); g4 = df_work_grid((const void*)df_block_model_kernel<4>); }
+    if (k == 8) hipLaunchKernelGGL(df_block_model_kernel<8>, dim3(g8), dim3(256), 0, st, b, nbx, nby, nbz, list_model, cnt + 1,
+                                   wf->bm.idx, wf->bm.lam, wf->bm.w, wf->bm.cnt, wf->blk.state);
+    else hipLaunchKernelGGL(df_block_model_kernel<4>, dim3(g4), dim3(256), 0, st, b, nbx, nby, nbz, list_model, cnt + 1,
+                            wf->bm.idx, wf->bm.lam, wf->bm.w, wf->bm.cnt, wf->blk.state);
+    DF_LAUNCH_CHECK();
+    return DF_OK;
+}
+
 // The verdict pass of the pipelined sweep (dfusion_warp_blocks.h) and the on-demand work it finds: table builds for alive blocks that
-// have none yet, blend models for alive blocks that have tables but no model (from the second sweep over the tables on, so that a node
-// set that changes every frame never pays for models; `now` = from the first).
+// have none yet, blend models for alive blocks that have tables but no model; what is made, and on which stream, is df_verdict_policy's.
 static int df_block_verdicts(DfWarpField* wf, DfWarpedArgs& a, int k, unsigned flags, hipStream_t st)
 {
     const int nbx = a.tab_ntx * (DF_TAB_TX / 8), nby = a.tab_nty * (DF_TAB_TY / 8), nbz = wf->tab_zn / 8;
     const size_t nblk = (size_t)nbx * nby * nbz;
-    if (nblk == 0 || nblk > wf->blk_cap) return DF_E_INVALID;
-    const bool use_models = !(flags & DF_WARP_NO_BLOCK_MODEL) && (k == 8 || k == 4);
-    const int want_models = !use_models ? 0 : (flags & DF_WARP_BLOCK_MODEL_NOW) ? 2 : wf->tab_sweeps >= 1 ? 1 : 0;
-    if (want_models && nblk > wf->bm_cap) {
-        wf->bm_cap = 0;
-        { int rc = wf->bm_idx.reserve(nblk * DF_BM_NU); if (rc) return rc; }
-        { int rc = wf->bm_lam.reserve(nblk * DF_BM_NU); if (rc) return rc; }
-        { int rc = wf->bm_w.reserve(nblk * DF_BM_NU); if (rc) return rc; }
-        { int rc = wf->bm_cnt.reserve(nblk); if (rc) return rc; }
-        wf->bm_cap = nblk;
-    }
-    // 4-bit neighbour codes + the sub-blocks' union lists (the sweep reads them at k = 8 only: no 4 bytes a voxel for the others)
-    // ... and the sub-blocks' own blend models, 2 x 4 bytes per union entry: what the sub-verdicts judge half layers by
-    if (want_models && k == 8 && (nblk * 512 > wf->code_cap || !wf->bm_ids || !wf->code_tab || !wf->bm_coded || !wf->bm_sub_lam || !wf->bm_sub_w ||
-                                  !wf->bm_sub_cnt || !wf->bm_sub_ok || !wf->blk_sub || !wf->sub_list)) {
-        wf->code_cap = 0;
-        { int rc = wf->bm_ids.reserve(nblk * 64); if (rc) return rc; }
-        { int rc = wf->code_tab.reserve(nblk * 512); if (rc) return rc; }
-        { int rc = wf->bm_coded.reserve(nblk); if (rc) return rc; }
-        DF_HIP(hipMemsetAsync(wf->bm_coded, 0, nblk, st));
-        { int rc = wf->bm_sub_lam.reserve(nblk * 8 * DF_BM_NU); if (rc) return rc; }
-        { int rc = wf->bm_sub_w.reserve(nblk * 8 * DF_BM_NU); if (rc) return rc; }
-        { int rc = wf->bm_sub_cnt.reserve(nblk * 8); if (rc) return rc; }
-        { int rc = wf->bm_sub_ok.reserve(nblk); if (rc) return rc; }
-        { int rc = wf->blk_sub.reserve(nblk); if (rc) return rc; }
-        { int rc = wf->sub_list.reserve(nblk); if (rc) return rc; }
-        DF_HIP(hipMemsetAsync(wf->bm_sub_ok, 0, nblk, st));
-        wf->code_cap = nblk * 512;
-    }
-    // look-ahead: with on-demand tables or models still to make, blocks NEAR the alive set get theirs on the side
-    // stream while the sweep runs -- unless the caller wants models made at once (then everything stays on the launch stream, in order)
-    bool ahead = !(flags & (DF_WARP_NO_PREFETCH | DF_WARP_BLOCK_MODEL_NOW));
-    if (ahead) { int rc = df_side_init(wf); if (rc) return rc; }
-    // The side stream costs a fork and a join (~13 us of barrier packets per frame): worth it while blocks are being built or modelled,
-    // not on a scene at rest.  Whether anything was listed lately comes from the plan kernel's host report -- read without a
-    // synchronisation, so it may be frames old; it only decides WHERE optional work runs.  On from the first sweeps over new tables,
-    // while the last report listed anything, and every 8th sweep as a probe (a camera that starts to move is picked up by the urgent
-    // list at once, by the look-ahead within the report's age).
-    // (The unsynchronised read makes WHICH frame switches the side stream off depend on host / GPU timing -- never a result, but the
-    // swept-voxel counter and frame times of a run.  DF_WARP_STEADY_PREFETCH keeps the look-ahead on in every frame: what tests and
-    // measurements that compare such counters between runs pass -- ADVICE r4.)
-    if (ahead && !(flags & DF_WARP_STEADY_PREFETCH) && wf->tab_sweeps >= 8 && (wf->tab_sweeps & 7) != 0 && wf->host_report &&
-        wf->host_report[0] == 0u && wf->host_report[1] == 0u && wf->host_report[2] == 0u) ahead = false;
-    const bool quiet = !ahead && !(flags & (DF_WARP_NO_PREFETCH | DF_WARP_BLOCK_MODEL_NOW));      // a frame at rest: optional work waits for the next probe
-    const int want_models_policy = want_models;
-    const int want_models_now = quiet ? 0 : want_models_policy;
-    // (not on the very first sweep over new tables: the urgent build of the whole alive set is the frame then, and a node set that
-    // changes every frame never pays for look-ahead work)
-    a.pf_margin = ahead && !wf->tab_complete && wf->tab_sweeps >= 1 ? DF_WARP_PREFETCH_MARGIN_M : 0.f;
-    a.pf_cap = DF_WARP_PREFETCH_CAP;
-    uint32_t* cnt = wf->blk_cnt + 8 * wf->blk_phase;
-    uint32_t* cnt_next = wf->blk_cnt + 8 * (wf->blk_phase ^ 1);
-    uint32_t* list_urgent = wf->blk_work, *list_ahead = wf->blk_work + wf->blk_cap, *list_model = wf->blk_work + 2 * wf->blk_cap;
+    if (nblk == 0 || !wf->blk.ready(nblk)) return DF_E_INVALID;
+    // The plan kernel's host report is read without a synchronisation, so it may be frames old; it only decides WHERE optional work runs:
+    // never a result, but the swept-voxel counter and frame times of a run (comparisons between runs pass DF_WARP_STEADY_PREFETCH).
+    uint32_t report[3] = {DF_REPORT_NONE, DF_REPORT_NONE, DF_REPORT_NONE};    // (what df_side_init, below, would leave in a new one)
+    if (wf->host_report) for (int i = 0; i < 3; ++i) report[i] = wf->host_report[i];
+    const DfVerdictPolicy p = df_verdict_policy(flags, k, wf->tab_sweeps, wf->tab_complete, report);
+    if (p.want_models) DF_TRY(wf->bm.reserve(nblk));
+    if (p.want_models && k == 8) DF_TRY(wf->codes.reserve(nblk, st));
+    if (p.ahead || p.quiet) DF_TRY(df_side_init(wf));                   // (a quiet frame keeps the side stream for the next probe)
+    a.pf_margin = p.pf_margin; a.pf_cap = DF_WARP_PREFETCH_CAP;
+    uint32_t* cnt = wf->blk_cnt + 8 * wf->blk_phase, *cnt_next = wf->blk_cnt + 8 * (wf->blk_phase ^ 1);
+    uint32_t* list_urgent = wf->blk.work, *list_ahead = wf->blk.work + wf->blk.cap, *list_model = wf->blk.work + 2 * wf->blk.cap;
     // sub-verdicts (k = 8): the kept blocks that have sub-block models and touch the dead set are listed and judged per 4 x 4 x 4 sub-block
     // right after the pass.  The verdict bytes alternate between two arrays: the pass reads its neighbours' verdicts of the frame before.
-    std::swap(wf->blk_alive, wf->blk_alive_prev);
-    const bool codes_exist = k == 8 && wf->bm_cnt && wf->code_tab && wf->bm_ids && wf->bm_coded && wf->code_cap >= nblk * 512;
-    const bool sub_verdicts = use_models && wf->bm_cap >= nblk && codes_exist && !(flags & DF_WARP_NO_SUB_VERDICT) && wf->bm_sub_lam && wf->bm_sub_w &&
-                              wf->bm_sub_cnt && wf->bm_sub_ok && wf->blk_sub && wf->sub_list && wf->blk_alive_prev;
-    if (sub_verdicts) { a.bm_ids = wf->bm_ids; a.bm_sub_lam = wf->bm_sub_lam; a.bm_sub_w = wf->bm_sub_w; a.bm_sub_cnt = wf->bm_sub_cnt; a.bm_sub_ok = wf->bm_sub_ok; }
+    std::swap(wf->blk.alive, wf->blk.alive_prev);
+    const DfBlockCodes& c = wf->codes;
+    const bool models = p.use_models && wf->bm.ready(nblk);
+    const bool codes_exist = k == 8 && wf->bm.cnt && c.ready(nblk);
+    const bool sub_verdicts = models && codes_exist && !(flags & DF_WARP_NO_SUB_VERDICT);
+    if (sub_verdicts) { a.bm_ids = c.ids; a.bm_sub_lam = c.sub_lam; a.bm_sub_w = c.sub_w; a.bm_sub_cnt = c.sub_cnt; a.bm_sub_ok = c.sub_ok; }
     hipLaunchKernelGGL(df_block_verdict_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, a, wf->rot, wf->node_t, nbx, nby, nbz,
-                       wf->blk_state, wf->blk_wmax, wf->brick_thr + wf->off_cap, wf->bx, wf->by, a.tile_wmax != nullptr ? 1 : 0,
-                       (use_models && wf->bm_cap >= nblk ? 1 : 0) | (codes_exist ? 2 : 0) | (sub_verdicts ? 4 : 0),     // (bit 1: the blocks' codes exist; bit 2: sub-verdicts follow)
-                       want_models_now,
-                       wf->tab_complete ? 0 : 1, wf->bm_idx, wf->bm_lam, wf->bm_w, wf->bm_cnt, wf->bm_coded, wf->blk_alive, list_urgent, list_ahead, list_model,
-                       cnt, cnt_next, sub_verdicts ? (uint8_t*)wf->blk_sub : nullptr, wf->sub_list, wf->blk_alive_prev);
+                       wf->blk.state, wf->blk.wmax, wf->brick_thr + wf->off_cap, wf->bx, wf->by, a.tile_wmax != nullptr ? 1 : 0,
+                       (models ? 1 : 0) | (codes_exist ? 2 : 0) | (sub_verdicts ? 4 : 0),     // (bit 1: the blocks' codes exist; bit 2: sub-verdicts follow)
+                       p.want_models_now,
+                       wf->tab_complete ? 0 : 1, wf->bm.idx, wf->bm.lam, wf->bm.w, wf->bm.cnt, c.coded, wf->blk.alive, list_urgent, list_ahead, list_model,
+                       cnt, cnt_next, sub_verdicts ? (uint8_t*)c.blk_sub : nullptr, c.sub_list, wf->blk.alive_prev);
     a.blk_cnt = cnt; a.host_report = (uint32_t*)wf->host_report; a.sweep_no = (uint32_t)wf->tab_sweeps;
     DF_LAUNCH_CHECK();
 #ifdef DF_TRACE_VERDICT
@@ -273,31 +241,16 @@ static int df_block_verdicts(DfWarpField* wf, DfWarpedArgs& a, int k, unsigned f
     }
 #endif
     wf->blk_phase ^= 1;
-    // (every frame: running this pass only every 4th frame saved its 4.6 us launch and cost 3 % more swept voxels, 18 us, on a moving camera)
-    auto launch_models = [&](hipStream_t s2) -> int {
-        const DfWarpedArgs b = df_table_args(wf);
-        static unsigned g8 = 0, g4 = 0;
-        if (!g8) {
-            g8 = df_work_grid((const void*)df_block_model_kernel<8>); g4 = df_work_grid((const void*)df_block_model_kernel<4>);
-        }
-        if (k == 8) hipLaunchKernelGGL(df_block_model_kernel<8>, dim3(g8), dim3(256), 0, s2, b, nbx, nby, nbz, list_model, cnt + 1,
-                                       wf->bm_idx, wf->bm_lam, wf->bm_w, wf->bm_cnt, wf->blk_state);
-        else hipLaunchKernelGGL(df_block_model_kernel<4>, dim3(g4), dim3(256), 0, s2, b, nbx, nby, nbz, list_model, cnt + 1,
-                                wf->bm_idx, wf->bm_lam, wf->bm_w, wf->bm_cnt, wf->blk_state);
-        DF_LAUNCH_CHECK();
-        return DF_OK;
-    };
-    const bool side_work = ahead && (!wf->tab_complete || want_models_now);
-    if (side_work) {
+    if (p.side_work) {
         // fork: the side stream starts once the verdict pass has written the lists; its kernels touch only blocks this frame's sweep
         // does not read (near, not alive) or structures the sweep never reads (model records, state bytes)
         DF_HIP(hipEventRecord(wf->ev_fork, st));
         DF_HIP(hipStreamWaitEvent(wf->side, wf->ev_fork, 0));
         // from here on the side stream may hold kernels that write tables, state bytes and model records: whatever fails below, the next
-        // call must not touch them before those kernels are done (an early return used to leave the fork unjoined)
+        // call must not touch them before those kernels are done
         int rc_side = DF_OK;
         if (!wf->tab_complete) rc_side = df_build_listed(wf, cnt, wf->side, 1);
-        if (rc_side == DF_OK && want_models_now) rc_side = launch_models(wf->side);
+        if (rc_side == DF_OK && p.want_models_now) rc_side = df_model_listed(wf, k, nbx, nby, nbz, cnt, wf->side);
         if (hipEventRecord(wf->ev_join, wf->side) == hipSuccess) wf->side_pending = true;      // joined by the next call that touches the tables
         else { (void)hipGetLastError(); df_side_drain(wf); if (rc_side == DF_OK) rc_side = (int)hipErrorUnknown; }
         if (rc_side != DF_OK) return rc_side;
@@ -306,37 +259,248 @@ static int df_block_verdicts(DfWarpField* wf, DfWarpedArgs& a, int k, unsigned f
         // (it reads models of blocks whose state was 2 when the verdict pass ran -- none that this frame's side-stream model builds write.
         // The list's length stays on the device: at most 1024 workgroups stride over it, those past its end return at once.)
         const unsigned sub_grid = (unsigned)std::min<size_t>((nblk * 8 + 255) / 256, 1024);
-        hipLaunchKernelGGL(df_sub_verdict_kernel, dim3(sub_grid), dim3(256), 0, st, a, wf->rot, wf->node_t, nbx, nby, nbz, wf->sub_list, cnt + 5, wf->blk_sub);
+        hipLaunchKernelGGL(df_sub_verdict_kernel, dim3(sub_grid), dim3(256), 0, st, a, wf->rot, wf->node_t, nbx, nby, nbz, c.sub_list, cnt + 5, c.blk_sub);
         DF_LAUNCH_CHECK();
-        a.blk_sub = wf->blk_sub;
+        a.blk_sub = c.blk_sub;
     }
-    if (!wf->tab_complete) { int rc = df_build_listed(wf, cnt, st, 0); if (rc) return rc; }      // urgent: before this frame's sweep
-    if (want_models_now && !ahead) { int rc = launch_models(st); if (rc) return rc; }
-    a.blk_alive = wf->blk_alive; a.bm_nbx = nbx; a.bm_nby = nby;
-    wf->alive_valid = true;
+    if (!wf->tab_complete) DF_TRY(df_build_listed(wf, cnt, st, 0));                            // urgent: before this frame's sweep
+    if (p.want_models_now && !p.ahead) DF_TRY(df_model_listed(wf, k, nbx, nby, nbz, cnt, st));
+    a.blk_alive = wf->blk.alive; a.bm_nbx = nbx; a.bm_nby = nby; wf->alive_valid = true;
     return DF_OK;
 }
 
-// The launch state dfusion_integrate_warped_prepare leaves for dfusion_integrate_warped_sweep
+// A planned launch of the batched or the pipelined sweep (a.plan_mask set: pipelined) and the geometry it was planned for: what
+// df_integrate_warped_impl hands to df_launch_prepared, on the whole call's stack or, from a prepare call to its sweep call, in the handle.
 typedef void (*df_lds_kernel_t)(const DfWarpedArgs, const DfWarpView, int);
 struct DfPrepared { DfWarpedArgs a; DfWarpView W; df_lds_kernel_t kern; dim3 grid; unsigned threads; size_t lds; int tiles_x; DfVolume v; DfSlab s; unsigned long long seq; };
 DfWarpField::DfWarpField() = default;
 DfWarpField::~DfWarpField() = default;
-enum { DF_MODE_WHOLE = 0, DF_MODE_PREPARE = 1 };
+static_assert(DF_DECIDE_PIPE_WGT == DF_PIPE_WGT && DF_DECIDE_LDS_ZT == DF_LDS_ZT && DF_ROW_TZ == DF_BRICK, "constants repeated in dfusion_warp_decide.h / assumed below");
 
-static int df_integrate_warped_impl(const uint16_t* dists, size_t pitch, int cols, int rows, DfVolume v, const DfSlab* slab,
+// The pipelined sweep's launch plan: verdict masks of all strip items (one wave each), the alive ones sorted by work; then one workgroup per
+// 2 (4) plan entries: P.grid, sized for every strip (nothing is read back; the workgroups past the plan's end return at once).
+static int df_pipe_plan(DfWarpField* wf, DfPrepared& P, int tiles_y, int k, unsigned flags, hipStream_t st)
+{
+    DfWarpedArgs& a = P.a;
+    const unsigned n_items = (unsigned)P.tiles_x * (unsigned)tiles_y * 2u * P.grid.y;
+    // The plan lives in TWO sets of (masks, bins), used alternately, and its bin counters in FOUR, each plan kernel zeroing the set of
+    // the plan after next: a sweep issued through the split API may still be reading its plan while the next frame's is made.
+    if (n_items > wf->plan_cap) {
+        DF_TRY(df_wait_all_sweeps_host(wf));
+        wf->plan_cap = 0;
+        for (int i = 0; i < 2; ++i) {
+            DF_TRY(wf->plan_mask2[i].reserve((size_t)n_items * 2));
+            DF_TRY(wf->plan_list2[i].reserve((size_t)n_items * DF_PLAN_BINS));      // the bins
+            DF_TRY(wf->plan_code2[i].reserve(n_items));
+        }
+        wf->plan_cap = n_items; wf->plan_reader[0] = wf->plan_reader[1] = 0;
+    }
+    if (!wf->plan_hist) {
+        DF_TRY(wf->plan_hist.reserve(4 * 128));
+        DF_HIP(hipMemsetAsync(wf->plan_hist, 0, 4 * 128 * sizeof(unsigned int), st));
+        wf->hphase = 0;
+    }
+    wf->pphase ^= 1;
+    DF_TRY(df_wait_reader(wf, wf->plan_reader[wf->pphase], st));      // (the sweep two plans ago)
+    if (a.cull) DF_TRY(df_block_verdicts(wf, a, k, flags, st));
+    else DF_TRY(df_tables_complete(wf, st));                          // (no verdicts: every block's tables)
+    ++wf->tab_sweeps;
+    unsigned int* cnt = wf->plan_hist + 128 * (wf->hphase & 3u);
+    unsigned int* cnt_next = wf->plan_hist + 128 * ((wf->hphase + 2u) & 3u);       // (last read by the sweep two plans ago: waited for above)
+    unsigned long long* pmask = wf->plan_mask2[wf->pphase]; unsigned int* plist = wf->plan_list2[wf->pphase];
+    // 4-bit neighbour codes (k = 8): for the cells whose block the model pass has been over, unless the models are switched off
+    unsigned long long* pcode = nullptr;
+    const DfBlockCodes& c = wf->codes;
+    if (k == 8 && a.cull && a.blk_alive && c.tab && c.ids && c.coded && wf->bm.cap >= (size_t)a.bm_nbx * a.bm_nby * (wf->tab_zn / 8) &&
+        !(flags & (DF_WARP_NO_BLOCK_MODEL | DF_WARP_NO_CODES))) {
+        pcode = wf->plan_code2[wf->pphase];
+        a.code_tab = c.tab; a.bm_ids = c.ids; a.bm_coded = c.coded;
+    }
+    hipLaunchKernelGGL(df_sweep_plan_kernel, dim3((n_items + DF_PLAN_WG / 64 - 1) / (DF_PLAN_WG / 64)), dim3(DF_PLAN_WG), 0, st, a, P.tiles_x, tiles_y, n_items, pmask, cnt,
+                       plist, cnt_next, pcode);
+    DF_LAUNCH_CHECK();
+    ++wf->hphase;                                                  // (only once the kernel that zeroes the set after next is in the stream)
+    a.plan_code = pcode; a.plan_mask = pmask; a.plan_bins = plist; a.plan_cnt = cnt; a.plan_items = n_items; a.plan_tiles_y = tiles_y;
+    // this plan's sweep: its number, and what it will read
+    wf->plan_reader[wf->pphase] = wf->node_reader[wf->nphase] = ++wf->seq;
+    const unsigned spw = P.threads >= 256u ? P.threads / 256u : 1u;
+    P.grid = dim3((n_items + spw - 1) / spw, 1);
+    return DF_OK;
+}
+
+// The argument checks of dfusion_integrate_warped and of its prepare half (include/dfusion.h); *s = the slab to sweep, z_own_n == 0: none.
+static int df_warped_check(const uint16_t* dists, size_t pitch, int cols, int rows, const DfVolume& v, const DfSlab* slab, const float vol2world[12],
+                           const float world2cam[12], const float proj[4], const DfWarpField* wf, int k, DfSlab* s)
+{
+    if (!dists || !vol2world || !world2cam || !proj || !wf || cols <= 0 || rows <= 0 || !df_pitch_ok(pitch, cols, 2) || !df_volume_valid(v)) return DF_E_INVALID;
+    if (k < 1 || k > 8 || wf->M < k) return DF_E_INVALID;
+    *s = df_slab_or_full(v, slab);
+    if (!df_slab_valid(v, *s)) return DF_E_INVALID;
+    if (!wf->index_valid || wf->k_built < k || memcmp(wf->geom_dims, v.dims, sizeof(wf->geom_dims)) ||
+        memcmp(wf->geom_vs, v.voxel_size, sizeof(wf->geom_vs)) || memcmp(wf->geom_aff, vol2world, sizeof(wf->geom_aff)))
+        return DF_E_NO_INDEX;
+    return DF_OK;
+}
+
+// Everything of a warped integrate that does not touch the volume, on `st`.  Which sweep runs is decided ONCE (df_warp_variant), before the
+// pyramid build; then the pyramid, the verdict pass with its builds and the launch plan are enqueued and P is filled.  P.kern stays null for
+// the brick and table-rows variants, which only the whole call launches.  `pipelined_only` (the prepare half: the split exists for the
+// cached, pipelined sweep only) refuses every other variant at the decision.
+static int df_integrate_warped_impl(const uint16_t* dists, size_t pitch, int cols, int rows, const DfVolume& v, const DfSlab& s,
                                     const float vol2world[12], const float world2cam[12], const float proj[4],
-                                    DfWarpField* wf, int k, unsigned flags, unsigned long long* n_updated, dfStream stream, int mode);
+                                    DfWarpField* wf, int k, unsigned flags, hipStream_t st, bool pipelined_only, DfPrepared& P)
+{
+    DF_TRY(df_side_join(wf, st));                             // the previous call's look-ahead builds (tables, models, state bytes)
+    wf->prep_valid = false;                                   // (a prepared plan that was never swept is void once the handle's scratch is rewritten)
+    const int tiles_x = (v.dims[0] + DF_ROW_TX - 1) / DF_ROW_TX, tiles_y = (v.dims[1] + DF_LDS_TY - 1) / DF_LDS_TY;       // (batched and pipelined kernels)
+    const int zt_lo = s.z_own0 / DF_ROW_TZ, layers = (s.z_own0 + s.z_own_n - 1) / DF_ROW_TZ - zt_lo + 1;
+    const bool tables_cover = wf->tab_valid && wf->tab_k == k && s.z_own0 >= wf->tab_z0 && s.z_own0 + s.z_own_n <= wf->tab_z0 + wf->tab_zn;
+    const size_t lds_limit = df_lds_limit();
+    const DfWarpVariant d = df_warp_variant(k, wf->M, flags, tables_cover, wf->w_tab_valid, pitch, rows, (unsigned long long)v.dims[0] * v.dims[1],
+                                            lds_limit, (long long)tiles_x * tiles_y * layers);
+    const bool use_tab = d.kind != DF_SWEEP_BRICKS, lds_rows = d.kind == DF_SWEEP_LDS_ROWS, pipelined = d.kind == DF_SWEEP_PIPELINED;
+    if (pipelined_only && !pipelined) return DF_E_INVALID;
+
+    DfWarpedArgs& a = P.a;
+    memset(&a, 0, sizeof(a));
+    a.X = v.dims[0]; a.Y = v.dims[1]; a.Z = v.dims[2];
+    a.z_store0 = s.z_store0; a.z_own0 = s.z_own0; a.z_own_n = s.z_own_n;
+    a.vsx = v.voxel_size[0]; a.vsy = v.voxel_size[1]; a.vsz = v.voxel_size[2];
+    a.vol2world = df_aff(vol2world); a.world2cam = df_aff(world2cam);
+    static const float I9[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    a.v2w_identity = memcmp(vol2world, I9, sizeof(I9)) == 0;         // bitwise: -0 entries do not qualify
+    a.P.dists = dists; a.P.pitch = pitch; a.P.cols = cols; a.P.rows = rows;
+    a.P.fx = proj[0]; a.P.fy = proj[1]; a.P.cx = proj[2]; a.P.cy = proj[3];
+    a.P.trunc = v.trunc_dist; a.P.trunc_inv = 1.f / v.trunc_dist; a.P.max_weight = v.max_weight;
+    a.sat_ok = df_sat_trunc_ok(v.trunc_dist) ? 1 : 0; a.n_swept = wf->dbg_swept;
+    a.kf = (float)k; a.cam_scale = 1.f; a.origin_cam = -1.f;
+    if (use_tab) {
+        a.knn_tab = wf->knn_tab; a.tab_z0 = wf->tab_z0;
+        a.tab_ntx = (a.X + DF_TAB_TX - 1) / DF_TAB_TX; a.tab_nty = (a.Y + DF_TAB_TY - 1) / DF_TAB_TY;
+        a.tab_nvox = (size_t)a.tab_ntx * DF_TAB_TX * a.tab_nty * DF_TAB_TY * wf->tab_zn;
+    }
+    if (d.weights) a.w_tab = wf->w_tab;
+    if (!(flags & DF_WARP_NO_CULL) && proj[0] > 0.f && proj[1] > 0.f) {
+        if (!(flags & DF_WARP_NO_DEPTH_PYRAMID)) {
+            DF_TRY(wf->pyr_mem.reserve(df_pyramid_elems(cols, rows)));
+            // the pipelined sweep reads the pyramid in its verdict pass only, and its plan kernel re-arms the image-maximum word: levels
+            // 1..5 in ONE launch; the other kernels take the full pyramid (two launches).  TWO such words ([6], [7]), used alternately: a
+            // call that returns early between its pyramid build and its plan kernel leaves ITS word dirty -- the next call uses the other
+            // one (zeroed by the plan kernel before), and that call's plan kernel cleans both (no memset node per frame).
+            wf->max_phase ^= 1;
+            unsigned int* max_word = (unsigned int*)(wf->bounds_dev + 6 + wf->max_phase);
+            DF_TRY(df_build_dists_pyramid(dists, pitch, cols, rows, wf->pyr_mem, wf->pyr_mem.cap, &a.py, st, pipelined, nullptr, pipelined ? max_word : nullptr));
+        }
+        if (a.py.top == 0) {                                      // no pyramid (switched off, or an image under 32 px): the image-wide maximum alone
+            DF_HIP(hipMemsetAsync(wf->bounds_dev + 2, 0, sizeof(float), st));
+            hipLaunchKernelGGL(df_dists_max_kernel, dim3(64), dim3(256), 0, st, dists, pitch, cols, rows, wf->bounds_dev + 2);
+            DF_LAUNCH_CHECK();
+        }
+        {   // world2cam rigid (R^T R = I to 1e-5)?  Then the distance bound of df_tile_culled holds with |world2cam.t|.
+            bool rigid = true;
+            for (int i = 0; i < 3 && rigid; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    double dot = 0.0;
+                    for (int r = 0; r < 3; ++r) dot += (double)world2cam[3 * r + i] * world2cam[3 * r + j];
+                    if (!(fabs(dot - (i == j ? 1.0 : 0.0)) < 1e-5)) { rigid = false; break; }
+                }
+            a.origin_cam = rigid ? (float)(sqrt((double)world2cam[9] * world2cam[9] + (double)world2cam[10] * world2cam[10] +
+                                                (double)world2cam[11] * world2cam[11]) * 1.0001 + 1e-6) : -1.f;
+        }
+        const double r = pipelined ? df_tile_radius(vol2world, 8, 8, DF_ROW_TZ, v)                   // (the tile of the chosen kernel)
+                         : use_tab ? df_tile_radius(vol2world, DF_ROW_TX, lds_rows ? DF_LDS_TY : DF_ROW_TY, DF_ROW_TZ, v)
+                                   : df_tile_radius(vol2world, DF_BRICK, DF_BRICK, DF_BRICK, v);
+        double fro = 0.0;    // Frobenius norm of world2cam.R bounds its operator norm; == sqrt(3) for a rotation
+        for (int i = 0; i < 9; ++i) fro += (double)world2cam[i] * world2cam[i];
+        fro = sqrt(fro);
+        a.cam_scale = (float)((fabs(fro - 1.7320508075688772) < 1e-3) ? 1.001 : fro * 1.001);
+        a.tile_r = (float)(r * 1.001 + 1e-6);
+        a.cull = wf->bounds_dev;
+        if (d.weights && !(flags & DF_WARP_NO_ZERO_SKIP)) a.tile_wmax = wf->tile_wmax;
+    }
+    P.W = df_view(wf); P.kern = nullptr; P.tiles_x = tiles_x; P.v = v; P.s = s;
+    if (!lds_rows && !pipelined) return DF_OK;
+
+    // The kernel, from the variant: k = 8 runs DF_PIPE_WGT = 256 threads (4 waves, 4 KiB of union copies each), one plane per batch (<= 80 VGPRs:
+    // six workgroups per CU, 6 waves / SIMD); k = 4 keeps two planes per batch (+4 % that way at 256^3).
+    const bool vi = a.v2w_identity != 0;
+    if (lds_rows && d.weights) { DF_DISPATCH_K(k, P.kern = (df_warp_rows_lds_kernel<K, true, 2>)); }
+    else if (lds_rows) { DF_DISPATCH_K(k, P.kern = (df_warp_rows_lds_kernel<K, false, 1>)); }
+    else if (k == 8) P.kern = vi ? df_warp_rows_pipe_kernel<8, 1, DF_PIPE_WGT, true, false> : df_warp_rows_pipe_kernel<8, 1, DF_PIPE_WGT, false, false>;
+    else if (d.wide) P.kern = vi ? df_warp_rows_pipe_kernel<4, 2, 1024, true, true> : df_warp_rows_pipe_kernel<4, 2, 1024, false, true>;
+    else if (d.k4_table) P.kern = vi ? df_warp_rows_pipe_kernel<4, 2, 512, true, true> : df_warp_rows_pipe_kernel<4, 2, 512, false, true>;
+    else P.kern = vi ? df_warp_rows_pipe_kernel<4, 2, 512, true, false> : df_warp_rows_pipe_kernel<4, 2, 512, false, false>;
+    a.bz0 = zt_lo; a.zt = d.zt; P.threads = d.threads; P.lds = d.lds;
+    P.grid = dim3((unsigned)(tiles_x * tiles_y), (unsigned)((layers + d.zt - 1) / d.zt));
+    // (the CU's whole LDS, whatever THIS launch asks for: the attribute belongs to the kernel, not to the launch, and two host threads
+    // sweeping warp fields of different sizes would otherwise lower it under each other's launches)
+    DF_HIP(hipFuncSetAttribute((const void*)P.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
+    if (lds_rows) DF_TRY(df_tables_complete(wf, st));
+    else DF_TRY(df_pipe_plan(wf, P, tiles_y, k, flags, st));
+    P.seq = wf->seq;
+    return DF_OK;
+}
+
+// The one launch of a planned batched or pipelined sweep into `vol`.  A pipelined sweep on a handle that is also driven through the split
+// API is recorded: the next frame's set_transforms / prepare on another stream wait for the sweeps that still read what they rewrite.
+static int df_launch_prepared(DfWarpField* wf, DfPrepared& P, void* vol, unsigned long long* n_updated, hipStream_t st)
+{
+    P.a.vol = (uint32_t*)vol; P.a.n_upd = n_updated;
+#ifdef DF_TRACE_WG
+    static unsigned long long* trace_dev = nullptr; static size_t trace_cap = 0;
+    const size_t trace_n = (size_t)P.grid.x * (P.threads / 64u) * 4;
+    if (P.a.plan_mask && trace_n > trace_cap) { (void)hipFree(trace_dev); DF_HIP(hipMalloc((void**)&trace_dev, trace_n * 8)); trace_cap = trace_n; }
+    if (P.a.plan_mask) { DF_HIP(hipMemsetAsync(trace_dev, 0, trace_n * 8, st)); P.a.trace = trace_dev; }
+#endif
+    P.kern<<<P.grid, dim3(P.threads), P.lds, st>>>(P.a, P.W, P.tiles_x);
+    DF_LAUNCH_CHECK();
+#ifdef DF_TRACE_WG
+    if (P.a.plan_mask && getenv("DF_TRACE_FILE")) {
+        DF_HIP(hipStreamSynchronize(st));
+        unsigned long long* h = (unsigned long long*)malloc(trace_n * 8);
+        DF_HIP(hipMemcpy(h, trace_dev, trace_n * 8, hipMemcpyDeviceToHost));
+        FILE* f = fopen(getenv("DF_TRACE_FILE"), "wb");
+        if (f) { unsigned long long hdr[4] = {P.grid.x, 1, (unsigned long long)(P.threads / 64u), 0}; fwrite(hdr, 8, 4, f); fwrite(h, 8, trace_n, f); fclose(f); }
+        free(h);
+    }
+#endif
+    if (P.a.plan_mask && wf->split_events) {
+        DF_HIP(hipEventRecord(wf->ev_sweep_done[P.seq & 1], st));
+        wf->recorded_seq = P.seq; wf->ring_seq[P.seq & 1] = P.seq;
+    }
+    return DF_OK;
+}
 
 extern "C" int dfusion_integrate_warped(const uint16_t* dists, size_t pitch, int cols, int rows, DfVolume v, const DfSlab* slab,
                                         const float vol2world[12], const float world2cam[12], const float proj[4],
                                         DfWarpField* wf, int k, unsigned flags, unsigned long long* n_updated, dfStream stream)
 {
-    return df_integrate_warped_impl(dists, pitch, cols, rows, v, slab, vol2world, world2cam, proj, wf, k, flags, n_updated, stream, DF_MODE_WHOLE);
+    DfSlab s;
+    DF_TRY(df_warped_check(dists, pitch, cols, rows, v, slab, vol2world, world2cam, proj, wf, k, &s));
+    if (s.z_own_n == 0) return DF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    DF_TRY(df_wait_split_sweep(wf, st));                      // (sweeps issued through the split API on another stream: all of them)
+    DfPrepared P;
+    DF_TRY(df_integrate_warped_impl(dists, pitch, cols, rows, v, s, vol2world, world2cam, proj, wf, k, flags, st, false, P));
+    if (P.kern) return df_launch_prepared(wf, P, v.data, n_updated, st);
+    DfWarpedArgs& a = P.a;                                    // the two variants without a launch plan: table rows, bricks
+    const int zt_lo = s.z_own0 / DF_ROW_TZ, zt_hi = (s.z_own0 + s.z_own_n - 1) / DF_ROW_TZ;      // (DF_ROW_TZ == DF_BRICK)
+    a.vol = (uint32_t*)v.data; a.n_upd = n_updated; a.bz0 = zt_lo;
+    if (a.knn_tab) {
+        DF_TRY(df_tables_complete(wf, st));
+        dim3 grid((unsigned)(P.tiles_x * ((a.Y + DF_ROW_TY - 1) / DF_ROW_TY)), (unsigned)(zt_hi - zt_lo + 1));
+        if (a.w_tab) { DF_DISPATCH_K(k, df_warp_rows_kernel<K, true, 4><<<grid, dim3(256), 0, st>>>(a, P.W, P.tiles_x)); }
+        else { DF_DISPATCH_K(k, df_warp_rows_kernel<K, false, 4><<<grid, dim3(256), 0, st>>>(a, P.W, P.tiles_x)); }
+    } else {
+        dim3 grid((unsigned)(P.W.bx * P.W.by), (unsigned)(zt_hi - zt_lo + 1));
+        DF_DISPATCH_K(k, df_warp_brick_kernel<K, false><<<grid, dim3(256), 0, st>>>(a, P.W));
+    }
+    DF_LAUNCH_CHECK();
+    return DF_OK;
 }
 
-// ---- the frame's warped integrate in two calls (include/dfusion.h): everything that does not touch the volume -- dists pyramid, verdict pass,
-// table builds, launch plan -- and the sweep.  The halves may be issued on different streams; the handle's events order them.
+// ---- the frame's warped integrate in two calls (include/dfusion.h), which may be issued on different streams: the handle's events order
+// them.  (A prepare waits only for the sweeps that still read what it rewrites: the plan sets of df_pipe_plan, the node arrays of df_warp_pack.)
 extern "C" int dfusion_integrate_warped_prepare(const uint16_t* dists, size_t pitch, int cols, int rows, DfVolume geometry, const DfSlab* slab,
                                                 const float vol2world[12], const float world2cam[12], const float proj[4],
                                                 DfWarpField* wf, int k, unsigned flags, dfStream stream)
@@ -353,8 +517,13 @@ extern "C" int dfusion_integrate_warped_prepare(const uint16_t* dists, size_t pi
     }
     wf->prep_valid = false;
     if (!geometry.data) geometry.data = (void*)(size_t)16;          // (never dereferenced by the prepare half; df_volume_valid wants a pointer)
-    const int rc = df_integrate_warped_impl(dists, pitch, cols, rows, geometry, slab, vol2world, world2cam, proj, wf, k, flags, nullptr, stream, DF_MODE_PREPARE);
-    if (rc != DF_OK) return rc;
+    DfSlab s;
+    DF_TRY(df_warped_check(dists, pitch, cols, rows, geometry, slab, vol2world, world2cam, proj, wf, k, &s));
+    if (s.z_own_n != 0) {
+        if (!wf->prep) wf->prep.reset(new DfPrepared());
+        DF_TRY(df_integrate_warped_impl(dists, pitch, cols, rows, geometry, s, vol2world, world2cam, proj, wf, k, flags, (hipStream_t)stream, true, *wf->prep));
+        wf->prep_valid = true;
+    }
     DF_HIP(hipEventRecord(wf->ev_prep_done, (hipStream_t)stream));
     return DF_OK;
 }
@@ -372,255 +541,7 @@ extern "C" int dfusion_integrate_warped_sweep(DfVolume v, const DfSlab* slab, Df
     hipStream_t st = (hipStream_t)stream;
     wf->prep_valid = false;
     DF_HIP(hipStreamWaitEvent(st, wf->ev_prep_done, 0));
-    P->a.vol = (uint32_t*)v.data; P->a.n_upd = n_updated;
-    P->kern<<<P->grid, dim3(P->threads), P->lds, st>>>(P->a, P->W, P->tiles_x);
-    DF_LAUNCH_CHECK();
-    DF_HIP(hipEventRecord(wf->ev_sweep_done[P->seq & 1], st));
-    wf->recorded_seq = P->seq; wf->ring_seq[P->seq & 1] = P->seq;
-    return DF_OK;
-}
-
-static int df_integrate_warped_impl(const uint16_t* dists, size_t pitch, int cols, int rows, DfVolume v, const DfSlab* slab,
-                                    const float vol2world[12], const float world2cam[12], const float proj[4],
-                                    DfWarpField* wf, int k, unsigned flags, unsigned long long* n_updated, dfStream stream, int mode)
-{
-    if (!dists || !vol2world || !world2cam || !proj || !wf || cols <= 0 || rows <= 0 || !df_pitch_ok(pitch, cols, 2) || !df_volume_valid(v)) return DF_E_INVALID;
-    if (k < 1 || k > 8 || wf->M < k) return DF_E_INVALID;
-    DfSlab s = df_slab_or_full(v, slab);
-    if (!df_slab_valid(v, s)) return DF_E_INVALID;
-    if (!wf->index_valid || wf->k_built < k || memcmp(wf->geom_dims, v.dims, sizeof(wf->geom_dims)) ||
-        memcmp(wf->geom_vs, v.voxel_size, sizeof(wf->geom_vs)) || memcmp(wf->geom_aff, vol2world, sizeof(wf->geom_aff)))
-        return DF_E_NO_INDEX;
-    if (s.z_own_n == 0) return DF_OK;
-    hipStream_t st = (hipStream_t)stream;
-    // (sweeps issued through the split API on another stream: the single call waits for all of them; a prepare only for the sweeps that
-    // still read what it rewrites -- see the plan sets below and df_warp_pack)
-    if (mode == DF_MODE_WHOLE) { int rc = df_wait_split_sweep(wf, st); if (rc) return rc; }
-    { int rc = df_side_join(wf, st); if (rc) return rc; }     // the previous call's look-ahead builds (tables, models, state bytes)
-    wf->prep_valid = false;                                   // (a prepared plan that was never swept is void once the handle's scratch is rewritten)
-
-    DfWarpedArgs a;
-    memset(&a, 0, sizeof(a));
-    a.vol = (uint32_t*)v.data; a.X = v.dims[0]; a.Y = v.dims[1]; a.Z = v.dims[2];
-    a.z_store0 = s.z_store0; a.z_own0 = s.z_own0; a.z_own_n = s.z_own_n;
-    a.vsx = v.voxel_size[0]; a.vsy = v.voxel_size[1]; a.vsz = v.voxel_size[2];
-    a.vol2world = df_aff(vol2world); a.world2cam = df_aff(world2cam);
-    {
-        static const float I9[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
-        a.v2w_identity = memcmp(vol2world, I9, sizeof(I9)) == 0;     // bitwise: -0 entries do not qualify
-    }
-    a.P.dists = dists; a.P.pitch = pitch; a.P.cols = cols; a.P.rows = rows;
-    a.P.fx = proj[0]; a.P.fy = proj[1]; a.P.cx = proj[2]; a.P.cy = proj[3];
-    a.P.trunc = v.trunc_dist; a.P.trunc_inv = 1.f / v.trunc_dist; a.P.max_weight = v.max_weight;
-    a.sat_ok = df_sat_trunc_ok(v.trunc_dist) ? 1 : 0;
-    a.n_upd = n_updated;
-    a.n_swept = wf->dbg_swept;
-    a.kf = (float)k; a.cam_scale = 1.f; a.origin_cam = -1.f;
-    const bool use_tab = wf->tab_valid && wf->tab_k == k && !(flags & DF_WARP_NO_TABLE) && s.z_own0 >= wf->tab_z0 &&
-                         s.z_own0 + s.z_own_n <= wf->tab_z0 + wf->tab_zn;
-    const bool use_w = use_tab && wf->w_tab_valid && !(flags & DF_WARP_NO_WEIGHT_TABLE);
-    if (use_tab) {
-        a.knn_tab = wf->knn_tab; a.tab_z0 = wf->tab_z0;
-        a.tab_ntx = (a.X + DF_TAB_TX - 1) / DF_TAB_TX; a.tab_nty = (a.Y + DF_TAB_TY - 1) / DF_TAB_TY;
-        a.tab_nvox = (size_t)a.tab_ntx * DF_TAB_TX * a.tab_nty * DF_TAB_TY * wf->tab_zn;
-    }
-    if (use_w) a.w_tab = wf->w_tab;
-    // the pipelined sweep's preconditions, decided ONCE: which pyramid is built below and which kernel is launched further down both
-    // follow from them (they used to be two hand-copied predicates).  The pipelined kernel forms row * pitch with a 24-bit
-    // multiply and a 32-bit dists offset.  It needs no LDS node table (round 6): k = 8 blends out of per-wave union copies or gathers from
-    // the L2, for ANY node count; k = 4 keeps the table (32 B per node) where it fits the CU's LDS.  DF_WARP_NO_LDS asks for the plain
-    // gather kernel (df_warp_rows_kernel: no plan, no verdicts).
-    const size_t lds_limit = df_lds_limit();
-    const bool no_lds = (flags & DF_WARP_NO_LDS) != 0;
-    const bool lds_fits = (size_t)wf->M * 32 <= lds_limit;
-    const bool pipe_form_ok = use_w && !(flags & DF_WARP_NO_PIPELINE) && pitch < (1u << 24) && rows < (1 << 24) &&
-                              (unsigned long long)rows * pitch < (1ull << 32) && (unsigned long long)v.dims[0] * v.dims[1] < (1ull << 30);
-    const bool pipe_sweep = use_tab && !no_lds && pipe_form_ok && (k == 8 || k == 4);
-
-    if (!(flags & DF_WARP_NO_CULL) && proj[0] > 0.f && proj[1] > 0.f) {
-        if (!(flags & DF_WARP_NO_DEPTH_PYRAMID)) {
-            const size_t elems = df_pyramid_elems(cols, rows);
-            { int rc = wf->pyr_mem.reserve(elems); if (rc) return rc; }
-            // the pipelined sweep (the product path) reads the pyramid in its verdict pass only, and its plan kernel re-arms the
-            // image-maximum word: levels 1..5 in ONE launch.  The other kernels take the full pyramid (two launches).
-            const bool pipe_path = pipe_sweep;
-            // The image-maximum word: TWO of them ([6], [7]), used alternately; every plan kernel zeroes both once its readers are done.
-            // A call that returns early between its pyramid build and its plan kernel leaves ITS word dirty -- the next call uses the other
-            // one (zeroed by the plan kernel before), and that call's plan kernel cleans both (ADVICE r4; no memset node per frame).
-            wf->max_phase ^= 1;
-            unsigned int* max_word = (unsigned int*)(wf->bounds_dev + 6 + wf->max_phase);
-            int rc = df_build_dists_pyramid(dists, pitch, cols, rows, wf->pyr_mem, wf->pyr_mem.cap, &a.py, st, pipe_path, nullptr,
-                                            pipe_path ? max_word : nullptr);
-            if (rc) return rc;
-        }
-        if (a.py.top == 0) {                                      // no pyramid (switched off, or an image under 32 px): the image-wide maximum alone
-            DF_HIP(hipMemsetAsync(wf->bounds_dev + 2, 0, sizeof(float), st));
-            hipLaunchKernelGGL(df_dists_max_kernel, dim3(64), dim3(256), 0, st, dists, pitch, cols, rows, wf->bounds_dev + 2);
-            DF_LAUNCH_CHECK();
-        }
-        {   // world2cam rigid (R^T R = I to 1e-5)?  Then the distance bound of df_tile_culled holds with |world2cam.t|.
-            bool rigid = true;
-            for (int i = 0; i < 3 && rigid; ++i)
-                for (int j = 0; j < 3; ++j) {
-                    double d = 0.0;
-                    for (int r = 0; r < 3; ++r) d += (double)world2cam[3 * r + i] * world2cam[3 * r + j];
-                    if (!(fabs(d - (i == j ? 1.0 : 0.0)) < 1e-5)) { rigid = false; break; }
-                }
-            a.origin_cam = rigid ? (float)(sqrt((double)world2cam[9] * world2cam[9] + (double)world2cam[10] * world2cam[10] +
-                                                (double)world2cam[11] * world2cam[11]) * 1.0001 + 1e-6) : -1.f;
-        }
-        const double r = use_tab ? df_tile_radius(vol2world, DF_ROW_TX, DF_ROW_TY, DF_ROW_TZ, v)
-                                 : df_tile_radius(vol2world, DF_BRICK, DF_BRICK, DF_BRICK, v);
-        double fro = 0.0;    // Frobenius norm of world2cam.R bounds its operator norm; == sqrt(3) for a rotation
-        for (int i = 0; i < 9; ++i) fro += (double)world2cam[i] * world2cam[i];
-        fro = sqrt(fro);
-        a.cam_scale = (float)((fabs(fro - 1.7320508075688772) < 1e-3) ? 1.001 : fro * 1.001);
-        a.tile_r = (float)(r * 1.001 + 1e-6);
-        a.cull = wf->bounds_dev;
-        if (use_w && !(flags & DF_WARP_NO_ZERO_SKIP)) a.tile_wmax = wf->tile_wmax;
-    }
-
-    DfWarpView W = df_view(wf);
-    if (use_tab && !no_lds && (pipe_sweep || lds_fits)) {
-        const int tiles_x = (a.X + DF_ROW_TX - 1) / DF_ROW_TX, tiles_y = (a.Y + DF_LDS_TY - 1) / DF_LDS_TY;
-        const int zt_lo = s.z_own0 / DF_ROW_TZ, zt_hi = (s.z_own0 + s.z_own_n - 1) / DF_ROW_TZ;
-        a.bz0 = zt_lo;
-        const bool pipe_ok = pipe_sweep;
-        if (a.cull) a.tile_r = (float)(df_tile_radius(vol2world, pipe_ok ? 8 : DF_ROW_TX, pipe_ok ? 8 : DF_LDS_TY, DF_ROW_TZ, v) * 1.001 + 1e-6);
-        // LDS of a launch: the node table (32 B a node) for the kernels that keep one -- k = 4's pipelined sweep where it fits, the batched
-        // kernel of the other k --, 4 KiB of union copies per wave for k = 8's, nothing for k = 4 without a table
-        const bool k4_table = pipe_ok && k == 4 && lds_fits;
-        const size_t lds = !pipe_ok || k4_table ? (size_t)wf->M * 32 : k == 8 ? (size_t)(DF_PIPE_WGT / 64) * 4096 : 0;
-        typedef void (*lds_kernel_t)(const DfWarpedArgs, const DfWarpView, int);
-        lds_kernel_t kern = nullptr;
-        // tile layers per workgroup: long walks amortise the LDS fill and the pipeline ramp, short ones even out the last round of
-        // workgroups on the 256 CUs (measured: 4 layers best at 256^3 = 1024 workgroups, 8 at 512^3, 16 at 1024^3 = 16384)
-        const long long cols_layers = (long long)tiles_x * tiles_y * (zt_hi - zt_lo + 1);
-        const bool pipe = pipe_sweep;                           // df_warp_rows_lds_kernel always walks DF_LDS_ZT layers per workgroup
-        a.zt = !pipe ? DF_LDS_ZT : cols_layers <= 8192 ? 4 : cols_layers <= 65536 ? 8 : 16;
-        dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)((zt_hi - zt_lo + 1 + a.zt - 1) / a.zt));
-        const bool wide = k4_table && lds > 80 * 1024;          // one workgroup per CU either way: make it 1024 threads
-        const bool vi = a.v2w_identity != 0;
-        // workgroup geometry: k = 8 runs DF_PIPE_WGT = 256 threads (4 waves, 4 KiB of union copies each), one plane per batch (<= 80 VGPRs: six
-        // workgroups per CU, 6 waves / SIMD; round 5, at 768 threads: -2 to -4 % against 512 threads, two planes, 4 waves); k = 4 keeps two planes per batch (+4 % that way at 256^3)
-        unsigned wg_threads = 512u;
-        if (pipe_ok && k == 8) {
-            kern = vi ? df_warp_rows_pipe_kernel<8, 1, DF_PIPE_WGT, true, false> : df_warp_rows_pipe_kernel<8, 1, DF_PIPE_WGT, false, false>;
-            wg_threads = (unsigned)DF_PIPE_WGT;
-        } else if (pipe_ok && k4_table) {
-            kern = wide ? (vi ? df_warp_rows_pipe_kernel<4, 2, 1024, true, true> : df_warp_rows_pipe_kernel<4, 2, 1024, false, true>)
-                        : (vi ? df_warp_rows_pipe_kernel<4, 2, 512, true, true> : df_warp_rows_pipe_kernel<4, 2, 512, false, true>);
-            wg_threads = wide ? 1024u : 512u;
-        } else if (pipe_ok) {
-            kern = vi ? df_warp_rows_pipe_kernel<4, 2, 512, true, false> : df_warp_rows_pipe_kernel<4, 2, 512, false, false>;
-        }
-        else if (use_w) { DF_DISPATCH_K(k, kern = (df_warp_rows_lds_kernel<K, true, 2>)); }
-        else { DF_DISPATCH_K(k, kern = (df_warp_rows_lds_kernel<K, false, 1>)); }
-        // (the CU's whole LDS, whatever THIS launch asks for: the attribute belongs to the kernel, not to the launch, and two host threads
-        // sweeping warp fields of different sizes would otherwise lower it under each other's launches)
-        if (lds > lds_limit) return DF_E_INVALID;
-        DF_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
-        if (!pipe) { int rc = df_tables_complete(wf, st); if (rc) return rc; }
-        if (pipe) {
-            // the launch plan: verdict masks of all strip items (one wave each), the alive ones sorted by work; then one workgroup per
-            // 2 (4) plan entries.  The grid is sized for every strip -- nothing is read back -- and the workgroups past the plan's end
-            // return at once.
-            const unsigned n_zb = grid.y, n_items = (unsigned)tiles_x * (unsigned)tiles_y * 2u * n_zb;
-            // The plan lives in TWO sets of (masks, bins), used alternately, and its bin counters in FOUR, each plan kernel zeroing the set of
-            // the plan after next: a sweep issued through the split API may still be reading its plan while the next frame's is made.
-            if (n_items > wf->plan_cap) {
-                { int rc = df_wait_all_sweeps_host(wf); if (rc) return rc; }
-                wf->plan_cap = 0;
-                for (int i = 0; i < 2; ++i) {
-                    { int rc = wf->plan_mask2[i].reserve((size_t)n_items * 2); if (rc) return rc; }
-                    { int rc = wf->plan_list2[i].reserve((size_t)n_items * DF_PLAN_BINS); if (rc) return rc; }      // the bins
-                    { int rc = wf->plan_code2[i].reserve(n_items); if (rc) return rc; }
-                }
-                wf->plan_cap = n_items; wf->plan_reader[0] = wf->plan_reader[1] = 0;
-            }
-            if (!wf->plan_hist) {
-                { int rc = wf->plan_hist.reserve(4 * 128); if (rc) return rc; }
-                DF_HIP(hipMemsetAsync(wf->plan_hist, 0, 4 * 128 * sizeof(unsigned int), st));
-                wf->hphase = 0;
-            }
-            wf->pphase ^= 1;
-            { int rc = df_wait_reader(wf, wf->plan_reader[wf->pphase], st); if (rc) return rc; }     // (the sweep two plans ago)
-            if (a.cull) { int rc = df_block_verdicts(wf, a, k, flags, st); if (rc) return rc; }
-            else { int rc = df_tables_complete(wf, st); if (rc) return rc; }
-            ++wf->tab_sweeps;
-            unsigned int* cnt = wf->plan_hist + 128 * (wf->hphase & 3u);
-            unsigned int* cnt_next = wf->plan_hist + 128 * ((wf->hphase + 2u) & 3u);       // (last read by the sweep two plans ago: waited for above)
-            unsigned long long* pmask = wf->plan_mask2[wf->pphase]; unsigned int* plist = wf->plan_list2[wf->pphase];
-            // 4-bit neighbour codes (k = 8): for the cells whose block the model pass has been over, unless the models are switched off
-            unsigned long long* pcode = nullptr;
-            if (k == 8 && a.cull && a.blk_alive && wf->code_tab && wf->bm_ids && wf->bm_coded && wf->bm_cap >= (size_t)a.bm_nbx * a.bm_nby * (wf->tab_zn / 8) &&
-                !(flags & (DF_WARP_NO_BLOCK_MODEL | DF_WARP_NO_CODES))) {
-                pcode = wf->plan_code2[wf->pphase];
-                a.code_tab = wf->code_tab; a.bm_ids = wf->bm_ids; a.bm_coded = wf->bm_coded;
-            }
-            hipLaunchKernelGGL(df_sweep_plan_kernel, dim3((n_items + DF_PLAN_WG / 64 - 1) / (DF_PLAN_WG / 64)), dim3(DF_PLAN_WG), 0, st, a, tiles_x, tiles_y, n_items, pmask, cnt,
-                               plist, cnt_next, pcode);
-            DF_LAUNCH_CHECK();
-            a.plan_code = pcode;
-            ++wf->hphase;                                                  // (only once the kernel that zeroes the set after next is in the stream)
-            a.plan_mask = pmask; a.plan_bins = plist; a.plan_cnt = cnt; a.plan_items = n_items; a.plan_tiles_y = tiles_y;
-            // this plan's sweep: its number, and what it will read
-            wf->plan_reader[wf->pphase] = wf->node_reader[wf->nphase] = ++wf->seq;
-            const unsigned spw = wg_threads >= 256u ? wg_threads / 256u : 1u;
-            const unsigned groups = (n_items + spw - 1) / spw;
-            grid = dim3(groups, 1);
-#ifdef DF_TRACE_WG
-            static unsigned long long* trace_dev = nullptr; static size_t trace_cap = 0;
-            const size_t trace_n = (size_t)groups * (wg_threads / 64u) * 4;
-            if (trace_n > trace_cap) { (void)hipFree(trace_dev); DF_HIP(hipMalloc((void**)&trace_dev, trace_n * 8)); trace_cap = trace_n; }
-            DF_HIP(hipMemsetAsync(trace_dev, 0, trace_n * 8, st));
-            a.trace = trace_dev;
-            kern<<<grid, dim3(wg_threads), lds, st>>>(a, W, tiles_x);
-            if (getenv("DF_TRACE_FILE")) {
-                DF_HIP(hipStreamSynchronize(st));
-                unsigned long long* h = (unsigned long long*)malloc(trace_n * 8);
-                DF_HIP(hipMemcpy(h, trace_dev, trace_n * 8, hipMemcpyDeviceToHost));
-                FILE* f = fopen(getenv("DF_TRACE_FILE"), "wb");
-                if (f) { unsigned long long hdr[4] = {groups, 1, (unsigned long long)(wg_threads / 64u), 0}; fwrite(hdr, 8, 4, f); fwrite(h, 8, trace_n, f); fclose(f); }
-                free(h);
-            }
-            DF_LAUNCH_CHECK();
-            return DF_OK;
-#endif
-        }
-        if (mode == DF_MODE_PREPARE) {
-            if (!pipe) return DF_E_INVALID;                                // (the split exists for the cached, pipelined sweep only)
-            if (!wf->prep) wf->prep.reset(new DfPrepared());
-            DfPrepared* P = wf->prep.get();
-            P->a = a; P->W = W; P->kern = kern; P->grid = grid; P->threads = wg_threads; P->lds = lds; P->tiles_x = tiles_x; P->v = v; P->s = s;
-            P->seq = wf->seq;
-            wf->prep_valid = true;
-            return DF_OK;
-        }
-        kern<<<grid, dim3(wg_threads), lds, st>>>(a, W, tiles_x);
-        if (pipe && wf->split_events) {                                   // (a handle that is also driven through the split API: this sweep counts)
-            DF_LAUNCH_CHECK();
-            DF_HIP(hipEventRecord(wf->ev_sweep_done[wf->seq & 1], st));
-            wf->recorded_seq = wf->seq; wf->ring_seq[wf->seq & 1] = wf->seq;
-        }
-    } else if (use_tab) {
-        if (mode == DF_MODE_PREPARE) return DF_E_INVALID;
-        { int rc = df_tables_complete(wf, st); if (rc) return rc; }
-        const int tiles_x = (a.X + DF_ROW_TX - 1) / DF_ROW_TX, tiles_y = (a.Y + DF_ROW_TY - 1) / DF_ROW_TY;
-        const int zt_lo = s.z_own0 / DF_ROW_TZ, zt_hi = (s.z_own0 + s.z_own_n - 1) / DF_ROW_TZ;
-        a.bz0 = zt_lo;
-        dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)(zt_hi - zt_lo + 1));
-        if (use_w) { DF_DISPATCH_K(k, df_warp_rows_kernel<K, true, 4><<<grid, dim3(256), 0, st>>>(a, W, tiles_x)); }
-        else { DF_DISPATCH_K(k, df_warp_rows_kernel<K, false, 4><<<grid, dim3(256), 0, st>>>(a, W, tiles_x)); }
-    } else {
-        if (mode == DF_MODE_PREPARE) return DF_E_INVALID;
-        const int bz_lo = s.z_own0 / DF_BRICK, bz_hi = (s.z_own0 + s.z_own_n - 1) / DF_BRICK;
-        a.bz0 = bz_lo;
-        dim3 grid((unsigned)(W.bx * W.by), (unsigned)(bz_hi - bz_lo + 1));
-        DF_DISPATCH_K(k, df_warp_brick_kernel<K, false><<<grid, dim3(256), 0, st>>>(a, W));
-    }
-    DF_LAUNCH_CHECK();
-    return DF_OK;
+    return df_launch_prepared(wf, *P, v.data, n_updated, st);
 }
 
 // Per-voxel k-NN (and weight) tables for planes [z_own0, z_own0 + z_own_n) (this rank's slab): allocated here; built here (every brick)
@@ -645,23 +566,14 @@ int df_build_voxel_table(DfWarpField* wf, const DfVolume& v, const DfSlab& s, co
         DF_HIP(hipMemsetAsync(wf->tile_wmax, 0, ntile * sizeof(float), st));
     }
     const size_t nblk = (size_t)ntx * (DF_TAB_TX / 8) * nty * (DF_TAB_TY / 8) * (tzn / 8);
-    if (nblk > wf->blk_cap) {
-        wf->blk_cap = 0;
-        { int rc = wf->blk_state.reserve(nblk); if (rc) return rc; }
-        { int rc = wf->blk_tie.reserve(nblk); if (rc) return rc; }
-        { int rc = wf->blk_wmax.reserve(nblk); if (rc) return rc; }
-        { int rc = wf->blk_alive.reserve(nblk); if (rc) return rc; }
-        { int rc = wf->blk_alive_prev.reserve(nblk); if (rc) return rc; }
-        { int rc = wf->blk_work.reserve(3 * nblk); if (rc) return rc; }
-        wf->blk_cap = nblk;
-    }
-    { int rc = wf->blk_cnt.reserve(16); if (rc) return rc; }
+    DF_TRY(wf->blk.reserve(nblk));
+    DF_TRY(wf->blk_cnt.reserve(16));
     DF_HIP(hipMemsetAsync(wf->blk_cnt, 0, 16 * sizeof(uint32_t), st));
-    DF_HIP(hipMemsetAsync(wf->blk_state, on_demand ? 0 : 1, nblk, st));
-    DF_HIP(hipMemsetAsync(wf->blk_tie, 0, nblk, st));
-    DF_HIP(hipMemsetAsync(wf->blk_wmax, 0, nblk * sizeof(float), st));
-    DF_HIP(hipMemsetAsync(wf->blk_alive, 1, nblk, st));                   // (no verdicts yet: "every neighbour kept" for the first pass's sub-verdict list)
-    DF_HIP(hipMemsetAsync(wf->blk_alive_prev, 1, nblk, st));
+    DF_HIP(hipMemsetAsync(wf->blk.state, on_demand ? 0 : 1, nblk, st));
+    DF_HIP(hipMemsetAsync(wf->blk.tie, 0, nblk, st));
+    DF_HIP(hipMemsetAsync(wf->blk.wmax, 0, nblk * sizeof(float), st));
+    DF_HIP(hipMemsetAsync(wf->blk.alive, 1, nblk, st));                   // (no verdicts yet: "every neighbour kept" for the first pass's sub-verdict list)
+    DF_HIP(hipMemsetAsync(wf->blk.alive_prev, 1, nblk, st));
     wf->blk_phase = 0;
     wf->tab_z0 = tz0; wf->tab_zn = tzn; wf->tab_k = k; wf->tab_valid = true; wf->w_tab_valid = weights;
     wf->tab_complete = !on_demand; wf->tab_sweeps = 0; wf->alive_valid = false;

@@ -375,7 +375,7 @@ int df_warp_grow(DfWarpField* wf, const float* pos, const float* dq, const float
     { int rc = df_warp_build_tie_tree(wf, st); if (rc) return rc; }
     if (!wf->index_valid) return DF_OK;
     const size_t nb = (size_t)wf->bx * wf->by * wf->bz;
-    const bool tabs = wf->tab_valid && wf->blk_state && wf->blk_tie;
+    const bool tabs = wf->tab_valid && wf->blk.state && wf->blk.tie;
     uint32_t* old_off = nullptr; uint16_t* old_list = nullptr;
     if (tabs) {                                                // the lists before the update, to find the bricks whose list changes
         const size_t off_bytes = ((nb + 1) * sizeof(uint32_t) + 255) & ~(size_t)255, need = off_bytes + wf->brick_list.cap * sizeof(uint16_t);
@@ -395,7 +395,7 @@ int df_warp_grow(DfWarpField* wf, const float* pos, const float* dq, const float
     const int nbz = wf->tab_zn / 8;
     const size_t nblk = (size_t)a.bm_nbx * a.bm_nby * nbz;
     hipLaunchKernelGGL(df_grow_dirty_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, old_off, old_list, wf->brick_off, wf->brick_list,
-                       wf->bx, wf->by, wf->bz, a.bm_nbx, a.bm_nby, nbz, wf->tab_z0 / DF_BRICK, wf->blk_state, a.blk_wmax, wf->blk_tie);
+                       wf->bx, wf->by, wf->bz, a.bm_nbx, a.bm_nby, nbz, wf->tab_z0 / DF_BRICK, wf->blk.state, a.blk_wmax, wf->blk.tie);
     DF_LAUNCH_CHECK();
     wf->alive_valid = false; wf->tab_complete = false;
     if (!((wf->index_flags & DF_INDEX_TABLES_ON_DEMAND) && wf->w_tab_valid)) {   // eager tables: the stale blocks are re-made here

@@ -86,7 +86,7 @@ int df_side_init(DfWarpField* wf)
     }
     if (!wf->host_report) {
         wf->host_report = (volatile uint32_t*)h;
-        wf->host_report[0] = wf->host_report[1] = wf->host_report[2] = 1u;       // nothing reported yet: assume work
+        wf->host_report[0] = wf->host_report[1] = wf->host_report[2] = DF_REPORT_NONE;
         wf->host_report[3] = 0u;
     }
     wf->ev_fork = ev_fork; wf->ev_join = ev_join; wf->side = side;

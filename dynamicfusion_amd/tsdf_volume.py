@@ -238,6 +238,13 @@ class TsdfVolume:
         if sync:                   # device::integrate ends with cudaDeviceSynchronize (tsdf_volume.cu:160)
             torch.cuda.current_stream().synchronize()
 
+    @staticmethod
+    def _verdict_flags(prefetch, block_model, codes, sub_verdict):
+        """The flag bits integrate_warped and integrate_warped_prepare share: what the pipelined sweep's verdict pass makes, and where."""
+        return ((capi.DF_WARP_STEADY_PREFETCH if prefetch == "steady" else 0 if prefetch else capi.DF_WARP_NO_PREFETCH) |
+                (0 if codes else capi.DF_WARP_NO_CODES) | (0 if sub_verdict else capi.DF_WARP_NO_SUB_VERDICT) |
+                (capi.DF_WARP_BLOCK_MODEL_NOW if block_model == "now" else 0 if block_model else capi.DF_WARP_NO_BLOCK_MODEL))
+
     # ---- the north-star composition (SURVEY.md 9.5); no reference method of this name exists
     def integrate_warped(self, dists, camera_pose, intr, warp_field, k=None, n_updated=None, cull=True, sync=True,
                          use_table=True, use_weights=True, use_lds=True, pipelined=True, zero_skip=True, depth_pyramid=True, block_model=True,
@@ -258,9 +265,7 @@ class TsdfVolume:
             (0 if cull else capi.DF_WARP_NO_CULL) | (0 if use_table else capi.DF_WARP_NO_TABLE) |
             (0 if use_weights else capi.DF_WARP_NO_WEIGHT_TABLE) | (0 if use_lds else capi.DF_WARP_NO_LDS) |
             (0 if pipelined else capi.DF_WARP_NO_PIPELINE) | (0 if zero_skip else capi.DF_WARP_NO_ZERO_SKIP) |
-            (0 if depth_pyramid else capi.DF_WARP_NO_DEPTH_PYRAMID) | (capi.DF_WARP_STEADY_PREFETCH if prefetch == "steady" else 0 if prefetch else capi.DF_WARP_NO_PREFETCH) |
-            (0 if codes else capi.DF_WARP_NO_CODES) | (0 if sub_verdict else capi.DF_WARP_NO_SUB_VERDICT) |
-            (capi.DF_WARP_BLOCK_MODEL_NOW if block_model == "now" else 0 if block_model else capi.DF_WARP_NO_BLOCK_MODEL),
+            (0 if depth_pyramid else capi.DF_WARP_NO_DEPTH_PYRAMID) | self._verdict_flags(prefetch, block_model, codes, sub_verdict),
             _ptr(n_updated) if n_updated is not None else None, _stream()), "dfusion_integrate_warped")
         if sync:
             torch.cuda.current_stream().synchronize()
@@ -275,10 +280,7 @@ class TsdfVolume:
         capi.check(capi.lib().dfusion_integrate_warped_prepare(
             dp, pitch, cols, rows, self.c_volume(), self.c_slab(), capi.floats(aff12(self.pose_)),
             capi.floats(aff12(world2cam)), intr.as_proj(), warp_field.handle, k,
-            (capi.DF_WARP_STEADY_PREFETCH if prefetch == "steady" else 0 if prefetch else capi.DF_WARP_NO_PREFETCH) |
-            (0 if codes else capi.DF_WARP_NO_CODES) | (0 if sub_verdict else capi.DF_WARP_NO_SUB_VERDICT) |
-            (capi.DF_WARP_BLOCK_MODEL_NOW if block_model == "now" else 0 if block_model else capi.DF_WARP_NO_BLOCK_MODEL),
-            _stream()), "dfusion_integrate_warped_prepare")
+            self._verdict_flags(prefetch, block_model, codes, sub_verdict), _stream()), "dfusion_integrate_warped_prepare")
 
     def integrate_warped_sweep(self, warp_field, n_updated=None, sync=False):
         capi.check(capi.lib().dfusion_integrate_warped_sweep(self.c_volume(), self.c_slab(), warp_field.handle,
