@@ -64,6 +64,7 @@ SYMBOLS = [
     "dfusion_warp_extend", "dfusion_warp_solve", "dfusion_warp_node_graph", "dfusion_extract_mesh",
     "dfusion_warp_solve_robust", "dfusion_associate_projective", "dfusion_warp_solve_plane",
     "dfusion_color_clear", "dfusion_color_integrate", "dfusion_color_fetch", "dfusion_warp_solve_rigid", "dfusion_render_mesh",
+    "dfusion_warp_set_graph_hierarchy", "dfusion_warp_graph_levels",
 ]
 
 
@@ -151,6 +152,8 @@ def load(path, strict=True):
     L.dfusion_warp_solve_data_term.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]
     L.dfusion_warp_solve.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp, vp, vp]
     L.dfusion_warp_node_graph.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.dfusion_warp_set_graph_hierarchy.argtypes = [vp, C.c_int, C.c_float, C.c_float]
+    L.dfusion_warp_graph_levels.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.dfusion_warp_solve_robust.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float,
                                             vp, vp, vp, vp, vp]
     L.dfusion_warp_solve_plane.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float,

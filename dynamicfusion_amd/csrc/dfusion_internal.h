@@ -138,6 +138,7 @@ struct DfBlockCodes {
 };
 
 struct DfPrepared;                             // (dfusion_warp.hip)
+#define DF_GRAPH_MAX_LEVELS 8                  // levels of the hierarchical node graph at most (dfusion_warp_graph.hip)
 
 struct __attribute__((visibility("hidden"))) DfWarpField {     // (opaque in dfusion.h: the library exports none of its members)
     DfWarpField(); ~DfWarpField();             // (dfusion_warp.hip, where DfPrepared is complete)
@@ -185,6 +186,12 @@ struct __attribute__((visibility("hidden"))) DfWarpField {     // (opaque in dfu
     // graph_kg = 0: none -- dfusion_warp_set_nodes and an extend that adds nodes drop it, the next regularised solve rebuilds it
     DfDevBuf<int> graph_nbr; DfDevBuf<float> graph_alpha; DfDevBuf<unsigned int> graph_in_off, graph_in_edge; DfDevBuf<char> graph_ws;
     int graph_kg = 0;
+    // the hierarchical form of that graph (dfusion_warp_graph.hip; dfusion_warp_set_graph_hierarchy): the setting -- hier_levels = 0: the
+    // flat graph -- which outlives the graph, and with the graph the highest level of every node top[M], the level sizes |S_0..S_8| and
+    // the effective depth L' (0: the graph held is the flat one)
+    int hier_levels = 0; float hier_radius = 0.f, hier_beta = 0.f;
+    DfDevBuf<int> graph_top; DfDevBuf<char> graph_hws;
+    int graph_sizes[DF_GRAPH_MAX_LEVELS + 1] = {}; int graph_eff = 0;
     // points an indexed k-NN / warp pass left to the scan kernel: [0] count, [1..] ids
     DfDevBuf<int> pt_ids;
     int pt_image_cols = 0;                             // dfusion_warp_set_point_tiling: 0 = point queries in linear order
@@ -241,6 +248,8 @@ DF_LOCAL int df_warp_pack_current(DfWarpField* wf, const float* pos, const float
 DF_LOCAL int df_warp_build_tie_tree(DfWarpField* wf, hipStream_t st);
 // dfusion_warp_index.hip
 DF_LOCAL int df_index_bricks(DfWarpField* wf, const DfVolume& v, const float vol2world[12], int k, hipStream_t st);
+// dfusion_warp_graph.hip
+DF_LOCAL int df_hg_build(DfWarpField* wf, int kg, unsigned int* keys, unsigned int* vals, hipStream_t st);
 // dfusion_warp.hip
 DF_LOCAL DfWarpedArgs df_table_args(const DfWarpField* wf);
 DF_LOCAL int df_tables_complete(DfWarpField* wf, hipStream_t st);

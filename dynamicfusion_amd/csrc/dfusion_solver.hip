@@ -943,7 +943,8 @@ static int df_sv_sort_bytes(size_t E, int end_bit, hipStream_t st, size_t* bytes
     return DF_OK;
 }
 
-// The node graph of the handle for `kg` neighbours, made on first use and kept until the node set changes (graph_kg = 0).
+// The node graph of the handle for `kg` neighbours, made on first use and kept until the node set or the hierarchy setting changes
+// (graph_kg = 0).
 static int df_sv_graph(DfWarpField* wf, int kg, dfStream stream)
 {
     if (wf->graph_kg == kg) return DF_OK;
@@ -966,11 +967,17 @@ static int df_sv_graph(DfWarpField* wf, int kg, dfStream stream)
     if ((rc = wf->graph_ws.reserve(carve(nullptr)))) return rc;
     carve(wf->graph_ws);
     const dim3 gM((M + 255) / 256);
-    hipLaunchKernelGGL(df_sv_graph_pos_kernel, gM, dim3(256), 0, st, wf->pos_sigma, M, pos3);
-    DF_LAUNCH_CHECK();
-    if ((rc = dfusion_knn(wf, kq, pos3, M, idx, d2, stream))) return rc;
-    hipLaunchKernelGGL(df_sv_graph_kernel, gM, dim3(256), 0, st, idx, wf->pos_sigma, M, kg, wf->graph_nbr.p, wf->graph_alpha.p, keys, vals);
-    DF_LAUNCH_CHECK();
+    // the edges: the hierarchy's (dfusion_warp_graph.hip) where the handle asks for one and it has a level to offer, else the flat graph
+    memset(wf->graph_sizes, 0, sizeof(wf->graph_sizes));
+    wf->graph_sizes[0] = M; wf->graph_eff = 0;                         // (without the setting there are no levels: S_0 alone)
+    if (wf->hier_levels > 0 && (rc = df_hg_build(wf, kg, keys, vals, st))) return rc;
+    if (wf->graph_eff == 0) {
+        hipLaunchKernelGGL(df_sv_graph_pos_kernel, gM, dim3(256), 0, st, wf->pos_sigma, M, pos3);
+        DF_LAUNCH_CHECK();
+        if ((rc = dfusion_knn(wf, kq, pos3, M, idx, d2, stream))) return rc;
+        hipLaunchKernelGGL(df_sv_graph_kernel, gM, dim3(256), 0, st, idx, wf->pos_sigma, M, kg, wf->graph_nbr.p, wf->graph_alpha.p, keys, vals);
+        DF_LAUNCH_CHECK();
+    }
     DF_HIP(hipcub::DeviceRadixSort::SortPairs(sort, sort_bytes, keys, skeys, vals, wf->graph_in_edge.p, (int)E, 0, 16, st));   // stable
     hipLaunchKernelGGL(df_sv_offsets_kernel, dim3((unsigned)((E + 1 + 255) / 256)), dim3(256), 0, st, skeys, (int)E, M, wf->graph_in_off);
     DF_LAUNCH_CHECK();
@@ -1369,5 +1376,19 @@ extern "C" int dfusion_warp_node_graph(DfWarpField* wf, int kg, int* nbr, float*
     const size_t E = (size_t)wf->M * kg;
     DF_HIP(hipMemcpyAsync(nbr, wf->graph_nbr, E * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (alpha) DF_HIP(hipMemcpyAsync(alpha, wf->graph_alpha, E * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return DF_OK;
+}
+
+extern "C" int dfusion_warp_graph_levels(DfWarpField* wf, int kg, int* top, int* sizes, int* effective, dfStream stream)
+{
+    if (!wf || kg < 1 || kg > 7 || wf->M < kg + 1) return DF_E_INVALID;
+    const int rc = df_sv_graph(wf, kg, stream);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const bool hier = wf->hier_levels > 0;                             // (without the setting no top[] is made: every node's is 0)
+    if (top && hier) DF_HIP(hipMemcpyAsync(top, wf->graph_top, (size_t)wf->M * sizeof(int), hipMemcpyDeviceToDevice, st));
+    if (top && !hier) DF_HIP(hipMemsetAsync(top, 0, (size_t)wf->M * sizeof(int), st));
+    if (sizes) DF_HIP(hipMemcpyAsync(sizes, wf->graph_sizes, sizeof(wf->graph_sizes), hipMemcpyHostToDevice, st));
+    if (effective) DF_HIP(hipMemcpyAsync(effective, &wf->graph_eff, sizeof(int), hipMemcpyHostToDevice, st));
     return DF_OK;
 }

@@ -8,6 +8,8 @@
 //       + setPointToPlane                                                      -> dfusion_warp_solve_plane
 //   warp_solve rigid  [neighbours lambda rounds tukey_c huber_delta]       default 4 1 3 0.02 0.01      (lambda_rot = 0.01)
 //       + setNodeRotations, on the unwarped points and normals                 -> dfusion_warp_solve_rigid
+// A last word `hier` (after the mode's arguments, or after the mode alone) puts the hierarchy under the regularisation term:
+//       + setRegularisationHierarchy(2, 0.5, 2)
 // The inputs come from 32-bit linear congruential generators and exact float arithmetic (the normals of `plane` and `rigid` from a second
 // one, after everything else: components in [-1, 1), not unit length), so that tests/solver_cases.py can make the same problem for the
 // Python mirror and the restatements, and the tests compare the bits.
@@ -32,9 +34,11 @@ int main(int argc, char** argv)
     const char* const mode = argc > 1 ? argv[1] : "";
     const bool reg = !std::strcmp(mode, "reg"), robust = !std::strcmp(mode, "robust"), plane = !std::strcmp(mode, "plane"), rigid = !std::strcmp(mode, "rigid");
     if (!reg && !robust && !plane && !rigid) {
-        std::fprintf(stderr, "usage: warp_solve reg [neighbours lambda]\n       warp_solve robust|plane|rigid [neighbours lambda rounds tukey_c huber_delta]\n");
+        std::fprintf(stderr, "usage: warp_solve reg [neighbours lambda] [hier]\n       warp_solve robust|plane|rigid [neighbours lambda rounds tukey_c huber_delta] [hier]\n");
         return 2;
     }
+    const bool hier = argc > 2 && !std::strcmp(argv[argc - 1], "hier");
+    if (hier) --argc;
     const bool given = argc > (reg ? 3 : 6);                                // all of the mode's arguments, or the defaults
     const int neighbours = given ? std::atoi(argv[2]) : 4;
     const float lambda = given ? (float)std::atof(argv[3]) : 1.0f;
@@ -65,6 +69,7 @@ int main(int argc, char** argv)
     wf.setSolverIterations(20);
     wf.setSolverDamping(1e-3f);
     wf.setRegularisation(neighbours, lambda);
+    if (hier) wf.setRegularisationHierarchy(2, 0.5f, 2.f);
     if (!reg) wf.setRobust(rounds, tukey_c, huber_delta);
     if (with_normals) wf.setPointToPlane(true);
     if (rigid) wf.setNodeRotations(true, 0.01f);

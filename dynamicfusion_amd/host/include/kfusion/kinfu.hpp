@@ -53,6 +53,9 @@ namespace kfusion
                                              // kinfu.cpp:118; the synthetic sequence has converged to 4 digits by 40)
         int warp_reg_neighbours = 0;         // regularisation of the warp solve (WarpField::setRegularisation): graph neighbours per node,
         float warp_reg_lambda = 0.f;         // and the term's weight; 0 = off, the data term alone as in the reference
+        int warp_reg_levels = 0;             // the term over the paper's node hierarchy (WarpField::setRegularisationHierarchy): levels, 0 = the
+        float warp_reg_radius = 0.05f;       // flat graph; the cell edge of level 1 (metres: twice the seed nodes' spacing is a start) and
+        float warp_reg_beta = 4.f;           // its growth from a level to the next
         int warp_robust_rounds = 1;          // robust warp solve (WarpField::setRobust): re-weighted rounds per frame,
         float warp_tukey_c = 0.f;            // the Tukey threshold of the point residuals (metres; 0 = quadratic data term)
         float warp_huber_delta = 0.f;        // and the Huber threshold of the graph edges (0 = quadratic regularisation); default: off

@@ -90,6 +90,12 @@ namespace kfusion
         /// nearest other nodes with weight `lambda` (dfusion_warp_solve).  Off by default (neighbours = 0 or lambda = 0): energy_data is
         /// then the data term alone, as in the reference.
         void setRegularisation(int neighbours, float lambda) { reg_neighbours_ = neighbours; reg_lambda_ = lambda; }
+        /// The paper's HIERARCHY of nodes under that term (section 3.4; dfusion_warp_set_graph_hierarchy): level l keeps one node per
+        /// cell of edge radius * beta^(l-1) of the level below, and a node's `neighbours` edges go to its nearest nodes one level up, so
+        /// that a correction crosses a long unobserved stretch of nodes in a few solver steps.  levels = 0 (the default): the flat graph.
+        /// The setting stays with the field: after extend() or a commit that changes positions the next energy_data makes the
+        /// hierarchy of the new node set.  Values outside 0..8, radius > 0, beta >= 1 raise an error and change nothing.
+        void setRegularisationHierarchy(int levels, float radius, float beta = 4.f);
         /// DynamicFusion's robust penalties in energy_data (dfusion_warp_solve_robust): `rounds` re-weighted solves with a Tukey weight
         /// (threshold `tukey_c`, metres) on every point and a Huber weight (threshold `huber_delta`) on every graph edge; a threshold of 0
         /// keeps that term quadratic.  Off by default (rounds <= 1 and both thresholds 0): energy_data then takes exactly the path above.
@@ -157,6 +163,7 @@ namespace kfusion
         float solver_lambda_ = 0.f;
         int reg_neighbours_ = 0;
         float reg_lambda_ = 0.f;
+        int hier_levels_ = 0; float hier_radius_ = 0.f, hier_beta_ = 0.f;   // what the handle was last given (setRegularisationHierarchy)
         int robust_rounds_ = 1;
         float tukey_c_ = 0.f, huber_delta_ = 0.f;
         bool point_to_plane_ = false;

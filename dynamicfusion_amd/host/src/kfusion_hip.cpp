@@ -585,6 +585,13 @@ void WarpField::setTransformsDevice(const cuda::DeviceArray<float>& dq8)
     nodes_stale_ = true;
 }
 
+void WarpField::setRegularisationHierarchy(int levels, float radius, float beta)
+{
+    if (levels == hier_levels_ && (levels == 0 || (radius == hier_radius_ && beta == hier_beta_))) return;   // (the call drops the graph: only for a new setting)
+    KF_DF(dfusion_warp_set_graph_hierarchy(handle_, levels, radius, beta));
+    hier_levels_ = levels; hier_radius_ = radius; hier_beta_ = beta;
+}
+
 int WarpField::extend(const std::vector<Vec3f>& points, float radius, float sigma)
 {
     static_assert(sizeof(Vec3f) == 12, "Vec3f must be 3 packed floats");
@@ -1083,6 +1090,7 @@ void KinFu::optimiseWarp(std::vector<Vec3f>& canonical, std::vector<Vec3f>& cano
     if (params_.warp_solver_iterations <= 0) return;
     warp_->setSolverIterations(params_.warp_solver_iterations);
     warp_->setRegularisation(params_.warp_reg_neighbours, params_.warp_reg_lambda);
+    warp_->setRegularisationHierarchy(params_.warp_reg_levels, params_.warp_reg_radius, params_.warp_reg_beta);
     warp_->setRobust(params_.warp_robust_rounds, params_.warp_tukey_c, params_.warp_huber_delta);
     warp_->energy_data(canonical, canonical_normals, live, canonical_normals);
 }
@@ -1317,6 +1325,7 @@ void KinFu::dynamicfusion(cuda::Depth& depth, cuda::Cloud live_frame, cuda::Norm
                                                depth.cols(), depth.rows(), nullptr, nullptr));
             warp_->setSolverIterations(params_.warp_solver_iterations);
             warp_->setRegularisation(params_.warp_reg_neighbours, params_.warp_reg_lambda);
+            warp_->setRegularisationHierarchy(params_.warp_reg_levels, params_.warp_reg_radius, params_.warp_reg_beta);
             warp_->setRobust(params_.warp_robust_rounds, params_.warp_tukey_c, params_.warp_huber_delta);
             warp_->setPointToPlane(params_.warp_point_to_plane);
             warp_->setNodeRotations(rotations, params_.warp_rot_lambda);

@@ -239,3 +239,21 @@ class WarpField:
         alpha = torch.empty((self.M, max(kg, 0)), dtype=torch.float32, device=self.device)
         capi.check(capi.lib().dfusion_warp_node_graph(self.handle, kg, _ptr(nbr), _ptr(alpha), _stream()), "dfusion_warp_node_graph")
         return nbr, alpha
+
+    def set_graph_hierarchy(self, levels, radius, beta=4.0):
+        """Regularise over DynamicFusion's hierarchy of nodes instead of the flat graph (include/dfusion.h
+        dfusion_warp_set_graph_hierarchy): level l keeps one node per cell of edge radius * beta^(l-1) of the level below, and a node's
+        edges go to its nearest nodes one level up, so a correction crosses a long unobserved stretch in a few steps.  levels = 0
+        switches it off.  The setting stays on the field; extend and set_nodes only drop the graph built from it."""
+        capi.check(capi.lib().dfusion_warp_set_graph_hierarchy(self.handle, int(levels), float(radius), float(beta)),
+                   "dfusion_warp_set_graph_hierarchy")
+
+    def graph_levels(self, kg):
+        """The levels behind node_graph(kg): (top int32 [M] the highest level of every node, sizes int32 [9] |S_0| .. |S_8|, effective
+        int32 [1] the depth in use; 0: the flat graph) device tensors."""
+        top = torch.empty(self.M, dtype=torch.int32, device=self.device)
+        sizes = torch.empty(9, dtype=torch.int32, device=self.device)
+        effective = torch.empty(1, dtype=torch.int32, device=self.device)
+        capi.check(capi.lib().dfusion_warp_graph_levels(self.handle, int(kg), _ptr(top), _ptr(sizes), _ptr(effective), _stream()),
+                   "dfusion_warp_graph_levels")
+        return top, sizes, effective

@@ -532,6 +532,28 @@ int dfusion_warp_solve_rigid(DfWarpField *wf, int k, const float *canonical_dev,
 /* The node graph dfusion_warp_solve uses for `kg` (1..7, M >= kg + 1; built now if the handle does not hold it):
  * nbr_dev[M*kg] int32 the head node of every edge, alpha_dev[M*kg] (nullable) the edge weights.                                      */
 int dfusion_warp_node_graph(DfWarpField *wf, int kg, int *nbr_dev, float *alpha_dev, dfStream stream);
+/* The HIERARCHICAL node graph (DynamicFusion section 3.3 eq. 8 and section 3.4: the regularisation graph is a hierarchy of nodes, level
+ * l + 1 a coarser subsampling of level l, edges from a node to its nearest nodes one level up) -- additions to ABI 7.  A setting of the
+ * handle, off (levels = 0) on every new handle; with it on, the four regularised solves and dfusion_warp_node_graph use this graph in
+ * place of the flat one, in the same layout (kg outgoing edges a node, e = i * kg + s):
+ *   levels    S_0 = every node.  S_l is made from S_{l-1} by dfusion_warp_extend's decimation with cell edge c_l, c_1 = radius,
+ *             c_{l+1} = f32(c_l * beta): the cell of p is floorf(p / c_l) per axis (IEEE f32 division); a node with a non-finite
+ *             coordinate or |p / c_l| >= 2^30 on an axis is never a member; the lowest node index of a cell is.  A c_l that overflows to
+ *             infinity leaves level l and all above it empty.
+ *   depth     L' = the largest l <= levels with |S_l| >= kg + 1;  top(i) = the highest l <= L' with i in S_l.
+ *   edges     node i's kg targets are the nearest members of S_t \ {i}, t = min(top(i) + 1, L'), by (d2, node index) ascending,
+ *             d2 = (dx dx + dy dy) + dz dz in f32 (query minus candidate, no contraction), a NaN d2 after every finite one;
+ *             alpha_e = max(dg_w_i, dg_w_j).
+ * L' = 0 (few nodes, or all in one cell): the flat graph, bit for bit.  The setting outlives the graph: dfusion_warp_set_nodes and a
+ * dfusion_warp_extend that adds nodes drop the graph, and the next solve builds the hierarchy of the new node set.  Restated in
+ * tests/solver_hier_ref.py.
+ *   levels  0..8 (0 = off; radius and beta are then stored and not looked at)   radius  finite, > 0   beta  finite, >= 1
+ * The call stores the three values and drops the graph.  DF_E_INVALID (the handle stays as it was): anything outside these ranges.    */
+int dfusion_warp_set_graph_hierarchy(DfWarpField *wf, int levels, float radius, float beta);
+/* The levels behind the graph the handle's setting selects for `kg` (1..7, M >= kg + 1; built now if the handle does not hold it).  Every
+ * pointer may be NULL:  top_dev[M] int32 top(i);  sizes_dev[9] int32 |S_0| .. |S_8|, 0 past `levels`;  effective_dev[1] int32 L'
+ * (0: the graph is the flat one).  With the hierarchy off: top = 0, sizes = {M, 0, ...}, L' = 0.                                       */
+int dfusion_warp_graph_levels(DfWarpField *wf, int kg, int *top_dev, int *sizes_dev, int *effective_dev, dfStream stream);
 
 /* The north-star kernel: per-voxel DQB (WarpField::DQB, warp_field.cpp:203-217) composed with
  * TsdfIntegrator (tsdf_volume.cu:77-104): x_c = vol2world*voxel, x_w = DQB(x_c).transform(x_c),
