@@ -65,6 +65,7 @@ SYMBOLS = [
     "dfusion_warp_solve_robust", "dfusion_associate_projective", "dfusion_warp_solve_plane",
     "dfusion_color_clear", "dfusion_color_integrate", "dfusion_color_fetch", "dfusion_warp_solve_rigid", "dfusion_render_mesh",
     "dfusion_warp_set_graph_hierarchy", "dfusion_warp_graph_levels",
+    "dfusion_warp_set_preconditioner", "dfusion_warp_preconditioner",
 ]
 
 
@@ -154,6 +155,8 @@ def load(path, strict=True):
     L.dfusion_warp_node_graph.argtypes = [vp, C.c_int, vp, vp, vp]
     L.dfusion_warp_set_graph_hierarchy.argtypes = [vp, C.c_int, C.c_float, C.c_float]
     L.dfusion_warp_graph_levels.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.dfusion_warp_set_preconditioner.argtypes = [vp, C.c_int]
+    L.dfusion_warp_preconditioner.argtypes = [vp, C.POINTER(C.c_int)]
     L.dfusion_warp_solve_robust.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float,
                                             vp, vp, vp, vp, vp]
     L.dfusion_warp_solve_plane.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float,

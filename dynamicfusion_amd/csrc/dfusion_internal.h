@@ -192,6 +192,8 @@ struct __attribute__((visibility("hidden"))) DfWarpField {     // (opaque in dfu
     int hier_levels = 0; float hier_radius = 0.f, hier_beta = 0.f;
     DfDevBuf<int> graph_top; DfDevBuf<char> graph_hws;
     int graph_sizes[DF_GRAPH_MAX_LEVELS + 1] = {}; int graph_eff = 0;
+    // dfusion_warp_set_preconditioner: 0 = none, 1 = 6x6 node blocks; read by dfusion_warp_solve_rigid alone (dfusion_solver.hip)
+    int precond = 0;
     // points an indexed k-NN / warp pass left to the scan kernel: [0] count, [1..] ids
     DfDevBuf<int> pt_ids;
     int pt_image_cols = 0;                             // dfusion_warp_set_point_tiling: 0 = point queries in linear order

@@ -18,7 +18,8 @@
 // dfusion_warp_solve adds DynamicFusion's regularisation term over a node graph, dfusion_warp_solve_robust a Tukey
 // penalty on the data term and a Huber penalty on the edges by re-weighted rounds, dfusion_warp_solve_plane takes the
 // data term along the model normals (point-to-plane), and dfusion_warp_solve_rigid makes the node rotations
-// unknowns too, against the warp dfusion_warp_points applies.  The host pipeline is at the end of this file.  Every entry point fills one
+// unknowns too, against the warp dfusion_warp_points applies, with 6x6 node blocks as preconditioner where the handle asks for them
+// (DESIGN.md 21).  The host pipeline is at the end of this file.  Every entry point fills one
 // description of its solve (SvSolve), checked by df_sv_check; df_sv_context makes of it what a solve works with (SvContext: flags, grids,
 // one workspace, the graph, the CG kernels) and holds every stage the solves share -- the preparation, the penalty weights, the energies,
 // the CG skeleton, the outputs -- in which a term that is switched off launches nothing.  What is left in the two round loops is their
@@ -921,6 +922,282 @@ __global__ __launch_bounds__(256) void df_sv_rigid_writeback_kernel(const float4
     o[0] = r1.w; o[1] = r1.x; o[2] = r1.y; o[3] = r1.z; o[4] = d.w; o[5] = d.x; o[6] = d.y; o[7] = d.z;
 }
 
+// ---------------------------------------------------------------- 6x6 node-block Jacobi preconditioner of the solve with rotations
+// dfusion_warp_set_preconditioner(1): per round the diagonal block B_n of every node of J^T Omega J + lambda_reg L + damping over its six
+// unknowns (omega_n, tau_n), factored B_n = L L^T in f32, and a conjugate-gradient recurrence preconditioned with them: z = B^-1 r is two
+// triangular substitutions in the node's thread, inside the init and step kernels, so a step launches what it launched.  The rule, sum
+// for sum, is restated in tests/solver_precond_ref.py.  Entry (i, j), i <= j, of a block sits at SV_UP(i, j) of its 21 upper-triangle
+// entries, L_ij (j <= i) at SV_LO(i, j); 0..2 = omega x y z, 3..5 = tau x y z.
+#define SV_UP(i, j) ((i) * 6 - (i) * ((i) - 1) / 2 + ((j) - (i)))
+#define SV_LO(i, j) ((i) * ((i) + 1) / 2 + (j))
+#define SV_PC_PLANES 22             // fac [22][M]: the 21 entries of L, then 1 (factored) or 0 (a pivot failed: the identity)
+
+// OO entries from the six sums xx xy xz yy yz zz of outer products: |m|^2 I - m m^T
+__device__ __forceinline__ void sv_pc_rotation_part(const float (&P)[6], float (&out)[6])
+{
+    out[0] = P[3] + P[5]; out[1] = -P[1]; out[2] = -P[2]; out[3] = P[0] + P[5]; out[4] = -P[4]; out[5] = P[0] + P[3];
+}
+
+// ---- the blocks and their factors: df_sv_rigid_jt_apply_kernel's walk, thread stride and tree over the node's list with, per entry,
+// m = w q_n - wn a_v and m' = w' q_n - wn' a_v (w', wn': the Tukey-scaled copies, or the lists themselves):
+//   point-to-point, 10 sums: P_cd += m'_c m_d (c <= d), K_c += w' m_c, T += w' w ; PLANE, 21 sums: B_ij += h'_i h_j, h = (n' x m, w n'),
+//   h' = (n' x m', w' n').
+// Lane 0 then adds the graph term (kg > 0: outgoing edges in slot order, incoming in ascending edge id) and the damping, factors the
+// block and stores the factor.
+template <bool PLANE>
+__global__ __launch_bounds__(256) void df_sv_pc_blocks_kernel(const unsigned int* __restrict__ off, const unsigned int* __restrict__ sorted_pt,
+                                                              const float* __restrict__ sw, const float* __restrict__ swn,
+                                                              const float* __restrict__ sw_use, const float* __restrict__ swn_use, int M,
+                                                              const float* __restrict__ a, const float4* __restrict__ qc,
+                                                              const float* __restrict__ nw, const float* __restrict__ alpha,
+                                                              const unsigned int* __restrict__ in_off, const unsigned int* __restrict__ in_edge,
+                                                              int kg, const float* __restrict__ arm, float lambda_reg, float lambda,
+                                                              float lambda_rot, float* __restrict__ fac)
+{
+    constexpr int S = PLANE ? 21 : 10;
+    __shared__ float lds[S * 128];
+    const int n = blockIdx.x, t = threadIdx.x;
+    const unsigned int b0 = off[n], e_end = off[n + 1];
+    const float4 qn = qc[n];
+    float s[S];
+#pragma unroll
+    for (int c = 0; c < S; ++c) s[c] = 0.f;
+    for (unsigned int i = b0 + t; i < e_end; i += 256) {
+        const unsigned int v = sorted_pt[i];
+        const float we = sw[i], wne = swn[i], wse = sw_use[i], wnse = swn_use[i];
+        const float ax = a[3 * v], ay = a[3 * v + 1], az = a[3 * v + 2];
+        const float m[3] = {we * qn.x - wne * ax, we * qn.y - wne * ay, we * qn.z - wne * az};
+        const float ms[3] = {wse * qn.x - wnse * ax, wse * qn.y - wnse * ay, wse * qn.z - wnse * az};
+        if constexpr (PLANE) {
+            const float nx = nw[3 * v], ny = nw[3 * v + 1], nz = nw[3 * v + 2];
+            const float h[6] = {ny * m[2] - nz * m[1], nz * m[0] - nx * m[2], nx * m[1] - ny * m[0], we * nx, we * ny, we * nz};
+            const float hs[6] = {ny * ms[2] - nz * ms[1], nz * ms[0] - nx * ms[2], nx * ms[1] - ny * ms[0], wse * nx, wse * ny, wse * nz};
+#pragma unroll
+            for (int i6 = 0; i6 < 6; ++i6)
+#pragma unroll
+                for (int j6 = i6; j6 < 6; ++j6) s[SV_UP(i6, j6)] = s[SV_UP(i6, j6)] + hs[i6] * h[j6];
+        } else {
+            s[0] = s[0] + ms[0] * m[0]; s[1] = s[1] + ms[0] * m[1]; s[2] = s[2] + ms[0] * m[2];
+            s[3] = s[3] + ms[1] * m[1]; s[4] = s[4] + ms[1] * m[2]; s[5] = s[5] + ms[2] * m[2];
+            s[6] = s[6] + wse * m[0]; s[7] = s[7] + wse * m[1]; s[8] = s[8] + wse * m[2];
+            s[9] = s[9] + wse * we;
+        }
+    }
+    sv_node_tree(s, lds, [&]() {
+        float B[21];
+        if constexpr (PLANE) {
+#pragma unroll
+            for (int c = 0; c < 21; ++c) B[c] = s[c];
+        } else {
+#pragma unroll
+            for (int c = 0; c < 21; ++c) B[c] = 0.f;
+            const float P[6] = {s[0], s[1], s[2], s[3], s[4], s[5]};
+            float oo[6];
+            sv_pc_rotation_part(P, oo);
+            B[SV_UP(0, 0)] = oo[0]; B[SV_UP(0, 1)] = oo[1]; B[SV_UP(0, 2)] = oo[2]; B[SV_UP(1, 1)] = oo[3]; B[SV_UP(1, 2)] = oo[4]; B[SV_UP(2, 2)] = oo[5];
+            B[SV_UP(0, 4)] = s[8]; B[SV_UP(0, 5)] = -s[7]; B[SV_UP(1, 3)] = -s[8]; B[SV_UP(1, 5)] = s[6]; B[SV_UP(2, 3)] = s[7]; B[SV_UP(2, 4)] = -s[6];
+            B[SV_UP(3, 3)] = s[9]; B[SV_UP(4, 4)] = s[9]; B[SV_UP(5, 5)] = s[9];
+        }
+        if (kg > 0) {
+            float Q[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, KB[3] = {0.f, 0.f, 0.f}, AT = 0.f;
+            for (int sl = 0; sl < kg; ++sl) {
+                const int e = n * kg + sl;
+                const float al = alpha[e];
+                const float bx = arm[3 * e], by = arm[3 * e + 1], bz = arm[3 * e + 2];
+                const float abx = al * bx, aby = al * by, abz = al * bz;
+                Q[0] = Q[0] + abx * bx; Q[1] = Q[1] + abx * by; Q[2] = Q[2] + abx * bz; Q[3] = Q[3] + aby * by; Q[4] = Q[4] + aby * bz; Q[5] = Q[5] + abz * bz;
+                KB[0] = KB[0] + abx; KB[1] = KB[1] + aby; KB[2] = KB[2] + abz;
+                AT = AT + al;
+            }
+            for (unsigned int i = in_off[n]; i < in_off[n + 1]; ++i) AT = AT + alpha[in_edge[i]];
+            float oo[6];
+            sv_pc_rotation_part(Q, oo);
+            B[SV_UP(0, 0)] = B[SV_UP(0, 0)] + lambda_reg * oo[0]; B[SV_UP(0, 1)] = B[SV_UP(0, 1)] + lambda_reg * oo[1];
+            B[SV_UP(0, 2)] = B[SV_UP(0, 2)] + lambda_reg * oo[2]; B[SV_UP(1, 1)] = B[SV_UP(1, 1)] + lambda_reg * oo[3];
+            B[SV_UP(1, 2)] = B[SV_UP(1, 2)] + lambda_reg * oo[4]; B[SV_UP(2, 2)] = B[SV_UP(2, 2)] + lambda_reg * oo[5];
+            B[SV_UP(0, 4)] = B[SV_UP(0, 4)] + lambda_reg * -KB[2]; B[SV_UP(0, 5)] = B[SV_UP(0, 5)] + lambda_reg * KB[1];
+            B[SV_UP(1, 3)] = B[SV_UP(1, 3)] + lambda_reg * KB[2]; B[SV_UP(1, 5)] = B[SV_UP(1, 5)] + lambda_reg * -KB[0];
+            B[SV_UP(2, 3)] = B[SV_UP(2, 3)] + lambda_reg * -KB[1]; B[SV_UP(2, 4)] = B[SV_UP(2, 4)] + lambda_reg * KB[0];
+            const float tt = lambda_reg * AT;
+            B[SV_UP(3, 3)] = B[SV_UP(3, 3)] + tt; B[SV_UP(4, 4)] = B[SV_UP(4, 4)] + tt; B[SV_UP(5, 5)] = B[SV_UP(5, 5)] + tt;
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { B[SV_UP(i, i)] = B[SV_UP(i, i)] + lambda_rot; B[SV_UP(i + 3, i + 3)] = B[SV_UP(i + 3, i + 3)] + lambda; }
+        // Cholesky by rows; a pivot that is not > 0 or not finite makes the node's preconditioner the identity
+        float L[21];
+        bool ok = true;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) {
+                float sum = B[SV_UP(j, i)];
+#pragma unroll
+                for (int k = 0; k < j; ++k) sum = sum - L[SV_LO(i, k)] * L[SV_LO(j, k)];
+                if (i == j) { ok = ok && sum > 0.f && isfinite(sum); L[SV_LO(i, i)] = sqrtf(sum); }
+                else L[SV_LO(i, j)] = sum / L[SV_LO(j, j)];
+            }
+#pragma unroll
+        for (int c = 0; c < 21; ++c) fac[(size_t)c * M + n] = L[c];
+        fac[(size_t)21 * M + n] = ok ? 1.f : 0.f;
+    });
+}
+
+// z = B_n^-1 r for the six values of node n (r[0..2] omega, r[3..5] tau): forward and back substitution, k ascending in both
+__device__ __forceinline__ void sv_pc_apply(const float* __restrict__ fac, int M, int n, const float (&r)[6], float (&z)[6])
+{
+    float L[21];
+#pragma unroll
+    for (int c = 0; c < 21; ++c) L[c] = fac[(size_t)c * M + n];
+    const bool ok = fac[(size_t)21 * M + n] != 0.f;
+    float y[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        float t = r[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) t = t - L[SV_LO(i, k)] * y[k];
+        y[i] = t / L[SV_LO(i, i)];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        float t = y[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) t = t - L[SV_LO(k, i)] * z[k];
+        z[i] = t / L[SV_LO(i, i)];
+    }
+    if (!ok) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) z[i] = r[i];
+    }
+}
+
+// The vector kernels of the preconditioned recurrence are organised by node: thread t owns nodes t, t + 1024, ... with all six values
+// of each (entry n and entry M + n of the 2M-entry arrays).  A dot product adds, per node and component, the omega product and then the
+// tau product to the thread's partial; then sv_block_sum3 and the coupling (s0 + s1) + s2.  scal[SV_RR] holds r . z.
+__device__ __forceinline__ void sv_pc_load(const float* __restrict__ v, int M, int n, float (&o)[6])
+{
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { o[c] = v[3 * n + c]; o[3 + c] = v[3 * ((size_t)M + n) + c]; }
+}
+__device__ __forceinline__ void sv_pc_store(float* __restrict__ v, int M, int n, const float (&o)[6])
+{
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { v[3 * n + c] = o[c]; v[3 * ((size_t)M + n) + c] = o[3 + c]; }
+}
+__device__ __forceinline__ void sv_pc_dot(float (&s)[3], const float (&u)[6], const float (&v)[6])
+{
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { s[c] = s[c] + u[c] * v[c]; s[c] = s[c] + u[3 + c] * v[3 + c]; }
+}
+
+// x0 = 0, z0 = B^-1 r0, p0 = z0, r . z
+__global__ __launch_bounds__(SV_BLOCK) void df_sv_pc_init_kernel(const float* __restrict__ r, int M, float* __restrict__ x, float* __restrict__ p,
+                                                                 float* __restrict__ scal, const float* __restrict__ fac)
+{
+    __shared__ float lds[3 * SV_BLOCK];
+    float s[3] = {0.f, 0.f, 0.f};
+    const float zero[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int n = threadIdx.x; n < M; n += SV_BLOCK) {
+        float rv[6], zv[6];
+        sv_pc_load(r, M, n, rv);
+        sv_pc_apply(fac, M, n, rv, zv);
+        sv_pc_store(x, M, n, zero);
+        sv_pc_store(p, M, n, zv);
+        sv_pc_dot(s, rv, zv);
+    }
+    sv_block_sum3(s, lds);
+    sv_cg_couple<true>(s);
+    if (threadIdx.x == 0) {
+        for (int c = 0; c < 3; ++c) { scal[SV_RR + c] = s[c]; scal[SV_RR0 + c] = s[c]; }
+        scal[SV_ACTIVE] = (float)(s[0] > 0.f);
+    }
+}
+
+// A step: alpha = r.z / p.q ; x += alpha p ; r -= alpha q ; z = B^-1 r ; beta = (r.z)_new / (r.z)_old ; p = z + beta p ; frozen once
+// (r.z)_new <= 1e-10 (r.z)_0 or alpha == 0 (sv_cg_alpha / sv_cg_beta / sv_cg_freeze on r . z).  NPT > 0: M <= NPT * SV_BLOCK, and p and
+// q -- then z in q's place -- are read once and stay in registers through the three passes (df_sv_step_reg_kernel's variants, counted in
+// nodes: 1, 3 and 4 for 2M <= 2, 5, 8 x 1024; x, r and the factor are needed by the middle pass alone, which reads them node by node);
+// NPT = 0: any M, every pass reads what it needs.  Same node -> thread assignment, same sums, same trees either way.
+template <int NPT>
+__global__ __launch_bounds__(SV_BLOCK) void df_sv_pc_step_kernel(const float* __restrict__ q, int M, float* __restrict__ x, float* __restrict__ r,
+                                                                 float* __restrict__ p, float* __restrict__ scal, const float* __restrict__ fac)
+{
+    __shared__ float lds[3 * SV_BLOCK];
+    if (scal[SV_ACTIVE] == 0.f) return;                                 // frozen: the step would change nothing
+    constexpr int R = NPT > 0 ? NPT : 1;
+    float pv[R][6], qv[R][6];
+    float pq[3] = {0.f, 0.f, 0.f};
+    if constexpr (NPT > 0) {
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) {
+            const int n = threadIdx.x + j * SV_BLOCK;
+            if (n < M) { sv_pc_load(p, M, n, pv[j]); sv_pc_load(q, M, n, qv[j]); }
+        }
+#pragma unroll
+        for (int j = 0; j < NPT; ++j)
+            if (threadIdx.x + j * SV_BLOCK < M) sv_pc_dot(pq, pv[j], qv[j]);
+    } else {
+        for (int n = threadIdx.x; n < M; n += SV_BLOCK) {
+            sv_pc_load(p, M, n, pv[0]); sv_pc_load(q, M, n, qv[0]);
+            sv_pc_dot(pq, pv[0], qv[0]);
+        }
+    }
+    sv_block_sum3(pq, lds);
+    sv_cg_couple<true>(pq);
+    float alpha[3], rz_old[3];
+    for (int c = 0; c < 3; ++c) { rz_old[c] = scal[SV_RR + c]; alpha[c] = sv_cg_alpha(pq[c], rz_old[c]); }
+    float rz[3] = {0.f, 0.f, 0.f};
+    // x, r and z of one node; z takes q's place in qn, which has served
+    auto update = [&](int n, const float (&pn)[6], float (&qn)[6]) {
+        float xn[6], rn[6];
+        sv_pc_load(x, M, n, xn); sv_pc_load(r, M, n, rn);
+#pragma unroll
+        for (int c = 0; c < 6; ++c) { xn[c] = xn[c] + alpha[c % 3] * pn[c]; rn[c] = rn[c] - alpha[c % 3] * qn[c]; }
+        sv_pc_store(x, M, n, xn); sv_pc_store(r, M, n, rn);
+        sv_pc_apply(fac, M, n, rn, qn);
+        sv_pc_dot(rz, rn, qn);
+    };
+    if constexpr (NPT > 0) {
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) {
+            const int n = threadIdx.x + j * SV_BLOCK;
+            if (n < M) update(n, pv[j], qv[j]);
+        }
+    } else {
+        for (int n = threadIdx.x; n < M; n += SV_BLOCK) {
+            sv_pc_load(p, M, n, pv[0]); sv_pc_load(q, M, n, qv[0]);
+            update(n, pv[0], qv[0]);
+        }
+        __syncthreads();                                                // (the last pass reads r back)
+    }
+    sv_block_sum3(rz, lds);
+    sv_cg_couple<true>(rz);
+    float beta[3];
+    for (int c = 0; c < 3; ++c) beta[c] = sv_cg_beta(alpha[c], rz[c], rz_old[c]);
+    if constexpr (NPT > 0) {
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) {
+            const int n = threadIdx.x + j * SV_BLOCK;
+            if (n < M) {
+#pragma unroll
+                for (int c = 0; c < 6; ++c) pv[j][c] = qv[j][c] + beta[c % 3] * pv[j][c];
+                sv_pc_store(p, M, n, pv[j]);
+            }
+        }
+    } else {
+        // z is recomputed from the stored r: the same operations on the same values, so the same bits as in the pass above
+        for (int n = threadIdx.x; n < M; n += SV_BLOCK) {
+            float rn[6];
+            sv_pc_load(p, M, n, pv[0]); sv_pc_load(r, M, n, rn);
+            sv_pc_apply(fac, M, n, rn, qv[0]);
+#pragma unroll
+            for (int c = 0; c < 6; ++c) pv[0][c] = qv[0][c] + beta[c % 3] * pv[0][c];
+            sv_pc_store(p, M, n, pv[0]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) sv_cg_freeze<true>(alpha, rz, scal);
+}
+
 // ---------------------------------------------------------------- host side
 // 256-byte aligned pieces of one buffer.  A carve-up is written once and run twice: from base 0, where `at` ends as the size to
 // reserve, and from the reserved buffer's address.
@@ -1003,10 +1280,11 @@ struct SvWorkspace {
     float *y, *nw, *a; float4 *c, *qc, *rec; float* arm;    // rigid: [3N] warped points, warped normals (with normals), a_v ; [M] node
     float *wn, *swn, *swn_scaled;                           // centres c_n, q_n ; [2N] J^T's point records ; [3Eg] edge arms ; [E] normalised
                                                             // weights point-major, node-major, Tukey (otherwise empty; x, r, p, q: 6M floats)
+    float* fac;                                             // rigid with the preconditioner: [SV_PC_PLANES][M] block factors (otherwise empty)
     char* sort; size_t sort_bytes;
 };
 
-static int df_sv_workspace(DfWarpField* wf, int N, int k, int M, int Eg, bool plane, bool tukey, bool huber, bool rigid, hipStream_t st,
+static int df_sv_workspace(DfWarpField* wf, int N, int k, int M, int Eg, bool plane, bool tukey, bool huber, bool rigid, bool precond, hipStream_t st,
                            SvWorkspace* ws)
 {
     const size_t E = (size_t)N * k, n = N, m = M, eg = Eg, mx = rigid ? 2 * m : m;
@@ -1028,6 +1306,7 @@ static int df_sv_workspace(DfWarpField* wf, int N, int k, int M, int Eg, bool pl
         ws->a = b.take<float>(rigid ? 3 * n : 0); ws->c = b.take<float4>(rigid ? m : 0); ws->qc = b.take<float4>(rigid ? m : 0); ws->rec = b.take<float4>(rigid ? 2 * n : 0);
         ws->arm = b.take<float>(rigid ? 3 * eg : 0); ws->wn = b.take<float>(rigid ? E : 0); ws->swn = b.take<float>(rigid ? E : 0);
         ws->swn_scaled = b.take<float>(rigid && tukey ? E : 0);
+        ws->fac = b.take<float>(precond ? SV_PC_PLANES * m : 0);
         ws->sort = b.take<char>(ws->sort_bytes);
         return (size_t)(b.at - (uintptr_t)base);
     };
@@ -1060,12 +1339,19 @@ struct SvSolve {
     DfWarpField* wf; int k; const float *canonical, *live, *normals; int N;
     int iters; float lambda, lambda_rot; int kg; float lambda_reg; int rounds; float tukey_c, huber_delta;
     float *dq_out, *energy; int n_energy; float *point_weights, *edge_weights; dfStream stream;
+    int precond;                                            // dfusion_warp_solve_rigid alone: the handle's preconditioner setting (others leave it 0)
 };
 
 // The CG kernels by the number of unknown entries X (x, r, p, q stay in registers up to 8 * SV_BLOCK of them), and an apply kernel
 // template <K, PLANE> by the neighbour count (compile-time for 8 and 4).
 typedef void (*SvInitKernel)(const float*, int, float*, float*, float*);
 typedef void (*SvStepKernel)(const float*, int, float*, float*, float*, float*);
+typedef void (*SvPcStepKernel)(const float*, int, float*, float*, float*, float*, const float*);   // the preconditioned step, by M nodes
+static SvPcStepKernel df_sv_pc_step_for(int M)
+{
+    return 2 * M <= 2 * SV_BLOCK ? df_sv_pc_step_kernel<1> : 2 * M <= 5 * SV_BLOCK ? df_sv_pc_step_kernel<3>
+         : 2 * M <= 8 * SV_BLOCK ? df_sv_pc_step_kernel<4> : df_sv_pc_step_kernel<0>;
+}
 template <bool COUPLED> static SvStepKernel df_sv_step_for(int X)
 {
     return X <= 2 * SV_BLOCK ? df_sv_step_reg_kernel<2, COUPLED> : X <= 5 * SV_BLOCK ? df_sv_step_reg_kernel<5, COUPLED>
@@ -1085,6 +1371,7 @@ struct SvContext {                                          // (df_sv_context fi
     SvWorkspace ws;
     const float *sw_use, *swn_use, *alpha_use, *active; float* en;
     SvInitKernel init; SvStepKernel step;
+    SvPcStepKernel pc_step;                                 // non-null: the recurrence is preconditioned with the node blocks in ws.fac
     // Once per call, what depends only on the canonical points and the node positions (the graph is the context's already): the k-NN,
     // `setup` (the entries' weights and node ids, point-major), the node offsets and the node-major lists (w2 / sw2: see df_sv_lists)
     template <typename Setup> int prepare(Setup setup, const float* w2, float* sw2) const
@@ -1125,16 +1412,19 @@ struct SvContext {                                          // (df_sv_context fi
         else hipLaunchKernelGGL(df_sv_reg_energy_kernel, one, dim3(SV_BLOCK), 0, st, wf->graph_nbr.p, wf->graph_alpha.p, ws.g, x, Eg, s.kg, out);
     }
     // conjugate gradients from the right-hand side in ws.r: x0 = 0, p0 = r0, then `iters` steps of q = A p by the caller's launches
-    // (apply: ws.p -> the point side ; apply_t: the point side -> ws.q, damping included ; reg_apply: ws.q += lambda_reg L ws.p)
+    // (apply: ws.p -> the point side ; apply_t: the point side -> ws.q, damping included ; reg_apply: ws.q += lambda_reg L ws.p).
+    // With pc_step the init and the step are the preconditioned ones over ws.fac: the same number of launches.
     template <typename Apply, typename ApplyT, typename RegApply> int cg(Apply apply, ApplyT apply_t, RegApply reg_apply) const
     {
-        hipLaunchKernelGGL(init, one, dim3(SV_BLOCK), 0, st, ws.r, X, ws.x, ws.p, ws.scal);
+        if (pc_step) hipLaunchKernelGGL(df_sv_pc_init_kernel, one, dim3(SV_BLOCK), 0, st, ws.r, M, ws.x, ws.p, ws.scal, ws.fac);
+        else hipLaunchKernelGGL(init, one, dim3(SV_BLOCK), 0, st, ws.r, X, ws.x, ws.p, ws.scal);
         DF_LAUNCH_CHECK();
         for (int it = 0; it < s.iters; ++it) {
             apply();
             apply_t();
             if (reg) reg_apply();
-            hipLaunchKernelGGL(step, one, dim3(SV_BLOCK), 0, st, ws.q, X, ws.x, ws.r, ws.p, ws.scal);
+            if (pc_step) hipLaunchKernelGGL(pc_step, one, dim3(SV_BLOCK), 0, st, ws.q, M, ws.x, ws.r, ws.p, ws.scal, ws.fac);
+            else hipLaunchKernelGGL(step, one, dim3(SV_BLOCK), 0, st, ws.q, X, ws.x, ws.r, ws.p, ws.scal);
             DF_LAUNCH_CHECK();
         }
         return DF_OK;
@@ -1168,7 +1458,8 @@ static int df_sv_context(const SvSolve& s, bool rigid, SvContext* cx)
     const bool reg = s.kg > 0, tukey = s.tukey_c != 0.f, huber = reg && s.huber_delta != 0.f, plane = s.normals != nullptr;
     const int M = wf->M, X = rigid ? 2 * M : M, E = s.N * s.k, Eg = M * s.kg;
     int rc;
-    if ((rc = df_sv_workspace(wf, s.N, s.k, M, Eg, plane, tukey, huber, rigid, (hipStream_t)s.stream, &ws))) return rc;
+    const bool precond = rigid && s.precond == 1;
+    if ((rc = df_sv_workspace(wf, s.N, s.k, M, Eg, plane, tukey, huber, rigid, precond, (hipStream_t)s.stream, &ws))) return rc;
     if (reg && (rc = df_sv_graph(wf, s.kg, s.stream))) return rc;     // (the first call on a handle allocates graph_alpha, read just below)
     // one recurrence over all components where the matrix mixes them: point-to-plane, and the six unknowns of a node
     const bool coupled = plane || rigid;
@@ -1176,7 +1467,7 @@ static int df_sv_context(const SvSolve& s, bool rigid, SvContext* cx)
                     dim3((s.N + 255) / 256), dim3((M + 255) / 256), dim3((unsigned)(((size_t)E + 255) / 256)), dim3((Eg + 255) / 256), dim3(M), dim3(1), ws,
                     tukey ? ws.sw_scaled : ws.sw, tukey ? ws.swn_scaled : ws.swn, huber ? ws.alpha_scaled : wf->graph_alpha.p,
                     ws.scal + SV_ACTIVE, ws.scal + SV_ENERGY, coupled ? df_sv_init_kernel<true> : df_sv_init_kernel<false>,
-                    coupled ? df_sv_step_for<true>(X) : df_sv_step_for<false>(X)};
+                    coupled ? df_sv_step_for<true>(X) : df_sv_step_for<false>(X), precond ? df_sv_pc_step_for(M) : nullptr};
     return DF_OK;
 }
 
@@ -1295,6 +1586,12 @@ static int df_sv_rigid_rounds(const SvSolve& s)
             if (s.energy && first) cx.reg_energy(nullptr, cx.en + 2);
             DF_LAUNCH_CHECK();
         }
+        if (cx.pc_step) {                                               // the round's node blocks, factored (one launch a round)
+            hipLaunchKernelGGL(plane ? df_sv_pc_blocks_kernel<true> : df_sv_pc_blocks_kernel<false>, gW, dim3(256), 0, st, ws.off, ws.spt, ws.sw, ws.swn,
+                               cx.sw_use, cx.swn_use, M, ws.a, ws.qc, ws.nw, cx.alpha_use, wf->graph_in_off.p, wf->graph_in_edge.p, kg, ws.arm, s.lambda_reg,
+                               s.lambda, s.lambda_rot, ws.fac);
+            DF_LAUNCH_CHECK();
+        }
         rc = cx.cg([&]() { hipLaunchKernelGGL(j_apply, gN, dim3(256), 0, st, ws.w, ws.wn, ws.keys, N, k, M, ws.p, ws.a, ws.qc, ws.rec, cx.active, ws.nw); },
                    [&]() { hipLaunchKernelGGL(df_sv_rigid_jt_apply_kernel, gW, dim3(256), 0, st, ws.off, ws.spt, cx.sw_use, cx.swn_use, M, ws.rec, ws.qc, s.lambda,
                                               s.lambda_rot, ws.p, ws.q, cx.active); },
@@ -1364,8 +1661,22 @@ extern "C" int dfusion_warp_solve_rigid(DfWarpField* wf, int k, const float* can
                                         float lambda, float lambda_rot, int kg, float lambda_reg, int rounds, float tukey_c, float huber_delta,
                                         float* dq_out, float* energy, float* point_weights, float* edge_weights, dfStream stream)
 {
-    SvSolve s = {wf, k, canonical, live, normals, N, iters, lambda, lambda_rot, kg, lambda_reg, rounds, tukey_c, huber_delta, dq_out, energy, 4, point_weights, edge_weights, stream};
+    SvSolve s = {wf, k, canonical, live, normals, N, iters, lambda, lambda_rot, kg, lambda_reg, rounds, tukey_c, huber_delta, dq_out, energy, 4, point_weights, edge_weights, stream, wf ? wf->precond : 0};
     return df_sv_check(&s, lambda_rot >= 0.f) ? DF_E_INVALID : df_sv_rigid_rounds(s);
+}
+
+extern "C" int dfusion_warp_set_preconditioner(DfWarpField* wf, int mode)
+{
+    if (!wf || (mode != 0 && mode != 1)) return DF_E_INVALID;
+    wf->precond = mode;
+    return DF_OK;
+}
+
+extern "C" int dfusion_warp_preconditioner(const DfWarpField* wf, int* mode)
+{
+    if (!wf || !mode) return DF_E_INVALID;
+    *mode = wf->precond;
+    return DF_OK;
 }
 
 extern "C" int dfusion_warp_node_graph(DfWarpField* wf, int kg, int* nbr, float* alpha, dfStream stream)

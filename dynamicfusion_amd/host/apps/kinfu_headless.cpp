@@ -5,7 +5,8 @@
 //   warp data-term solve; depth: the reference's USE_DEPTH build -- depth pyramids and masked-depth ICP; assoc: projective data
 //   association in front of the warp solve, KinFuParams::warp_projective_association -- under trace its counts are printed per frame;
 //   plane: the warp solve's point-to-plane data term, KinFuParams::warp_point_to_plane; rigid: the node rotations as unknowns of the warp
-//   solve, KinFuParams::warp_solve_rotations with warp_rot_lambda = 1e-3 and 4 graph neighbours at weight 1; hier: the regularisation over
+//   solve, KinFuParams::warp_solve_rotations with warp_rot_lambda = 1e-3 and 4 graph neighbours at weight 1; pcg (beside rigid): that solve
+//   preconditioned with the node blocks, KinFuParams::warp_precondition; hier: the regularisation over
 //   the node hierarchy, KinFuParams::warp_reg_levels = 3 with radius 0.05 and beta 4, and 4 graph neighbours at weight 1; renderlive: after the
 //   last frame KinFu::renderLive, and what a caller needs to repeat it appended to out.bin)
 // in.bin : intrinsics fx fy cx cy f32[4], then per frame depth u16[rows*cols] (mm).
@@ -26,7 +27,7 @@ using namespace kfusion;
 
 int main(int argc, char** argv)
 {
-    if (argc != 8 && argc != 9) { std::fprintf(stderr, "usage: %s cols rows frames dims size in.bin out.bin [warped|host|nosolver|depth|assoc|plane|rigid|hier|trace, '-' separated]\n", argv[0]); return 2; }
+    if (argc != 8 && argc != 9) { std::fprintf(stderr, "usage: %s cols rows frames dims size in.bin out.bin [warped|host|nosolver|depth|assoc|plane|rigid|pcg|hier|trace, '-' separated]\n", argv[0]); return 2; }
     const int cols = std::atoi(argv[1]), rows = std::atoi(argv[2]), frames = std::atoi(argv[3]), dims = std::atoi(argv[4]);
     const float size = (float)std::atof(argv[5]);
     FILE* in = std::fopen(argv[6], "rb");
@@ -51,6 +52,7 @@ int main(int argc, char** argv)
         p.warp_solve_rotations = true; p.warp_rot_lambda = 1e-3f;
         p.warp_reg_neighbours = 4; p.warp_reg_lambda = 1.f;              // rotations that few points determine follow their neighbours
     }
+    p.warp_precondition = mode.find("pcg") != std::string::npos;
     if (mode.find("hier") != std::string::npos) {
         p.warp_reg_neighbours = 4; p.warp_reg_lambda = 1.f;
         p.warp_reg_levels = 3; p.warp_reg_radius = 0.05f; p.warp_reg_beta = 4.f;

@@ -10,6 +10,8 @@
 //       + setNodeRotations, on the unwarped points and normals                 -> dfusion_warp_solve_rigid
 // A last word `hier` (after the mode's arguments, or after the mode alone) puts the hierarchy under the regularisation term:
 //       + setRegularisationHierarchy(2, 0.5, 2)
+// and a last word `pcg` (behind `hier` where both are given) preconditions the `rigid` solve with the node blocks:
+//       + setPreconditioner(1)
 // The inputs come from 32-bit linear congruential generators and exact float arithmetic (the normals of `plane` and `rigid` from a second
 // one, after everything else: components in [-1, 1), not unit length), so that tests/solver_cases.py can make the same problem for the
 // Python mirror and the restatements, and the tests compare the bits.
@@ -34,9 +36,11 @@ int main(int argc, char** argv)
     const char* const mode = argc > 1 ? argv[1] : "";
     const bool reg = !std::strcmp(mode, "reg"), robust = !std::strcmp(mode, "robust"), plane = !std::strcmp(mode, "plane"), rigid = !std::strcmp(mode, "rigid");
     if (!reg && !robust && !plane && !rigid) {
-        std::fprintf(stderr, "usage: warp_solve reg [neighbours lambda] [hier]\n       warp_solve robust|plane|rigid [neighbours lambda rounds tukey_c huber_delta] [hier]\n");
+        std::fprintf(stderr, "usage: warp_solve reg [neighbours lambda] [hier]\n       warp_solve robust|plane|rigid [neighbours lambda rounds tukey_c huber_delta] [hier] [pcg]\n");
         return 2;
     }
+    const bool pcg = argc > 2 && !std::strcmp(argv[argc - 1], "pcg");
+    if (pcg) --argc;
     const bool hier = argc > 2 && !std::strcmp(argv[argc - 1], "hier");
     if (hier) --argc;
     const bool given = argc > (reg ? 3 : 6);                                // all of the mode's arguments, or the defaults
@@ -73,6 +77,7 @@ int main(int argc, char** argv)
     if (!reg) wf.setRobust(rounds, tukey_c, huber_delta);
     if (with_normals) wf.setPointToPlane(true);
     if (rigid) wf.setNodeRotations(true, 0.01f);
+    if (pcg) wf.setPreconditioner(1);
     if (!reg) wf.setTrackEnergy(true);
     wf.energy_data(src, normals, dst, normals);
     const std::vector<kfusion::deformation_node>& out = *wf.getNodes();

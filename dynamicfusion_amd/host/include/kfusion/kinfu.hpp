@@ -64,6 +64,9 @@ namespace kfusion
         bool warp_solve_rotations = false;   // device-resident dynamicfusion(): the node ROTATIONS are unknowns of the warp solve too
         float warp_rot_lambda = 0.f;         // (WarpField::setNodeRotations, with this damping of the rotations); the solve then gets copies of
                                              // the canonical points and normals from before the first warp; default off = the launches of before
+        bool warp_precondition = false;      // that solve's conjugate gradients preconditioned with the 6x6 node blocks
+                                             // (WarpField::setPreconditioner(1)): several times fewer steps to the round's solution, one launch
+                                             // more per round; default off = the plain recurrence
         bool warp_projective_association = false;   // device-resident dynamicfusion(): pair every warped point with the live sample at the
                                              // pixel it projects to (cuda::associateProjective) instead of by pixel index; default off =
                                              // the reference's pairing

@@ -109,6 +109,11 @@ namespace kfusion
         /// setSolverDamping damps the translations.  The canonical points (and normals) must then be the UNWARPED ones: the solve warps
         /// them itself.  With setPointToPlane and normals the residual is taken along the warped normal.  Off by default.
         void setNodeRotations(bool on, float lambda_rot = 0.f) { node_rotations_ = on; rot_lambda_ = lambda_rot; }
+        /// The preconditioner of that solve's conjugate gradients (dfusion_warp_set_preconditioner): 0 none (the default), 1 the 6x6
+        /// diagonal block of every node's rotation and translation, rebuilt and factored every round, which the badly scaled system with
+        /// rotations needs several times fewer steps with.  The setting stays with the field; the translation-only solves do not read
+        /// it.  Any other value raises an error and changes nothing.
+        void setPreconditioner(int mode);
         /// E_reg before / after the last regularised energy_data (with setTrackEnergy; 0 while the term is off)
         float lastRegEnergyBefore() const { return last_energy_[2]; }
         float lastRegEnergyAfter() const { return last_energy_[3]; }
@@ -168,6 +173,7 @@ namespace kfusion
         float tukey_c_ = 0.f, huber_delta_ = 0.f;
         bool point_to_plane_ = false;
         bool node_rotations_ = false; float rot_lambda_ = 0.f;
+        int preconditioner_ = 0;                               // what the handle was last given (setPreconditioner)
         float last_energy_[4] = {0.f, 0.f, 0.f, 0.f};
         bool track_energy_ = false;
     };

@@ -592,6 +592,13 @@ void WarpField::setRegularisationHierarchy(int levels, float radius, float beta)
     hier_levels_ = levels; hier_radius_ = radius; hier_beta_ = beta;
 }
 
+void WarpField::setPreconditioner(int mode)
+{
+    if (mode == preconditioner_) return;
+    KF_DF(dfusion_warp_set_preconditioner(handle_, mode));
+    preconditioner_ = mode;
+}
+
 int WarpField::extend(const std::vector<Vec3f>& points, float radius, float sigma)
 {
     static_assert(sizeof(Vec3f) == 12, "Vec3f must be 3 packed floats");
@@ -1329,6 +1336,7 @@ void KinFu::dynamicfusion(cuda::Depth& depth, cuda::Cloud live_frame, cuda::Norm
             warp_->setRobust(params_.warp_robust_rounds, params_.warp_tukey_c, params_.warp_huber_delta);
             warp_->setPointToPlane(params_.warp_point_to_plane);
             warp_->setNodeRotations(rotations, params_.warp_rot_lambda);
+            warp_->setPreconditioner(params_.warp_precondition ? 1 : 0);
             if (rotations) {                                                 // (the association above still paired the WARPED points)
                 if (params_.warp_point_to_plane) warp_->energy_data(df_unwarped_points3_, df_live3_, df_unwarped_normals3_, (int)n);
                 else warp_->energy_data(df_unwarped_points3_, df_live3_, (int)n);

@@ -257,3 +257,15 @@ class WarpField:
         capi.check(capi.lib().dfusion_warp_graph_levels(self.handle, int(kg), _ptr(top), _ptr(sizes), _ptr(effective), _stream()),
                    "dfusion_warp_graph_levels")
         return top, sizes, effective
+
+    def set_preconditioner(self, mode):
+        """The preconditioner of solve_rigid's conjugate gradients (include/dfusion.h dfusion_warp_set_preconditioner): 0 none (the
+        default), 1 the 6x6 diagonal block of every node (its rotation and translation together), rebuilt and factored every round.  The
+        setting stays on the field through extend, set_nodes and set_transforms; solve, solve_robust and solve_plane do not read it."""
+        capi.check(capi.lib().dfusion_warp_set_preconditioner(self.handle, int(mode)), "dfusion_warp_set_preconditioner")
+
+    @property
+    def preconditioner(self):
+        mode = C.c_int(-1)
+        capi.check(capi.lib().dfusion_warp_preconditioner(self.handle, C.byref(mode)), "dfusion_warp_preconditioner")
+        return mode.value

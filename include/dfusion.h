@@ -554,6 +554,18 @@ int dfusion_warp_set_graph_hierarchy(DfWarpField *wf, int levels, float radius, 
  * pointer may be NULL:  top_dev[M] int32 top(i);  sizes_dev[9] int32 |S_0| .. |S_8|, 0 past `levels`;  effective_dev[1] int32 L'
  * (0: the graph is the flat one).  With the hierarchy off: top = 0, sizes = {M, 0, ...}, L' = 0.                                       */
 int dfusion_warp_graph_levels(DfWarpField *wf, int kg, int *top_dev, int *sizes_dev, int *effective_dev, dfStream stream);
+/* The preconditioner of dfusion_warp_solve_rigid's conjugate gradients -- additions to ABI 7.  A setting of the handle, 0 on every new
+ * handle, kept through dfusion_warp_extend, dfusion_warp_set_nodes and dfusion_warp_set_transforms; no other entry point reads it.
+ *   mode 0  none: the launches and the bits of before.
+ *   mode 1  6x6 node blocks (block Jacobi).  Every round the diagonal block of each node's six unknowns (omega_n, tau_n) of the round's
+ *           normal matrix -- the data term with the round's Tukey weights, the graph term with its Huber-scaled edge weights, lambda_rot
+ *           and lambda -- is summed in a fixed order and factored by Cholesky in f32 (one launch a round); the recurrence is
+ *           preconditioned with them, z = B^-1 r by two triangular substitutions per node inside the step kernel (no launch more per
+ *           step), and stops once r.z <= 1e-10 (r.z)_0.  A node whose block has a pivot that is not > 0 or not finite (no entries and no
+ *           edges under zero damping, a NaN) takes the identity.  Restated in tests/solver_precond_ref.py; DESIGN.md 21.
+ * DF_E_INVALID: a NULL handle (or mode_out), a mode other than 0 or 1 (the handle stays as it was).                                 */
+int dfusion_warp_set_preconditioner(DfWarpField *wf, int mode);
+int dfusion_warp_preconditioner(const DfWarpField *wf, int *mode_out);
 
 /* The north-star kernel: per-voxel DQB (WarpField::DQB, warp_field.cpp:203-217) composed with
  * TsdfIntegrator (tsdf_volume.cu:77-104): x_c = vol2world*voxel, x_w = DQB(x_c).transform(x_c),
