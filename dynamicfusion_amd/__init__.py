@@ -5,9 +5,11 @@ Warp-field-deformed TSDF integration, surface ray-casting and the per-voxel dual
 host-side mirrors of kfusion::cuda::TsdfVolume / kfusion::WarpField, the colour volume (ColorVolume), the depth front-end + ProjectiveICP (frontend) and the Z-slab
 collectives (sharded).
 """
-from . import build, capi, frontend, mesh_io, sharded, synth  # noqa: F401
+from . import build, capi, frontend, mesh_io, mesh_ops, sharded, synth  # noqa: F401
 from .tsdf_volume import Intr, TsdfVolume, compute_dists, download_u16, upload_u16  # noqa: F401
 from .warp_field import WarpField  # noqa: F401
 from .color_volume import ColorVolume  # noqa: F401
+from .mesh_ops import mesh_components, remove_small_components  # noqa: F401
 
-__all__ = ["build", "capi", "frontend", "mesh_io", "sharded", "synth", "Intr", "TsdfVolume", "WarpField", "ColorVolume", "compute_dists", "upload_u16", "download_u16"]
+__all__ = ["build", "capi", "frontend", "mesh_io", "mesh_ops", "sharded", "synth", "Intr", "TsdfVolume", "WarpField", "ColorVolume", "compute_dists", "upload_u16", "download_u16", "mesh_components",
+           "remove_small_components"]

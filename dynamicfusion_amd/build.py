@@ -15,9 +15,9 @@ LIB_PATH = os.path.join(PKG_DIR, "libdfusion_hip.so")
 
 SOURCES = ["dfusion_volume.hip", "dfusion_warp.hip", "dfusion_warp_nodes.hip", "dfusion_warp_points.hip", "dfusion_warp_index.hip",
            "dfusion_raycast.hip", "dfusion_frontend.hip", "dfusion_solver.hip", "dfusion_selftest.hip", "dfusion_warp_extend.hip", "dfusion_mesh.hip", "dfusion_associate.hip", "dfusion_color.hip", "dfusion_render.hip",
-           "dfusion_warp_graph.hip"]
+           "dfusion_warp_graph.hip", "dfusion_mesh_components.hip"]
 HEADERS = ["dfusion_device.h", "dfusion_internal.h", "dfusion_nanoflann.h", "dfusion_pyramid.h", "dfusion_warp_topk.h", "dfusion_warp_sweep.h",
-           "dfusion_warp_blocks.h", "dfusion_warp_pipe.h", "dfusion_plan_halves.h", "dfusion_warp_decide.h", os.path.join(REPO_DIR, "include", "dfusion.h")]
+           "dfusion_warp_blocks.h", "dfusion_warp_pipe.h", "dfusion_plan_halves.h", "dfusion_warp_decide.h", "dfusion_mesh_cc.h", os.path.join(REPO_DIR, "include", "dfusion.h")]
 
 # -ffp-contract=off: fused multiply-adds only where the reference writes __fmaf_rn (explicit fmaf);
 # that is what makes the kernels bit-comparable with the IEEE CPU oracle.
@@ -63,6 +63,7 @@ def kernel_source_sha(kernel):
          else "dfusion_raycast.hip" if k.startswith(("df_raycast", "df_extract"))
          else "dfusion_solver.hip" if k.startswith("df_sv")
          else "dfusion_warp_graph.hip" if k.startswith("df_hg")
+         else "dfusion_mesh_components.hip" if k.startswith("df_mcc_")
          else "dfusion_mesh.hip" if k.startswith("df_mesh")
          else "dfusion_associate.hip" if k.startswith("df_assoc")
          else "dfusion_color.hip" if k.startswith("df_color")

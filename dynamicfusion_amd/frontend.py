@@ -237,7 +237,20 @@ def renderLiveModel(volume, warp_field, camera_pose, intr, cols, rows, color_vol
     nearest nodes, default warp_field.k) and rendered into the camera at `camera_pose` (inverted in f64), with the canonical vertices
     as the attribute.  -> (points, normals, canonical points, colours) images as renderMesh gives them; the normals stay in the frame
     the warp leaves them in."""
-    vertices, triangles, normals = volume.fetchMesh(with_normals=True)
+    return _render_live_mesh(volume.fetchMesh(with_normals=True), warp_field, camera_pose, intr, cols, rows, color_volume, k)
+
+
+def renderLiveModelFiltered(volume, warp_field, camera_pose, intr, cols, rows, color_volume=None, k=None, min_component_triangles=0,
+                            keep_largest=False):
+    """renderLiveModel without the floaters: the mesh's connected pieces of fewer than min_component_triangles triangles (with
+    keep_largest: all but the largest) are dropped first -- fetchMesh's arguments -- so the colours are fetched and the warp runs
+    for the kept vertices only.  At the defaults: renderLiveModel's calls exactly."""
+    mesh = volume.fetchMesh(with_normals=True, min_component_triangles=min_component_triangles, keep_largest=keep_largest)
+    return _render_live_mesh(mesh, warp_field, camera_pose, intr, cols, rows, color_volume, k)
+
+
+def _render_live_mesh(mesh, warp_field, camera_pose, intr, cols, rows, color_volume, k):
+    vertices, triangles, normals = mesh
     colors = color_volume.fetchColors(vertices) if color_volume is not None else None
     nv = int(vertices.shape[0])
     p3, n3 = vertices[:, :3].contiguous(), normals[:, :3].contiguous()

@@ -12,6 +12,8 @@
 //   headless_frame mesh <out.ply> <the arguments above>: the same run, and the volume's surface after the frames (before any
 //          surface_fusion) as a triangle mesh, TsdfVolume::fetchMesh, in a binary little-endian PLY -- byte for byte the file
 //          dynamicfusion_amd.mesh_io.write_ply makes of the Python mirror's fetchMesh.
+//   headless_frame mesh <out.ply> <min_triangles> <the arguments above>: that mesh without its connected pieces of fewer than
+//          min_triangles triangles (fetchMesh's overload; the mirror's fetchMesh(min_component_triangles=...)).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -113,10 +115,10 @@ static int bench_mode(int argc, char** argv)
     return 0;
 }
 
-static int write_mesh_ply(const cuda::TsdfVolume& volume, const char* path)
+static int write_mesh_ply(const cuda::TsdfVolume& volume, const char* path, unsigned long long min_triangles)
 {
     cuda::DeviceArray<Point> vertices; cuda::DeviceArray<int> triangles;
-    volume.fetchMesh(vertices, triangles);
+    volume.fetchMesh(vertices, triangles, min_triangles);
     std::vector<Point> v; std::vector<int> t;
     vertices.download(v); triangles.download(t);
     FILE* f = std::fopen(path, "wb");
@@ -135,7 +137,11 @@ int main(int argc, char** argv)
 {
     if (argc >= 2 && !std::strcmp(argv[1], "bench")) return bench_mode(argc, argv);
     const char* mesh_path = nullptr;
+    unsigned long long mesh_min_triangles = 0;
     if (argc >= 3 && !std::strcmp(argv[1], "mesh")) { mesh_path = argv[2]; argv[2] = argv[0]; argv += 2; argc -= 2; }
+    if (mesh_path && (argc == 12 || (argc == 11 && std::strcmp(argv[10], "surface_fusion")))) {        // one argument more than the run takes
+        mesh_min_triangles = std::strtoull(argv[1], nullptr, 10); argv[1] = argv[0]; argv += 1; argc -= 1;
+    }
     if (argc != 10 && argc != 11) { std::fprintf(stderr, "usage: %s dims size cols rows frames nodes k in.bin out.bin\n", argv[0]); return 2; }
     const int dims = std::atoi(argv[1]); const float size = (float)std::atof(argv[2]);
     const int cols = std::atoi(argv[3]), rows = std::atoi(argv[4]), frames = std::atoi(argv[5]), M = std::atoi(argv[6]), k = std::atoi(argv[7]);
@@ -211,7 +217,7 @@ int main(int argc, char** argv)
         std::fwrite(volume.get_cloud_host().data(), 16, cnt, out);
         std::fwrite(volume.get_normal_host().data(), 16, cnt, out);
     }
-    if (mesh_path && write_mesh_ply(volume, mesh_path)) return 2;
+    if (mesh_path && write_mesh_ply(volume, mesh_path, mesh_min_triangles)) return 2;
     if (argc == 11 && M > 0) {
         const Affine3f camera_pose = cam[frames - 1];
         const Affine3f inverse_pose = camera_pose.inv();                             // kinfu.cpp:357

@@ -1,0 +1,27 @@
+// kfusion/cuda/mesh_ops.hpp -- kfusion::cuda::meshComponents / removeSmallComponents: the connected components of an indexed triangle
+// mesh and the mesh without its small pieces (no reference counterpart).  Forward to dfusion_mesh_components / dfusion_mesh_filter /
+// dfusion_gather_rows of include/dfusion.h, where the rule is stated; no kernels of their own.  Same calls as the Python mirror
+// (dynamicfusion_amd.mesh_ops).
+#pragma once
+#include <kfusion/types.hpp>
+
+namespace kfusion { namespace cuda {
+
+/// triangles: 3 vertex indices each (TsdfVolume::fetchMesh's) over n_vertices vertices.  vertex_label[v] = the smallest vertex index of
+/// v's component, triangle_count[r] = the valid triangles of the component labelled r (0 where r is no label); counts (optional, 4
+/// values): components with a triangle, unused vertices, invalid triangles, the largest component's triangles.  Enqueued only: nothing
+/// synchronises.
+void meshComponents(const DeviceArray<int>& triangles, size_t n_vertices, DeviceArray<int>& vertex_label, DeviceArray<int>& triangle_count,
+                    DeviceArray<unsigned long long>* counts = nullptr);
+
+/// The mesh without the components of fewer than min_triangles triangles and -- with keep_largest -- without all but the one with the
+/// most; invalid triangles and the vertices no kept triangle uses go too, everything else keeps its order.  vertex_src[i] = the old
+/// index of new vertex i.  Every array is sized exactly (a count-only filter call whose counts are read back, then one of that size).
+void removeSmallComponents(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, unsigned long long min_triangles,
+                           bool keep_largest, DeviceArray<Point>& vertices_out, DeviceArray<int>& triangles_out, DeviceArray<int>& vertex_src);
+
+/// out[i] = src[index[i]] for per-vertex rows of 16 bytes (normals, points) or 4 bytes (colours): the attributes of a filtered mesh.
+void gatherRows(const DeviceArray<Point>& src, const DeviceArray<int>& index, DeviceArray<Point>& out);
+void gatherRows(const DeviceArray<RGB>& src, const DeviceArray<int>& index, DeviceArray<RGB>& out);
+
+} }

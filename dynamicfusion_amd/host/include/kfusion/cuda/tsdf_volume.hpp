@@ -99,6 +99,9 @@ public:
     // (no reference counterpart) the same surface as a triangle mesh, include/dfusion.h dfusion_extract_mesh: vertices in the rule's order,
     // triangles 3 vertex indices each; both arrays are sized exactly (a count-only call, then one of that size)
     void fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& triangles) const;
+    // that mesh without its connected pieces of fewer than min_component_triangles triangles and -- with keep_largest -- without all but
+    // the largest (kfusion/cuda/mesh_ops.hpp removeSmallComponents); 0 and false: the call above, nothing else
+    void fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& triangles, unsigned long long min_component_triangles, bool keep_largest = false) const;
     void compute_points();
     void compute_normals();
 #ifdef KFUSION_USE_OPENCV

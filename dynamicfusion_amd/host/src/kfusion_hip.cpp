@@ -11,6 +11,7 @@
 #include <kfusion/cuda/color_volume.hpp>
 #include <kfusion/cuda/imgproc.hpp>
 #include <kfusion/cuda/render_mesh.hpp>
+#include <kfusion/cuda/mesh_ops.hpp>
 #include <kfusion/warp_field.hpp>
 #include <kfusion/cuda/projective_icp.hpp>
 #include <kfusion/kinfu.hpp>
@@ -314,6 +315,60 @@ void TsdfVolume::fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& trian
     if (!n[0] && !n[1]) return;
     KF_DF(dfusion_extract_mesh(c_volume(*this), c_slab(*this).ptr(), aff, n[0] ? (float*)vertices.ptr() : nullptr, n[0],
                                n[1] ? (unsigned int*)triangles.ptr() : nullptr, n[1], counts.ptr(), nullptr));
+}
+
+void TsdfVolume::fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& triangles, unsigned long long min_component_triangles, bool keep_largest) const
+{
+    if (!min_component_triangles && !keep_largest) { fetchMesh(vertices, triangles); return; }
+    DeviceArray<Point> all_vertices; DeviceArray<int> all_triangles, vertex_src;
+    fetchMesh(all_vertices, all_triangles);
+    removeSmallComponents(all_vertices, all_triangles, min_component_triangles, keep_largest, vertices, triangles, vertex_src);
+}
+
+// ------------------------------------------------------------------------------------------ mesh components (include/dfusion.h dfusion_mesh_*)
+void kfusion::cuda::meshComponents(const DeviceArray<int>& triangles, size_t n_vertices, DeviceArray<int>& vertex_label, DeviceArray<int>& triangle_count,
+                                   DeviceArray<unsigned long long>* counts)
+{
+    const size_t nt = triangles.size() / 3;
+    vertex_label.create(n_vertices);
+    triangle_count.create(n_vertices);
+    if (counts) counts->create(4);
+    KF_DF(dfusion_mesh_components(nt ? (const unsigned int*)triangles.ptr() : nullptr, nt, n_vertices,
+                                  n_vertices ? (unsigned int*)vertex_label.ptr() : nullptr, n_vertices ? (unsigned int*)triangle_count.ptr() : nullptr,
+                                  counts ? counts->ptr() : nullptr, nullptr));
+}
+
+template <typename T>
+static void gather_rows(const DeviceArray<T>& src, const DeviceArray<int>& index, DeviceArray<T>& out)
+{
+    static_assert(sizeof(T) == 4 || sizeof(T) == 12 || sizeof(T) == 16, "dfusion_gather_rows: rows of 4, 12 or 16 bytes");
+    out.create(index.size());
+    if (!index.size()) return;
+    KF_DF(dfusion_gather_rows(src.ptr(), (unsigned int)sizeof(T), (const unsigned int*)index.ptr(), index.size(), out.ptr(), nullptr));
+}
+void kfusion::cuda::gatherRows(const DeviceArray<Point>& src, const DeviceArray<int>& index, DeviceArray<Point>& out) { gather_rows(src, index, out); }
+void kfusion::cuda::gatherRows(const DeviceArray<RGB>& src, const DeviceArray<int>& index, DeviceArray<RGB>& out) { gather_rows(src, index, out); }
+
+void kfusion::cuda::removeSmallComponents(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, unsigned long long min_triangles,
+                                          bool keep_largest, DeviceArray<Point>& vertices_out, DeviceArray<int>& triangles_out,
+                                          DeviceArray<int>& vertex_src)
+{
+    const size_t nv = vertices.size(), nt = triangles.size() / 3;
+    DeviceArray<int> label, count;
+    meshComponents(triangles, nv, label, count);
+    DeviceArray<unsigned long long> counts(2);
+    auto filter = [&](unsigned int* tri_out, unsigned long long tcap, unsigned int* src, unsigned long long vcap) {
+        KF_DF(dfusion_mesh_filter(nt ? (const unsigned int*)triangles.ptr() : nullptr, nt, nv, nv ? (const unsigned int*)label.ptr() : nullptr,
+                                  nv ? (const unsigned int*)count.ptr() : nullptr, min_triangles, keep_largest ? 1 : 0, tri_out, tcap, src, vcap,
+                                  nullptr, counts.ptr(), nullptr));
+    };
+    filter(nullptr, 0, nullptr, 0);
+    unsigned long long n[2] = {0, 0};
+    counts.download(n);
+    triangles_out.create((size_t)n[1] * 3);
+    vertex_src.create((size_t)n[0]);
+    if (n[0] || n[1]) filter(n[1] ? (unsigned int*)triangles_out.ptr() : nullptr, n[1], n[0] ? (unsigned int*)vertex_src.ptr() : nullptr, n[0]);
+    gatherRows(vertices, vertex_src, vertices_out);
 }
 
 // ------------------------------------------------------------------------------------------ ColorVolume (include/dfusion.h dfusion_color_*)

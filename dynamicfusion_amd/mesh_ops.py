@@ -1,0 +1,78 @@
+"""Operations on an indexed triangle mesh (fetchMesh's, or any) over the C-ABI: its connected components and the mesh without its small
+pieces (include/dfusion.h dfusion_mesh_components / dfusion_mesh_filter / dfusion_gather_rows, where the rule is stated).  Device
+tensors in, device tensors out; all compute is in libdfusion_hip.so."""
+import torch
+
+from . import capi
+from .tsdf_volume import _flat, _stream
+
+
+def _triangles(triangles):
+    if triangles.dtype != torch.int32 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise ValueError("triangles %s %s, expected int32 [T, 3]" % (triangles.dtype, tuple(triangles.shape)))
+    if not triangles.is_cuda:
+        raise ValueError("triangles are not on a CUDA device")
+    nt = int(triangles.shape[0])
+    return (_flat(triangles) if nt else None), nt
+
+
+def mesh_components(triangles, n_vertices, return_counts=False):
+    """triangles int32 [T, 3] (uint32 bits) over n_vertices vertices -> (vertex_label int32 [V]: the smallest vertex index of every
+    vertex's component, triangle_count int32 [V]: the valid triangles of the component labelled r, 0 where r is no label), both uint32
+    bits; with return_counts also counts int64 [4]: components with a triangle, unused vertices, invalid triangles, the largest
+    component's triangles.  Device tensors; nothing synchronises."""
+    tp, nt = _triangles(triangles)
+    nv = int(n_vertices)
+    dev = triangles.device
+    label = torch.empty(nv, dtype=torch.int32, device=dev)
+    count = torch.empty(nv, dtype=torch.int32, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev) if return_counts else None
+    capi.check(capi.lib().dfusion_mesh_components(tp, nt, nv, _flat(label) if nv else None, _flat(count) if nv else None,
+                                                  _flat(counts) if return_counts else None, _stream()), "dfusion_mesh_components")
+    return (label, count, counts) if return_counts else (label, count)
+
+
+def gather_rows(src, index, n=None):
+    """src[index[:n]] for a contiguous tensor whose rows are 4, 12 or 16 bytes (index: int32, uint32 bits) -> a new tensor [n, ...]."""
+    n = int(index.shape[0]) if n is None else int(n)
+    if not src.is_contiguous():
+        raise ValueError("per-vertex array must be contiguous (shape %s, strides %s)" % (tuple(src.shape), src.stride()))
+    row = src.element_size()
+    for d in src.shape[1:]:
+        row *= int(d)
+    if src.dim() < 1 or row not in (4, 12, 16):
+        raise ValueError("per-vertex rows of %d bytes (%s %s), expected 4, 12 or 16" % (row, src.dtype, tuple(src.shape)))
+    out = torch.empty((n,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    if n:
+        capi.check(capi.lib().dfusion_gather_rows(_flat(src), row, _flat(index), n, _flat(out), _stream()), "dfusion_gather_rows")
+    return out
+
+
+def remove_small_components(vertices, triangles, min_triangles=0, keep_largest=False, attributes=()):
+    """The mesh without the components of fewer than min_triangles triangles and -- with keep_largest -- without all but the one with
+    the most (a tie: the smaller label); invalid triangles and the vertices no kept triangle uses go too, everything else keeps its
+    order.  vertices [V, ...] and every tensor of `attributes` (per-vertex rows of 4, 12 or 16 bytes) are gathered with vertex_src.
+    -> (vertices, triangles, attributes (a tuple), vertex_src int32 [n]: the old index of every new vertex).  One count-only filter
+    call, then one of exactly that size (the counts are read back, as fetchMesh reads its own)."""
+    tp, nt = _triangles(triangles)
+    nv = int(vertices.shape[0])
+    for a in attributes:
+        if int(a.shape[0]) != nv:
+            raise ValueError("attribute of %d rows for %d vertices" % (int(a.shape[0]), nv))
+    dev = triangles.device
+    label, count = mesh_components(triangles, nv)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    L = capi.lib()
+
+    def run(tri_out, n_tri, src, n_src):
+        capi.check(L.dfusion_mesh_filter(tp, nt, nv, _flat(label) if nv else None, _flat(count) if nv else None, int(min_triangles),
+                                         1 if keep_largest else 0, _flat(tri_out) if n_tri else None, n_tri,
+                                         _flat(src) if n_src else None, n_src, None, _flat(counts), _stream()), "dfusion_mesh_filter")
+
+    run(None, 0, None, 0)
+    kv, kt = (int(c) for c in counts.tolist())
+    tri_out = torch.empty((kt, 3), dtype=torch.int32, device=dev)
+    src = torch.empty(kv, dtype=torch.int32, device=dev)
+    if kv or kt:
+        run(tri_out, kt, src, kv)
+    return gather_rows(vertices, src), tri_out, tuple(gather_rows(a, src) for a in attributes), src

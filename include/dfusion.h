@@ -297,6 +297,53 @@ int dfusion_extract_mesh(DfVolume v, const DfSlab *slab, const float aff[12], fl
                          unsigned long long vertex_capacity, unsigned int *triangles_dev,
                          unsigned long long triangle_capacity, unsigned long long *counts_dev, dfStream stream);
 
+/* Connected components of an indexed triangle mesh, and the mesh without its small pieces (no reference counterpart; additive, ABI 7).
+ * DESIGN.md section 22 has the kernels; tests/mesh_components_ref.py restates the rule in numpy and every output equals it.
+ * Inputs: T triangles of three uint32 indices and a vertex count V.  Positions play no part: coincident vertices do not connect, only
+ * shared indices do.
+ *   - triangle t is VALID iff all three indices are < V (tested before anything is indexed); an invalid triangle connects nothing and
+ *     is never kept;
+ *   - the graph has the vertices 0 .. V-1 and an edge between any two different indices of a valid triangle ((a, a, b) is valid and
+ *     connects a and b; (a, a, a) connects nothing and is a triangle of a's component);
+ *   - vertex_label[v] = the smallest vertex index in v's component; a vertex used by no valid triangle labels itself;
+ *   - triangle_count[r] = the number of valid triangles whose vertices carry label r, 0 for every r that is not a label (all V
+ *     entries are written);
+ *   - counts[4] (u64, WRITTEN, not incremented): [0] components holding at least one triangle, [1] vertices used by no valid triangle,
+ *     [2] invalid triangles, [3] the triangle count of the largest component.
+ * dfusion_mesh_filter, given the mesh and those two arrays: a triangle is KEPT iff it is valid, triangle_count[label] >= min_triangles
+ * (inclusive) and -- with keep_largest != 0 -- its label is that of the component with the most triangles, an exact tie going to the
+ * smaller label.  A vertex is kept iff a kept triangle uses it.  Kept triangles and kept vertices keep their relative order (stable
+ * compaction); triangles_out_dev holds the kept triangles with the NEW indices; vertex_src_dev[i] = the old index of new vertex i,
+ * the gather list for any per-vertex attribute (dfusion_gather_rows); vertex_map_dev[v] (nullable, V entries) = the new index of
+ * old vertex v, or 0xffffffff.  counts_dev[0], [1] are WRITTEN: kept vertices and kept triangles, always the full numbers.  Nothing is
+ * written past a capacity; if a count exceeds its capacity the contents of the output arrays are unspecified (dfusion_extract_mesh's
+ * contract).  Both capacities 0: counts only (vertex_map_dev is not written either).
+ * T == 0 or V == 0 is valid input, to which the rule applies as it stands: no component, nothing kept, every vertex unused (T == 0),
+ * every triangle invalid (V == 0).  Arrays of length 0 may be NULL.
+ * DF_E_INVALID: V or T > 2^32 - 1 (indices and triangle counts are 32-bit), NULL where not nullable, a NULL output array with a non-zero
+ * capacity.  Without a device DF_E_NO_DEVICE.  No device-to-host copy and no synchronisation; every launch covers T and V with 64-bit
+ * indices.  The union is a lock-free union-find in which a root is only ever linked under a smaller index: vertex_label_dev itself is
+ * the forest, so a label is final only when the call's work on the stream is done.  Workspace, from the per-(device, stream) scratch of
+ * dfusion_extract_mesh (dfusion_release_scratch): components V bytes (+ 4 V when triangle_count_dev is NULL and counts_dev is not;
+ * none when both are NULL), filter 4 (T + 1) + 4 (V + 1) + 16 bytes and hipcub's scan storage.  Integer atomics only: no output depends
+ * on scheduling.                                                                                                                      */
+int dfusion_mesh_components(const unsigned int *triangles_dev, unsigned long long n_triangles,
+                            unsigned long long n_vertices, unsigned int *vertex_label_dev,
+                            unsigned int *triangle_count_dev /* nullable */,
+                            unsigned long long *counts_dev /* [4], nullable */, dfStream stream);
+int dfusion_mesh_filter(const unsigned int *triangles_dev, unsigned long long n_triangles,
+                        unsigned long long n_vertices, const unsigned int *vertex_label_dev,
+                        const unsigned int *triangle_count_dev, unsigned long long min_triangles,
+                        int keep_largest, unsigned int *triangles_out_dev,
+                        unsigned long long triangle_capacity, unsigned int *vertex_src_dev,
+                        unsigned long long vertex_capacity, unsigned int *vertex_map_dev /* nullable */,
+                        unsigned long long *counts_dev /* [2] */, dfStream stream);
+/* dst row i = src row index_dev[i] for i < n, rows of row_bytes = 4, 12 or 16 bytes (anything else: DF_E_INVALID), both arrays 4-byte
+ * aligned and not overlapping; the indices are not checked against the source's length.  n == 0: nothing (the arrays may be NULL).  */
+int dfusion_gather_rows(const void *src_dev, unsigned int row_bytes /* 4, 12 or 16 */,
+                        const unsigned int *index_dev, unsigned long long n, void *dst_dev,
+                        dfStream stream);
+
 /* ---- colour volume (no reference counterpart: KinFu::operator() drops its colour image; additive, ABI 7) ----------------------
  * A colour volume belongs to a TSDF volume: the same dims, linear layout (x + y X + z X Y) and stored planes (DfSlab), 4 bytes a
  * voxel {c0, c1, c2, w}: three channels in the byte order of the input image (the kernels treat them alike) and a weight byte;
