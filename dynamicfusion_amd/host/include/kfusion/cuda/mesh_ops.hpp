@@ -1,6 +1,7 @@
 // kfusion/cuda/mesh_ops.hpp -- kfusion::cuda::meshComponents / removeSmallComponents: the connected components of an indexed triangle
 // mesh and the mesh without its small pieces (no reference counterpart).  Forward to dfusion_mesh_components / dfusion_mesh_filter /
-// dfusion_gather_rows of include/dfusion.h, where the rule is stated; no kernels of their own.  Same calls as the Python mirror
+// dfusion_gather_rows of include/dfusion.h, where the rule is stated; no kernels of their own.  simplifyMesh: the mesh simplified by
+// vertex clustering (dfusion_mesh_simplify).  Same calls as the Python mirror
 // (dynamicfusion_amd.mesh_ops).
 #pragma once
 #include <kfusion/types.hpp>
@@ -23,5 +24,14 @@ void removeSmallComponents(const DeviceArray<Point>& vertices, const DeviceArray
 /// out[i] = src[index[i]] for per-vertex rows of 16 bytes (normals, points) or 4 bytes (colours): the attributes of a filtered mesh.
 void gatherRows(const DeviceArray<Point>& src, const DeviceArray<int>& index, DeviceArray<Point>& out);
 void gatherRows(const DeviceArray<RGB>& src, const DeviceArray<int>& index, DeviceArray<RGB>& out);
+
+/// The mesh simplified by vertex clustering on a grid of cubic cells of size `cell` (> 0, finite): the vertices of one cell become one
+/// -- their integer-averaged mean, with DF_SIMPLIFY_KEEP_FIRST the lowest-index one as it is --, triangles with two corners in a cell
+/// collapse, and of the triangles over the same three cells one survives, or none where both orientations come equally often
+/// (DF_SIMPLIFY_KEEP_DUPLICATES keeps them all).  vertex_src[j] = the lowest old index of new vertex j's cluster; counts (optional): the
+/// call's 8 counts.  Every array is sized exactly (a count-only call whose counts are read back, then one of that size).
+void simplifyMesh(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, float cell, unsigned int flags,
+                  DeviceArray<Point>& out_vertices, DeviceArray<int>& out_triangles, DeviceArray<int>& vertex_src,
+                  DeviceArray<unsigned long long>* counts = nullptr);
 
 } }

@@ -102,6 +102,8 @@ public:
     // that mesh without its connected pieces of fewer than min_component_triangles triangles and -- with keep_largest -- without all but
     // the largest (kfusion/cuda/mesh_ops.hpp removeSmallComponents); 0 and false: the call above, nothing else
     void fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& triangles, unsigned long long min_component_triangles, bool keep_largest = false) const;
+    // and, after that filter, simplified by vertex clustering at simplify_cell (kfusion/cuda/mesh_ops.hpp simplifyMesh); 0: the call above
+    void fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& triangles, unsigned long long min_component_triangles, bool keep_largest, float simplify_cell) const;
     void compute_points();
     void compute_normals();
 #ifdef KFUSION_USE_OPENCV

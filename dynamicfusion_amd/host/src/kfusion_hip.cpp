@@ -325,6 +325,15 @@ void TsdfVolume::fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& trian
     removeSmallComponents(all_vertices, all_triangles, min_component_triangles, keep_largest, vertices, triangles, vertex_src);
 }
 
+void TsdfVolume::fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& triangles, unsigned long long min_component_triangles, bool keep_largest,
+                           float simplify_cell) const
+{
+    if (simplify_cell == 0.f) { fetchMesh(vertices, triangles, min_component_triangles, keep_largest); return; }
+    DeviceArray<Point> all_vertices; DeviceArray<int> all_triangles, vertex_src;
+    fetchMesh(all_vertices, all_triangles, min_component_triangles, keep_largest);
+    simplifyMesh(all_vertices, all_triangles, simplify_cell, 0u, vertices, triangles, vertex_src);
+}
+
 // ------------------------------------------------------------------------------------------ mesh components (include/dfusion.h dfusion_mesh_*)
 void kfusion::cuda::meshComponents(const DeviceArray<int>& triangles, size_t n_vertices, DeviceArray<int>& vertex_label, DeviceArray<int>& triangle_count,
                                    DeviceArray<unsigned long long>* counts)
@@ -369,6 +378,29 @@ void kfusion::cuda::removeSmallComponents(const DeviceArray<Point>& vertices, co
     vertex_src.create((size_t)n[0]);
     if (n[0] || n[1]) filter(n[1] ? (unsigned int*)triangles_out.ptr() : nullptr, n[1], n[0] ? (unsigned int*)vertex_src.ptr() : nullptr, n[0]);
     gatherRows(vertices, vertex_src, vertices_out);
+}
+
+void kfusion::cuda::simplifyMesh(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, float cell, unsigned int flags,
+                                 DeviceArray<Point>& out_vertices, DeviceArray<int>& out_triangles, DeviceArray<int>& vertex_src,
+                                 DeviceArray<unsigned long long>* counts_out)
+{
+    const size_t nv = vertices.size(), nt = triangles.size() / 3;
+    DeviceArray<unsigned long long> own;
+    DeviceArray<unsigned long long>& counts = counts_out ? *counts_out : own;
+    counts.create(8);
+    auto run = [&](float* v_out, unsigned int* src, unsigned long long vcap, unsigned int* tri_out, unsigned long long tcap) {
+        KF_DF(dfusion_mesh_simplify(nv ? (const float*)vertices.ptr() : nullptr, nv, nt ? (const unsigned int*)triangles.ptr() : nullptr, nt, cell, flags,
+                                    v_out, vcap, tri_out, tcap, src, nullptr, counts.ptr(), nullptr));
+    };
+    run(nullptr, nullptr, 0, nullptr, 0);
+    unsigned long long n[8];
+    counts.download(n);
+    out_vertices.create((size_t)n[0]);
+    vertex_src.create((size_t)n[0]);
+    out_triangles.create((size_t)n[1] * 3);
+    if (n[0] || n[1])
+        run(n[0] ? (float*)out_vertices.ptr() : nullptr, n[0] ? (unsigned int*)vertex_src.ptr() : nullptr, n[0],
+            n[1] ? (unsigned int*)out_triangles.ptr() : nullptr, n[1]);
 }
 
 // ------------------------------------------------------------------------------------------ ColorVolume (include/dfusion.h dfusion_color_*)

@@ -1,6 +1,6 @@
 """Operations on an indexed triangle mesh (fetchMesh's, or any) over the C-ABI: its connected components and the mesh without its small
-pieces (include/dfusion.h dfusion_mesh_components / dfusion_mesh_filter / dfusion_gather_rows, where the rule is stated).  Device
-tensors in, device tensors out; all compute is in libdfusion_hip.so."""
+pieces (include/dfusion.h dfusion_mesh_components / dfusion_mesh_filter / dfusion_gather_rows, where the rule is stated), and the mesh
+simplified by vertex clustering (dfusion_mesh_simplify).  Device tensors in, device tensors out; all compute is in libdfusion_hip.so."""
 import torch
 
 from . import capi
@@ -76,3 +76,42 @@ def remove_small_components(vertices, triangles, min_triangles=0, keep_largest=F
     if kv or kt:
         run(tri_out, kt, src, kv)
     return gather_rows(vertices, src), tri_out, tuple(gather_rows(a, src) for a in attributes), src
+
+
+KEEP_FIRST, KEEP_DUPLICATES = 1, 2                       # DF_SIMPLIFY_*
+
+
+def simplify_mesh(vertices, triangles, cell, keep_first=False, keep_duplicates=False, return_counts=False):
+    """The mesh simplified by vertex clustering on a grid of cubic cells of size `cell` (include/dfusion.h dfusion_mesh_simplify has the
+    rule): the vertices of one cell that a valid triangle uses become one vertex -- their integer-averaged mean, with keep_first the
+    lowest-index one of them as it is --, triangles with two corners in one cell collapse, and of the triangles over the same three
+    cells one survives, or none where both orientations come equally often (a fin); keep_duplicates keeps every non-collapsed one.
+    vertices float32 [V, 4], triangles int32 [T, 3] (uint32 bits) -> (vertices float32 [n, 4], triangles int32 [m, 3], vertex_src int32
+    [n]: the lowest old index of every new vertex's cluster, vertex_map int32 [V]: the new index of every old vertex or 0xffffffff);
+    with return_counts also counts int64 [8]: output vertices, output triangles, invalid, collapsed, fin and duplicate triangles,
+    clusters, unclusterable vertices.  One count-only call, then one of exactly that size (the counts are read back)."""
+    tp, nt = _triangles(triangles)
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 4 or not vertices.is_contiguous():
+        raise ValueError("vertices %s %s, expected contiguous float32 [V, 4]" % (vertices.dtype, tuple(vertices.shape)))
+    if vertices.device != triangles.device:
+        raise ValueError("vertices on %s, triangles on %s" % (vertices.device, triangles.device))
+    nv = int(vertices.shape[0])
+    dev = triangles.device
+    flags = (KEEP_FIRST if keep_first else 0) | (KEEP_DUPLICATES if keep_duplicates else 0)
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    L = capi.lib()
+
+    def run(out_v, n_v, out_t, n_t, src, vmap):
+        capi.check(L.dfusion_mesh_simplify(_flat(vertices) if nv else None, nv, tp, nt, float(cell), flags, _flat(out_v) if n_v else None, n_v,
+                                           _flat(out_t) if n_t else None, n_t, _flat(src) if n_v else None, _flat(vmap) if vmap is not None and nv else None,
+                                           _flat(counts), _stream()), "dfusion_mesh_simplify")
+
+    run(None, 0, None, 0, None, None)
+    kv, kt = (int(c) for c in counts[:2].tolist())
+    out_v = torch.empty((kv, 4), dtype=torch.float32, device=dev)
+    out_t = torch.empty((kt, 3), dtype=torch.int32, device=dev)
+    src = torch.empty(kv, dtype=torch.int32, device=dev)
+    vmap = torch.full((nv,), -1, dtype=torch.int32, device=dev)             # nothing kept: every entry stays 0xffffffff
+    if kv or kt:
+        run(out_v, kv, out_t, kt, src, vmap)
+    return (out_v, out_t, src, vmap, counts) if return_counts else (out_v, out_t, src, vmap)

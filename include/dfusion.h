@@ -344,6 +344,52 @@ int dfusion_gather_rows(const void *src_dev, unsigned int row_bytes /* 4, 12 or 
                         const unsigned int *index_dev, unsigned long long n, void *dst_dev,
                         dfStream stream);
 
+/* A triangle mesh simplified by vertex clustering (no reference counterpart; additive, ABI 7).  DESIGN.md section 23 has the kernels;
+ * tests/mesh_simplify_ref.py restates the rule in numpy and every output equals it bit for bit.
+ * Inputs: V vertices of four floats (x, y, z, w), T triangles of three uint32 indices, a cell size `cell` (f32, finite, > 0), flags.
+ *   CELL      per axis a, t_a = p_a / cell (IEEE f32 division).  A vertex is CLUSTERABLE iff |t_a| < 2^30 on all three axes (NaN and
+ *             inf fail); its cell is c_a = (int)floorf(t_a) -- the cell rule of dfusion_warp_extend.  A vertex at k * cell opens cell k;
+ *             +0 and -0 share cell 0.
+ *   VALID     a triangle is valid iff all three indices are < V (tested before anything is indexed) and all three vertices are
+ *             clusterable; an invalid triangle connects nothing and is never kept.  A vertex is a MEMBER iff a valid triangle uses it.
+ *   CLUSTER   the members of one cell: n its member count, src its smallest member index, and per axis S_a = the sum over its members
+ *             of q_a = (uint32)(f_a * 16777216.f), truncated, with f_a = t_a - floorf(t_a) (IEEE f32 subtraction; exact for t_a >= 0,
+ *             rounded for some t_a < 0, where a tiny negative t_a gives f_a = 1 and q_a = 2^24), as an unsigned 64-bit sum.
+ *   TRIANGLE  every valid triangle's indices are mapped to clusters.  It is COLLAPSED (dropped) unless the three clusters are pairwise
+ *             different.  The others are grouped by their unordered cluster triple; in a group, P are the triangles that are an even
+ *             permutation of the triple taken in ascending src, N the odd ones.  |P| == |N|: the group is a FIN and all of it is
+ *             dropped -- two faces of one surface folded onto each other enclose nothing, and dropping only one of them would leave
+ *             the surface open.  Otherwise the lowest-index triangle of the larger side is kept and the group's others are
+ *             DUPLICATES.  With DF_SIMPLIFY_KEEP_DUPLICATES every non-collapsed triangle is kept and nothing is grouped.  Kept
+ *             triangles come in their original order, their indices in their original rotation.
+ *   VERTICES  one output vertex per cluster that a kept triangle uses, in ascending src.  vertex_src_dev[j] is that src (the gather
+ *             list for any per-vertex attribute, dfusion_gather_rows); vertex_map_dev[v] is the new index of member v's cluster,
+ *             0xffffffff for a non-member and for a cluster no kept triangle uses.
+ *   POSITION  in f64 without contraction: m_a = (double)S_a / (double)n, pos_a = (float)(((double)c_a + m_a * 2^-24) * (double)cell),
+ *             w = 0 -- the members' mean inside the cell, independent of the order of the sums.  With DF_SIMPLIFY_KEEP_FIRST the
+ *             output vertex is the 16 bytes of vertex src as they are.
+ *   counts_dev[8] (u64, WRITTEN, always the full numbers): [0] output vertices, [1] output triangles, [2] invalid, [3] collapsed,
+ *             [4] fin and [5] duplicate triangles ([1] .. [5] add up to T), [6] clusters, [7] the unclusterable vertices among those
+ *             that a triangle with all three indices < V uses.
+ * Nothing is written past a capacity; if a count exceeds its capacity the contents of the output arrays are unspecified
+ * (dfusion_mesh_filter's contract).  Both capacities 0: counts only (vertex_map_dev is not written either).  T == 0 or V == 0 is valid
+ * input: nothing is kept, and with V == 0 every triangle is invalid.  Arrays of length 0 may be NULL.
+ * DF_E_INVALID: V or T > 2^32 - 1, a NULL input or output array with a non-zero size or capacity, counts_dev NULL, cell not finite
+ * or <= 0, a flag bit other than the two below, an output array (counts_dev included) that overlaps vertices_dev or triangles_dev.
+ * Without a device DF_E_NO_DEVICE.  No device-to-host copy, no synchronisation, no floating-point atomics; every launch covers T and V
+ * with 64-bit indices.  Workspace, from the per-(device, stream) scratch of dfusion_extract_mesh (dfusion_release_scratch): 53 V + 4 T
+ * bytes, + 32 T for the groups unless DF_SIMPLIFY_KEEP_DUPLICATES is set, and hipcub's scan storage.                                    */
+#define DF_SIMPLIFY_KEEP_FIRST 1u
+#define DF_SIMPLIFY_KEEP_DUPLICATES 2u
+int dfusion_mesh_simplify(const float *vertices_dev, unsigned long long n_vertices,
+                          const unsigned int *triangles_dev, unsigned long long n_triangles,
+                          float cell, unsigned int flags,
+                          float *vertices_out_dev, unsigned long long vertex_capacity,
+                          unsigned int *triangles_out_dev, unsigned long long triangle_capacity,
+                          unsigned int *vertex_src_dev /* nullable, vertex_capacity */,
+                          unsigned int *vertex_map_dev /* nullable, n_vertices */,
+                          unsigned long long *counts_dev /* [8] */, dfStream stream);
+
 /* ---- colour volume (no reference counterpart: KinFu::operator() drops its colour image; additive, ABI 7) ----------------------
  * A colour volume belongs to a TSDF volume: the same dims, linear layout (x + y X + z X Y) and stored planes (DfSlab), 4 bytes a
  * voxel {c0, c1, c2, w}: three channels in the byte order of the input image (the kernels treat them alike) and a weight byte;
