@@ -1,0 +1,320 @@
+// dfusion_mesh_smooth.hip -- dfusion_mesh_adjacency: the vertex adjacency of an indexed triangle mesh as a CSR of sorted unique
+// neighbours, with the classes of its edges and vertices; dfusion_mesh_smooth: lambda | mu umbrella steps (Taubin) over that adjacency.
+// Both rules are stated in include/dfusion.h and DESIGN.md section 24 and restated in numpy by tests/mesh_smooth_ref.py, against which
+// every output is compared for equality.  The adjacency is decided by integers alone (a sort, a scan for the positions, integer
+// atomicMax and counts); a smoothing step is a function of its input buffer alone, its f32 operations in one stated order.
+//
+//   emit      one lane per triangle: six 2k-bit keys (src << k | dst), k the bits of V -- each half-edge a -> b with a != b as (a, b)
+//             with the value 0 and as (b, a) with the value 1; every other place of the six holds the all-ones key, whose src no vertex
+//             has.  Invalid and degenerate triangles counted
+//   sort      one hipcub::DeviceRadixSort::SortPairs over the 2k bits
+//   heads     a flag of 1 on the first key of every run of equal keys but the all-ones one; one hipcub exclusive sum, in place, with a
+//             spare element for the total: the position of every CSR entry
+//   edges     one lane per sorted key: a run head writes its dst at its position; the head of a run with src < dst counts the values
+//             of its run (f zeros, b ones), classifies the edge and raises the classes of its two ends by integer atomicMax
+//   rows      one lane per v in 0 .. V: a binary search for the first key with src >= v; row_start[v] is that key's position
+//   classes   one lane per vertex: its class byte from its degree and the raised word; the vertices with a neighbour and those on a
+//             boundary or irregular edge counted
+//   step      one lane per vertex: dfusion_mesh_smooth's hot path, run 2 x iterations times (below)
+// Every grid is capped at DF_MSM_MAX_BLOCKS workgroups (524 288 lanes) and strides over its range with 64-bit indices.
+#include <hipcub/hipcub.hpp>
+#include "dfusion_internal.h"
+#include <math.h>
+
+#pragma clang fp contract(off)                       // p + s * delta is a multiply, then an add (the library's -ffp-contract=off, kept for this file)
+
+#define DF_MSM_MAX_BLOCKS 2048u
+#define DF_MSM_GATHER 8                              // neighbour positions in flight per lane
+
+static inline unsigned df_msm_blocks(size_t n) { const size_t b = (n + 255) / 256; return (unsigned)(b < DF_MSM_MAX_BLOCKS ? b : DF_MSM_MAX_BLOCKS); }
+
+struct DfMsmArgs {
+    const uint32_t* tris; size_t T; size_t V; size_t N;      // N = 6 T keys
+    int k;                                                   // bits of V: every index < V fits, and 2^k - 1 is no vertex
+    unsigned long long *keys_in, *keys;                      // [N] as emitted, sorted
+    uint8_t *dir_in, *dir;                                   // [N] 0: the half-edge src -> dst exists, 1: its reverse does
+    uint32_t* pos;                                           // [N + 1] head flags, then their exclusive sum (over keys_in, dead after the sort)
+    uint32_t* cls;                                           // [V] 0, raised to 2 (boundary) or 3 (irregular)
+    uint32_t* row_start;                                     // [V + 1] the caller's, or workspace
+    uint32_t* nbr; unsigned long long cap;
+    uint8_t* vclass;
+    unsigned long long* counts;
+};
+
+__device__ __forceinline__ void msm_count(unsigned long long* counts, int which, unsigned long long wave_uniform)
+{
+    if ((threadIdx.x & 63) == 0 && wave_uniform) atomicAdd(&counts[which], wave_uniform);
+}
+
+__global__ __launch_bounds__(256) void df_msm_emit_kernel(const DfMsmArgs a)
+{
+    const unsigned long long none = a.k == 32 ? ~0ull : (1ull << (2 * a.k)) - 1ull;
+    unsigned long long n_invalid = 0ull, n_degenerate = 0ull;           // wave-uniform
+    for (size_t t0 = (size_t)blockIdx.x * 256; t0 < a.T; t0 += (size_t)gridDim.x * 256) {      // (workgroup-uniform trip count)
+        const size_t t = t0 + threadIdx.x;
+        bool invalid = false, degenerate = false;
+        if (t < a.T) {
+            const uint32_t i[3] = {a.tris[3 * t], a.tris[3 * t + 1], a.tris[3 * t + 2]};
+            invalid = !((size_t)i[0] < a.V && (size_t)i[1] < a.V && (size_t)i[2] < a.V);       // tested before anything is indexed
+            degenerate = !invalid && (i[0] == i[1] || i[1] == i[2] || i[0] == i[2]);
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                const unsigned long long s = i[e], d = i[e == 2 ? 0 : e + 1];
+                const bool live = !invalid && s != d;
+                a.keys_in[6 * t + 2 * e] = live ? (s << a.k | d) : none;
+                a.keys_in[6 * t + 2 * e + 1] = live ? (d << a.k | s) : none;
+                a.dir_in[6 * t + 2 * e] = 0;
+                a.dir_in[6 * t + 2 * e + 1] = 1;
+            }
+        }
+        n_invalid += (unsigned long long)__popcll(__ballot(invalid));
+        n_degenerate += (unsigned long long)__popcll(__ballot(degenerate));
+    }
+    msm_count(a.counts, 5, n_invalid);
+    msm_count(a.counts, 6, n_degenerate);
+}
+
+__global__ __launch_bounds__(256) void df_msm_heads_kernel(const DfMsmArgs a)
+{
+    const unsigned long long none = a.k == 32 ? ~0ull : (1ull << (2 * a.k)) - 1ull;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i <= a.N; i += (size_t)gridDim.x * 256) {
+        uint32_t head = 0u;
+        if (i < a.N) {
+            const unsigned long long key = a.keys[i];
+            head = key != none && (i == 0 || a.keys[i - 1] != key) ? 1u : 0u;
+        }
+        a.pos[i] = head;
+    }
+}
+
+__global__ __launch_bounds__(256) void df_msm_edges_kernel(const DfMsmArgs a)
+{
+    const unsigned long long lo_mask = a.k == 32 ? 0xffffffffull : (1ull << a.k) - 1ull;
+    unsigned long long n_edges = 0ull, n_boundary = 0ull, n_irregular = 0ull;                  // wave-uniform
+    for (size_t i0 = (size_t)blockIdx.x * 256; i0 < a.N; i0 += (size_t)gridDim.x * 256) {
+        const size_t i = i0 + threadIdx.x;
+        bool edge = false, boundary = false, irregular = false;
+        if (i < a.N) {
+            const uint32_t p = a.pos[i];
+            if (a.pos[i + 1] != p) {                                    // a run head
+                const unsigned long long key = a.keys[i];
+                const uint32_t src = (uint32_t)(key >> a.k), dst = (uint32_t)(key & lo_mask);
+                if ((unsigned long long)p < a.cap) a.nbr[p] = dst;
+                if (src < dst) {                                        // the edge {src < dst} is judged once, here
+                    unsigned long long f = 0ull, b = 0ull;              // half-edges src -> dst, dst -> src
+                    for (size_t j = i; j < a.N && a.keys[j] == key; ++j) { if (a.dir[j]) ++b; else ++f; }
+                    edge = true;
+                    boundary = f + b == 1ull;
+                    irregular = !boundary && !(f == 1ull && b == 1ull);
+                    if (boundary || irregular) {
+                        const uint32_t c = irregular ? 3u : 2u;
+                        atomicMax(&a.cls[src], c);
+                        atomicMax(&a.cls[dst], c);
+                    }
+                }
+            }
+        }
+        n_edges += (unsigned long long)__popcll(__ballot(edge));
+        n_boundary += (unsigned long long)__popcll(__ballot(boundary));
+        n_irregular += (unsigned long long)__popcll(__ballot(irregular));
+    }
+    msm_count(a.counts, 1, n_edges);
+    msm_count(a.counts, 2, n_boundary);
+    msm_count(a.counts, 3, n_irregular);
+}
+
+__global__ __launch_bounds__(256) void df_msm_rows_kernel(const DfMsmArgs a)
+{
+    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v <= a.V; v += (size_t)gridDim.x * 256) {
+        size_t lo = 0, hi = a.N;                                        // the first key whose src is >= v (the all-ones key's is 2^k - 1 >= V)
+        while (lo < hi) {
+            const size_t mid = lo + (hi - lo) / 2;
+            if ((a.keys[mid] >> a.k) < (unsigned long long)v) lo = mid + 1; else hi = mid;
+        }
+        a.row_start[v] = a.pos[lo];
+        if (v == a.V) a.counts[0] = a.pos[a.N];                         // (= pos[lo]: no real key has a src >= V)
+    }
+}
+
+__global__ __launch_bounds__(256) void df_msm_classes_kernel(const DfMsmArgs a)
+{
+    unsigned long long n_used = 0ull, n_open = 0ull;                    // wave-uniform
+    for (size_t v0 = (size_t)blockIdx.x * 256; v0 < a.V; v0 += (size_t)gridDim.x * 256) {
+        const size_t v = v0 + threadIdx.x;
+        uint32_t c = 0u;
+        if (v < a.V) {
+            const uint32_t raised = a.cls[v];
+            c = a.row_start[v + 1] != a.row_start[v] ? (raised > 1u ? raised : 1u) : 0u;
+            if (a.vclass) a.vclass[v] = (uint8_t)c;
+        }
+        n_used += (unsigned long long)__popcll(__ballot(c != 0u));
+        n_open += (unsigned long long)__popcll(__ballot(c >= 2u));
+    }
+    msm_count(a.counts, 4, n_used);
+    msm_count(a.counts, 7, n_open);
+}
+
+__global__ void df_msm_set_kernel(unsigned long long* dst, unsigned long long value)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) *dst = value;
+}
+
+static inline bool msm_overlap(const void* p, size_t pn, const void* q, size_t qn)
+{
+    if (!p || !q || !pn || !qn) return false;
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + qn && b < a + pn;
+}
+
+extern "C" int dfusion_mesh_adjacency(const unsigned int* triangles_dev, unsigned long long n_triangles, unsigned long long n_vertices,
+                                      unsigned int* row_start_dev, unsigned int* neighbours_dev, unsigned long long neighbour_capacity,
+                                      unsigned char* vertex_class_dev, unsigned long long* counts_dev, dfStream stream)
+{
+    if (n_vertices > 0xffffffffull || n_triangles > 0xffffffffull / 6ull || !counts_dev) return DF_E_INVALID;
+    if ((n_triangles && !triangles_dev) || (neighbour_capacity && !neighbours_dev)) return DF_E_INVALID;
+    const size_t V = (size_t)n_vertices, T = (size_t)n_triangles, N = 6 * T;
+    const struct { const void* p; size_t n; } outs[4] = {{row_start_dev, (V + 1) * 4}, {neighbours_dev, (size_t)neighbour_capacity * 4},
+                                                         {vertex_class_dev, V}, {counts_dev, 64}};
+    for (const auto& o : outs)
+        if (msm_overlap(triangles_dev, T * 12, o.p, o.n)) return DF_E_INVALID;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return DF_E_NO_DEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    DF_HIP(hipMemsetAsync(counts_dev, 0, 64, st));
+    if (!V || !T) {                                                       // no vertex: every triangle is invalid; no triangle: no neighbour
+        if (row_start_dev) DF_HIP(hipMemsetAsync(row_start_dev, 0, (V + 1) * 4, st));
+        if (vertex_class_dev && V) DF_HIP(hipMemsetAsync(vertex_class_dev, 0, V, st));
+        if (!V && T) { hipLaunchKernelGGL(df_msm_set_kernel, dim3(1), dim3(64), 0, st, counts_dev + 5, n_triangles); DF_LAUNCH_CHECK(); }
+        return DF_OK;
+    }
+    DfMsmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.tris = triangles_dev; a.T = T; a.V = V; a.N = N;
+    a.k = 1;
+    while (a.k < 32 && (V >> a.k)) ++a.k;                                 // 2^k > V
+    a.nbr = neighbours_dev; a.cap = neighbour_capacity; a.vclass = vertex_class_dev; a.counts = counts_dev;
+    size_t sort_bytes = 0, scan_bytes = 0;
+    DF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                              (const uint8_t*)nullptr, (uint8_t*)nullptr, N, 0, 2 * a.k, st));
+    DF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, N + 1, st));
+    size_t cub_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
+    // workspace: [keys as emitted 48 T, then the positions 24 T + 4 over them] [sorted keys 48 T] [values 6 T] [sorted values 6 T]
+    //            [raised classes 4 V, zeroed] [row_start 4 (V + 1), unless the caller gives one] [hipcub's storage]
+    auto up = [](size_t b) { return (b + 15) / 16 * 16; };
+    const size_t o_keys_in = 0, o_keys = o_keys_in + up(N * 8), o_dir_in = o_keys + up(N * 8), o_dir = o_dir_in + up(N), o_cls = o_dir + up(N),
+                 o_rows = o_cls + up(V * 4), o_cub = (o_rows + (row_start_dev ? 0 : up((V + 1) * 4)) + 255) / 256 * 256;
+    DfScratchHold hold(st, o_cub + cub_bytes);                            // held until the last launch is enqueued
+    if (!hold.entry) return (int)hipErrorOutOfMemory;
+    char* const ws = hold.mem;
+    a.keys_in = (unsigned long long*)(ws + o_keys_in); a.keys = (unsigned long long*)(ws + o_keys);
+    a.dir_in = (uint8_t*)(ws + o_dir_in); a.dir = (uint8_t*)(ws + o_dir);
+    a.pos = (uint32_t*)(ws + o_keys_in);                                  // 4 (N + 1) <= 8 N
+    a.cls = (uint32_t*)(ws + o_cls);
+    a.row_start = row_start_dev ? row_start_dev : (uint32_t*)(ws + o_rows);
+    DF_HIP(hipMemsetAsync(a.cls, 0, V * 4, st));
+    const dim3 gt(df_msm_blocks(T)), gn(df_msm_blocks(N + 1)), gv(df_msm_blocks(V + 1)), wg(256);
+    hipLaunchKernelGGL(df_msm_emit_kernel, gt, wg, 0, st, a);
+    DF_LAUNCH_CHECK();
+    DF_HIP(hipcub::DeviceRadixSort::SortPairs(ws + o_cub, cub_bytes, (const unsigned long long*)a.keys_in, a.keys, (const uint8_t*)a.dir_in, a.dir,
+                                              N, 0, 2 * a.k, st));
+    hipLaunchKernelGGL(df_msm_heads_kernel, gn, wg, 0, st, a);
+    DF_LAUNCH_CHECK();
+    DF_HIP(hipcub::DeviceScan::ExclusiveSum(ws + o_cub, cub_bytes, a.pos, a.pos, N + 1, st));
+    hipLaunchKernelGGL(df_msm_edges_kernel, gn, wg, 0, st, a);
+    DF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(df_msm_rows_kernel, gv, wg, 0, st, a);
+    DF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(df_msm_classes_kernel, gv, wg, 0, st, a);
+    DF_LAUNCH_CHECK();
+    return DF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- dfusion_mesh_smooth
+// One step: Q[v] = P[v] + s * (mean of P over v's row - P[v]) for a movable v, P[v] as it is otherwise.  One lane per vertex.  The row
+// bounds are one 8-byte load where v is even (row_start is 8-byte aligned then), every position one load of a float4 (of a neighbour
+// the compiler fetches the 12 bytes that are used), the result one 16-byte store.  A row is taken DF_MSM_GATHER neighbours at a time: their indices are read first, then all their positions are
+// requested, and only then added in the row's order -- up to DF_MSM_GATHER gathers in flight per lane, whatever the degree.
+__global__ __launch_bounds__(256) void df_msm_step_kernel(const float4* __restrict__ P, float4* __restrict__ Q, const uint32_t* __restrict__ row_start,
+                                                          const uint32_t* __restrict__ nbr, const uint8_t* __restrict__ vclass, size_t V, float s,
+                                                          int fix_boundary)
+{
+    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (size_t)gridDim.x * 256) {
+        uint32_t r0, r1;
+        if ((v & 1) == 0 && ((uintptr_t)row_start & 7) == 0) {
+            const uint2 r = *reinterpret_cast<const uint2*>(row_start + v);
+            r0 = r.x; r1 = r.y;
+        } else {
+            r0 = row_start[v]; r1 = row_start[v + 1];
+        }
+        const float4 p = P[v];
+        const uint32_t d = r1 - r0;
+        const bool movable = d != 0u && (!fix_boundary || !vclass || vclass[v] == 1);
+        float4 q = p;
+        if (movable) {
+            float ax = 0.f, ay = 0.f, az = 0.f;
+            for (size_t j = r0; j < r1; j += DF_MSM_GATHER) {
+                const size_t left = r1 - j;                              // >= 1
+                uint32_t u[DF_MSM_GATHER];
+                float4 g[DF_MSM_GATHER];
+#pragma unroll
+                for (int c = 0; c < DF_MSM_GATHER; ++c) u[c] = (size_t)c < left ? nbr[j + c] : (uint32_t)v;     // past the row: v itself, not added
+#pragma unroll
+                for (int c = 0; c < DF_MSM_GATHER; ++c) g[c] = P[u[c]];
+#pragma unroll
+                for (int c = 0; c < DF_MSM_GATHER; ++c)
+                    if ((size_t)c < left) { ax = ax + g[c].x; ay = ay + g[c].y; az = az + g[c].z; }
+            }
+            const float n = (float)d;
+            const float mx = ax / n, my = ay / n, mz = az / n;               // IEEE f32 division
+            const float dx = mx - p.x, dy = my - p.y, dz = mz - p.z;
+            q.x = p.x + s * dx; q.y = p.y + s * dy; q.z = p.z + s * dz;       // a multiply, then an add
+        }
+        Q[v] = q;
+    }
+}
+
+extern "C" int dfusion_mesh_smooth(const float* vertices_dev, unsigned long long n_vertices, const unsigned int* row_start_dev,
+                                   const unsigned int* neighbours_dev, unsigned long long n_neighbours, const unsigned char* vertex_class_dev,
+                                   int iterations, float lambda, float mu, unsigned int flags, float* vertices_out_dev, dfStream stream)
+{
+    if (n_vertices > 0xffffffffull || n_neighbours > 0xffffffffull || iterations < 0 || !isfinite(lambda) || !isfinite(mu)) return DF_E_INVALID;
+    if (flags & ~DF_SMOOTH_FIX_BOUNDARY) return DF_E_INVALID;
+    if (n_vertices && (!vertices_dev || !vertices_out_dev || !row_start_dev)) return DF_E_INVALID;
+    if (n_neighbours && !neighbours_dev) return DF_E_INVALID;
+    const size_t V = (size_t)n_vertices;
+    const bool in_place = vertices_out_dev == vertices_dev;
+    const struct { const void* p; size_t n; } ins[4] = {{in_place ? nullptr : vertices_dev, V * 16}, {row_start_dev, (V + 1) * 4},
+                                                        {neighbours_dev, (size_t)n_neighbours * 4}, {vertex_class_dev, V}};
+    for (const auto& i : ins)
+        if (msm_overlap(i.p, i.n, vertices_out_dev, V * 16)) return DF_E_INVALID;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return DF_E_NO_DEVICE;
+    if (!V) return DF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t per_iteration = mu == 0.f ? 1 : 2, steps = (size_t)iterations * per_iteration;
+    if (!steps) {
+        if (!in_place) DF_HIP(hipMemcpyAsync(vertices_out_dev, vertices_dev, V * 16, hipMemcpyDeviceToDevice, st));
+        return DF_OK;
+    }
+    // Ping-pong between the output and one scratch buffer [16 V].  Out of place the step that has an even number of steps after it
+    // writes the output, so the last one does.  In place no step may write the buffer it reads: step 0 writes the scratch, and when
+    // that leaves the last step in the scratch too (an odd count) one copy brings the result home.
+    DfScratchHold hold(st, steps > 1 || in_place ? V * 16 : 16);
+    if (!hold.entry) return (int)hipErrorOutOfMemory;
+    float4* const scratch = (float4*)hold.mem;
+    float4* const out = (float4*)vertices_out_dev;
+    const dim3 grid(df_msm_blocks(V)), wg(256);
+    const float4* src = (const float4*)vertices_dev;
+    float4* dst = nullptr;
+    for (size_t k = 0; k < steps; ++k) {
+        const bool to_out = in_place ? (k & 1) != 0 : ((steps - 1 - k) & 1) == 0;
+        dst = to_out ? out : scratch;
+        const float s = per_iteration == 2 && (k & 1) ? mu : lambda;
+        hipLaunchKernelGGL(df_msm_step_kernel, grid, wg, 0, st, src, dst, (const uint32_t*)row_start_dev, (const uint32_t*)neighbours_dev,
+                           (const uint8_t*)vertex_class_dev, V, s, (int)((flags & DF_SMOOTH_FIX_BOUNDARY) != 0));
+        DF_LAUNCH_CHECK();
+        src = dst;
+    }
+    if (dst != out) DF_HIP(hipMemcpyAsync(out, scratch, V * 16, hipMemcpyDeviceToDevice, st));
+    return DF_OK;
+}

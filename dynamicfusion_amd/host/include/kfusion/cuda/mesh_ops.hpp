@@ -1,7 +1,8 @@
 // kfusion/cuda/mesh_ops.hpp -- kfusion::cuda::meshComponents / removeSmallComponents: the connected components of an indexed triangle
 // mesh and the mesh without its small pieces (no reference counterpart).  Forward to dfusion_mesh_components / dfusion_mesh_filter /
 // dfusion_gather_rows of include/dfusion.h, where the rule is stated; no kernels of their own.  simplifyMesh: the mesh simplified by
-// vertex clustering (dfusion_mesh_simplify).  Same calls as the Python mirror
+// vertex clustering (dfusion_mesh_simplify).  meshAdjacency / smoothMesh: the vertex adjacency with the edge statistics and Taubin
+// smoothing over it (dfusion_mesh_adjacency / dfusion_mesh_smooth).  Same calls as the Python mirror
 // (dynamicfusion_amd.mesh_ops).
 #pragma once
 #include <kfusion/types.hpp>
@@ -33,5 +34,23 @@ void gatherRows(const DeviceArray<RGB>& src, const DeviceArray<int>& index, Devi
 void simplifyMesh(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, float cell, unsigned int flags,
                   DeviceArray<Point>& out_vertices, DeviceArray<int>& out_triangles, DeviceArray<int>& vertex_src,
                   DeviceArray<unsigned long long>* counts = nullptr);
+
+/// The vertex adjacency of a mesh over n_vertices vertices: row v of `neighbours`, [row_start[v], row_start[v + 1]), holds v's
+/// neighbours, each once, ascending; vertex_class[v] = 0 no neighbour, 1 interior, 2 on a boundary edge, 3 on an irregular edge (used
+/// three or more times, or twice in the same direction); counts (optional): the call's 8 counts -- CSR entries, edges, boundary and
+/// irregular edges, vertices with a neighbour, invalid and degenerate triangles, vertices of class 2 or 3.  One call with a capacity of
+/// 6 T, trimmed from one read-back of the counts.
+void meshAdjacency(const DeviceArray<int>& triangles, size_t n_vertices, DeviceArray<int>& row_start, DeviceArray<int>& neighbours,
+                   DeviceArray<unsigned char>& vertex_class, DeviceArray<unsigned long long>* counts = nullptr);
+
+/// `iterations` of Taubin's lambda | mu smoothing (a step with lambda towards the mean of the neighbours, then unless mu == 0 a step with
+/// mu on its result) over a meshAdjacency; with DF_SMOOTH_FIX_BOUNDARY only the vertices of class 1 move.  out_vertices may be
+/// `vertices` itself.  Nothing synchronises.
+void smoothMesh(const DeviceArray<Point>& vertices, const DeviceArray<int>& row_start, const DeviceArray<int>& neighbours,
+                const DeviceArray<unsigned char>& vertex_class, int iterations, float lambda, float mu, unsigned int flags,
+                DeviceArray<Point>& out_vertices);
+/// The same, building the adjacency of `triangles` first.
+void smoothMesh(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, int iterations, float lambda, float mu, unsigned int flags,
+                DeviceArray<Point>& out_vertices);
 
 } }

@@ -104,6 +104,9 @@ public:
     void fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& triangles, unsigned long long min_component_triangles, bool keep_largest = false) const;
     // and, after that filter, simplified by vertex clustering at simplify_cell (kfusion/cuda/mesh_ops.hpp simplifyMesh); 0: the call above
     void fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& triangles, unsigned long long min_component_triangles, bool keep_largest, float simplify_cell) const;
+    // and, after both, smoothed by smooth_iterations lambda | mu iterations with the boundary fixed (kfusion/cuda/mesh_ops.hpp smoothMesh); 0: the call above
+    void fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& triangles, unsigned long long min_component_triangles, bool keep_largest, float simplify_cell,
+                   int smooth_iterations, float smooth_lambda = 0.5f, float smooth_mu = -0.53f) const;
     void compute_points();
     void compute_normals();
 #ifdef KFUSION_USE_OPENCV

@@ -334,6 +334,14 @@ void TsdfVolume::fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& trian
     simplifyMesh(all_vertices, all_triangles, simplify_cell, 0u, vertices, triangles, vertex_src);
 }
 
+void TsdfVolume::fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& triangles, unsigned long long min_component_triangles, bool keep_largest,
+                           float simplify_cell, int smooth_iterations, float smooth_lambda, float smooth_mu) const
+{
+    fetchMesh(vertices, triangles, min_component_triangles, keep_largest, simplify_cell);
+    if (smooth_iterations == 0 || vertices.size() == 0) return;
+    smoothMesh(vertices, triangles, smooth_iterations, smooth_lambda, smooth_mu, DF_SMOOTH_FIX_BOUNDARY, vertices);
+}
+
 // ------------------------------------------------------------------------------------------ mesh components (include/dfusion.h dfusion_mesh_*)
 void kfusion::cuda::meshComponents(const DeviceArray<int>& triangles, size_t n_vertices, DeviceArray<int>& vertex_label, DeviceArray<int>& triangle_count,
                                    DeviceArray<unsigned long long>* counts)
@@ -401,6 +409,46 @@ void kfusion::cuda::simplifyMesh(const DeviceArray<Point>& vertices, const Devic
     if (n[0] || n[1])
         run(n[0] ? (float*)out_vertices.ptr() : nullptr, n[0] ? (unsigned int*)vertex_src.ptr() : nullptr, n[0],
             n[1] ? (unsigned int*)out_triangles.ptr() : nullptr, n[1]);
+}
+
+void kfusion::cuda::meshAdjacency(const DeviceArray<int>& triangles, size_t n_vertices, DeviceArray<int>& row_start, DeviceArray<int>& neighbours,
+                                  DeviceArray<unsigned char>& vertex_class, DeviceArray<unsigned long long>* counts_out)
+{
+    const size_t nt = triangles.size() / 3;
+    DeviceArray<unsigned long long> own;
+    DeviceArray<unsigned long long>& counts = counts_out ? *counts_out : own;
+    counts.create(8);
+    row_start.create(n_vertices + 1);
+    vertex_class.create(n_vertices);
+    DeviceArray<int> all;
+    all.create(6 * nt);
+    KF_DF(dfusion_mesh_adjacency(nt ? (const unsigned int*)triangles.ptr() : nullptr, nt, n_vertices, (unsigned int*)row_start.ptr(),
+                                 nt ? (unsigned int*)all.ptr() : nullptr, 6 * nt, n_vertices ? vertex_class.ptr() : nullptr, counts.ptr(), nullptr));
+    unsigned long long n[8];
+    counts.download(n);
+    neighbours.create((size_t)n[0]);
+    if (n[0]) KF_HIP(hipMemcpyAsync(neighbours.ptr(), all.ptr(), (size_t)n[0] * sizeof(int), hipMemcpyDeviceToDevice, nullptr));
+    KF_HIP(hipStreamSynchronize(nullptr));                                // `all` is freed on return
+}
+
+void kfusion::cuda::smoothMesh(const DeviceArray<Point>& vertices, const DeviceArray<int>& row_start, const DeviceArray<int>& neighbours,
+                               const DeviceArray<unsigned char>& vertex_class, int iterations, float lambda, float mu, unsigned int flags,
+                               DeviceArray<Point>& out_vertices)
+{
+    const size_t nv = vertices.size(), nn = neighbours.size();
+    if (out_vertices.ptr() != vertices.ptr() || out_vertices.size() != nv) out_vertices.create(nv);
+    KF_DF(dfusion_mesh_smooth(nv ? (const float*)vertices.ptr() : nullptr, nv, (const unsigned int*)row_start.ptr(),
+                              nn ? (const unsigned int*)neighbours.ptr() : nullptr, nn, vertex_class.size() ? vertex_class.ptr() : nullptr, iterations,
+                              lambda, mu, flags, nv ? (float*)out_vertices.ptr() : nullptr, nullptr));
+}
+
+void kfusion::cuda::smoothMesh(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, int iterations, float lambda, float mu,
+                               unsigned int flags, DeviceArray<Point>& out_vertices)
+{
+    DeviceArray<int> row_start, neighbours; DeviceArray<unsigned char> vertex_class;
+    meshAdjacency(triangles, vertices.size(), row_start, neighbours, vertex_class);
+    smoothMesh(vertices, row_start, neighbours, vertex_class, iterations, lambda, mu, flags, out_vertices);
+    KF_HIP(hipStreamSynchronize(nullptr));                                // the adjacency is freed on return
 }
 
 // ------------------------------------------------------------------------------------------ ColorVolume (include/dfusion.h dfusion_color_*)

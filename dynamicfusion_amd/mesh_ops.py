@@ -1,6 +1,7 @@
 """Operations on an indexed triangle mesh (fetchMesh's, or any) over the C-ABI: its connected components and the mesh without its small
 pieces (include/dfusion.h dfusion_mesh_components / dfusion_mesh_filter / dfusion_gather_rows, where the rule is stated), and the mesh
-simplified by vertex clustering (dfusion_mesh_simplify).  Device tensors in, device tensors out; all compute is in libdfusion_hip.so."""
+simplified by vertex clustering (dfusion_mesh_simplify), its vertex adjacency with the edge statistics (dfusion_mesh_adjacency) and Taubin
+smoothing over it (dfusion_mesh_smooth).  Device tensors in, device tensors out; all compute is in libdfusion_hip.so."""
 import torch
 
 from . import capi
@@ -115,3 +116,60 @@ def simplify_mesh(vertices, triangles, cell, keep_first=False, keep_duplicates=F
     if kv or kt:
         run(out_v, kv, out_t, kt, src, vmap)
     return (out_v, out_t, src, vmap, counts) if return_counts else (out_v, out_t, src, vmap)
+
+
+FIX_BOUNDARY = 1                                         # DF_SMOOTH_FIX_BOUNDARY
+TOPOLOGY_NAMES = ("csr_entries", "edges", "boundary_edges", "irregular_edges", "used_vertices", "invalid_triangles", "degenerate_triangles",
+                  "open_vertices")
+
+
+def mesh_adjacency(triangles, n_vertices, return_counts=False):
+    """The vertex adjacency of an indexed mesh (include/dfusion.h dfusion_mesh_adjacency has the rule): triangles int32 [T, 3] (uint32
+    bits) over n_vertices vertices -> (row_start int32 [V + 1], neighbours int32 [row_start[V]]: every vertex's neighbours, each once,
+    ascending (uint32 bits both), vertex_class uint8 [V]: 0 no neighbour, 1 interior, 2 on a boundary edge, 3 on an irregular edge); with
+    return_counts also counts int64 [8]: CSR entries, edges, boundary and irregular edges, vertices with a neighbour, invalid and
+    degenerate triangles, vertices of class 2 or 3.  One call with a capacity of 6 T, trimmed from one read-back of the counts."""
+    tp, nt = _triangles(triangles)
+    nv = int(n_vertices)
+    dev = triangles.device
+    row_start = torch.empty(nv + 1, dtype=torch.int32, device=dev)
+    neighbours = torch.empty(6 * nt, dtype=torch.int32, device=dev)
+    vertex_class = torch.empty(nv, dtype=torch.uint8, device=dev)
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    capi.check(capi.lib().dfusion_mesh_adjacency(tp, nt, nv, _flat(row_start), _flat(neighbours) if nt else None, 6 * nt,
+                                                 _flat(vertex_class) if nv else None, _flat(counts), _stream()), "dfusion_mesh_adjacency")
+    neighbours = neighbours[:int(counts[0])]
+    return (row_start, neighbours, vertex_class, counts) if return_counts else (row_start, neighbours, vertex_class)
+
+
+def mesh_topology(triangles, n_vertices):
+    """-> dict of dfusion_mesh_adjacency's eight counts (TOPOLOGY_NAMES) plus `euler`, the Euler characteristic used_vertices - edges +
+    valid triangles (of a mesh without degenerate triangles).  A count-only call; the counts are read back."""
+    tp, nt = _triangles(triangles)
+    counts = torch.empty(8, dtype=torch.int64, device=triangles.device)
+    capi.check(capi.lib().dfusion_mesh_adjacency(tp, nt, int(n_vertices), None, None, 0, None, _flat(counts), _stream()), "dfusion_mesh_adjacency")
+    out = dict(zip(TOPOLOGY_NAMES, (int(c) for c in counts.tolist())))
+    out["euler"] = out["used_vertices"] - out["edges"] + (nt - out["invalid_triangles"])
+    return out
+
+
+def smooth_mesh(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, fix_boundary=True, adjacency=None):
+    """Taubin's lambda | mu smoothing (include/dfusion.h dfusion_mesh_smooth has the rule): every iteration moves each vertex by lam
+    towards the mean of its neighbours and then, unless mu == 0, by mu (negative: away again, which undoes the shrinkage) on the
+    result; with fix_boundary only the vertices of class 1 move.  vertices float32 [V, 4], triangles int32 [T, 3] (uint32 bits) -> new
+    vertices float32 [V, 4]; the triangles stay as they are.  adjacency: mesh_adjacency's (row_start, neighbours, vertex_class) of
+    this mesh, built here when None.  Nothing synchronises when an adjacency is given."""
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 4 or not vertices.is_contiguous():
+        raise ValueError("vertices %s %s, expected contiguous float32 [V, 4]" % (vertices.dtype, tuple(vertices.shape)))
+    if vertices.device != triangles.device:
+        raise ValueError("vertices on %s, triangles on %s" % (vertices.device, triangles.device))
+    nv = int(vertices.shape[0])
+    row_start, neighbours, vertex_class = mesh_adjacency(triangles, nv) if adjacency is None else adjacency[:3]
+    if int(row_start.shape[0]) != nv + 1 or (vertex_class is not None and int(vertex_class.shape[0]) != nv):
+        raise ValueError("adjacency of %d vertices for %d vertices" % (int(row_start.shape[0]) - 1, nv))
+    nn = int(neighbours.shape[0])
+    out = torch.empty_like(vertices)
+    capi.check(capi.lib().dfusion_mesh_smooth(_flat(vertices) if nv else None, nv, _flat(row_start), _flat(neighbours) if nn else None, nn,
+                                              _flat(vertex_class) if vertex_class is not None and nv else None, int(iterations), float(lam), float(mu),
+                                              FIX_BOUNDARY if fix_boundary else 0, _flat(out) if nv else None, _stream()), "dfusion_mesh_smooth")
+    return out

@@ -385,13 +385,16 @@ class TsdfVolume:
         return normals
 
     # ---- no reference counterpart: the surface as a triangle mesh (include/dfusion.h dfusion_extract_mesh)
-    def fetchMesh(self, with_normals=False, min_component_triangles=0, keep_largest=False, simplify_cell=0.0):
+    def fetchMesh(self, with_normals=False, min_component_triangles=0, keep_largest=False, simplify_cell=0.0, smooth_iterations=0, smooth_lambda=0.5,
+                  smooth_mu=-0.53):
         """-> (vertices float32 [n, 4], triangles int32 [m, 3] (uint32 bits)) device tensors, in the rule's order; with_normals: also
         fetchNormals(vertices).  One count-only call, then one of exactly that size; the counts stay in last_mesh_counts_.
         min_component_triangles / keep_largest: the mesh goes through mesh_ops.remove_small_components first (the connected pieces of
         fewer triangles, or all but the largest, are dropped with the vertices no triangle uses; the normals are then fetched for the
         kept vertices only).  simplify_cell > 0: the mesh -- after the component filter -- is simplified by vertex clustering at that cell
-        size (mesh_ops.simplify_mesh); the normals are fetched for the new vertices.  At their defaults nothing but the calls above runs."""
+        size (mesh_ops.simplify_mesh); the normals are fetched for the new vertices.  smooth_iterations > 0: the vertices -- after both --
+        go through that many lambda | mu iterations of mesh_ops.smooth_mesh (boundary vertices fixed); the normals are fetched at the
+        smoothed positions.  At their defaults nothing but the calls above runs."""
         aff = capi.floats(aff12(self.pose_))
         counts = torch.empty(2, dtype=torch.int64, device=self.device)
         capi.check(capi.lib().dfusion_extract_mesh(self.c_volume(), self.c_slab(), aff, None, 0, None, 0, _ptr(counts), _stream()),
@@ -414,6 +417,9 @@ class TsdfVolume:
             vertices, triangles, _, _ = simplify_mesh(vertices, triangles, simplify_cell)
             if with_normals and not vertices.shape[0]:
                 return vertices, triangles, torch.empty((0, 4), dtype=torch.float32, device=self.device)
+        if smooth_iterations and vertices.shape[0]:
+            from .mesh_ops import smooth_mesh
+            vertices = smooth_mesh(vertices, triangles, smooth_iterations, smooth_lambda, smooth_mu)
         if with_normals:
             return vertices, triangles, self.fetchNormals(vertices)
         return vertices, triangles

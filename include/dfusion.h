@@ -390,6 +390,67 @@ int dfusion_mesh_simplify(const float *vertices_dev, unsigned long long n_vertic
                           unsigned int *vertex_map_dev /* nullable, n_vertices */,
                           unsigned long long *counts_dev /* [8] */, dfStream stream);
 
+/* The vertex adjacency of an indexed triangle mesh, with its edge statistics (no reference counterpart; additive, ABI 7).  DESIGN.md
+ * section 24 has the kernels; tests/mesh_smooth_ref.py restates the rule in numpy and every output equals it bit for bit.
+ * Inputs: T triangles of three uint32 indices over V vertices (the positions take no part).
+ *   VALID       a triangle is valid iff its three indices are < V (tested before anything is indexed); an invalid one contributes
+ *               nothing.  A valid triangle with two equal indices is DEGENERATE; it still contributes the pairs whose ends differ.
+ *   HALF-EDGES  of a valid triangle (a, b, c): a -> b, b -> c, c -> a, leaving out those with equal ends.
+ *   NEIGHBOUR   u is a neighbour of v iff a half-edge u -> v or v -> u exists.
+ *   CSR         row v of neighbours_dev, [row_start_dev[v], row_start_dev[v + 1]), holds v's neighbours, each once, in ascending
+ *               index; row_start_dev[0] = 0, the difference of two consecutive entries is v's degree, row_start_dev[V] the total.
+ *   EDGE        for an undirected edge {lo < hi}, f = the number of half-edges lo -> hi and b = the number hi -> lo.  INTERIOR iff
+ *               f == 1 and b == 1, BOUNDARY iff f + b == 1, everything else IRREGULAR: an edge used three or more times, and an
+ *               edge used twice in the same direction (two faces that do not agree on the surface's side).
+ *   vertex_class_dev[v] (one byte)  0 = no neighbour; 3 = an irregular edge ends at v; 2 = otherwise, a boundary edge ends at v;
+ *               1 = otherwise.
+ *   counts_dev[8] (u64, WRITTEN, always the full numbers): [0] CSR entries (= 2 E), [1] undirected edges E, [2] boundary edges,
+ *               [3] irregular edges, [4] vertices with a neighbour, [5] invalid triangles, [6] degenerate triangles, [7] vertices of
+ *               class 2 or 3.  For a mesh without degenerate triangles the Euler characteristic is [4] - [1] + (T - [5]).
+ * Nothing is written past neighbour_capacity; if [0] exceeds it the contents of neighbours_dev are unspecified, row_start_dev and
+ * vertex_class_dev are complete all the same.  Capacity 0 is valid (counts, rows and classes only); 6 T entries always suffice.
+ * row_start_dev [V + 1] and vertex_class_dev [V] may be NULL.  T == 0 or V == 0 is valid input.  Arrays of length 0 may be NULL.
+ * DF_E_INVALID: V > 2^32 - 1, 6 T > 2^32 - 1 (row offsets are 32-bit), triangles_dev NULL with T > 0, neighbours_dev NULL with a
+ * capacity > 0, counts_dev NULL, an output array (counts_dev included) that overlaps triangles_dev.  Without a device DF_E_NO_DEVICE.
+ * No device-to-host copy, no synchronisation, no floating-point atomics; every launch covers its range with 64-bit indices.  The
+ * time of the edges launch grows with the longest run of uses of ONE edge, which one lane counts.  Workspace, from the
+ * per-(device, stream) scratch of dfusion_extract_mesh (dfusion_release_scratch): 108 T + 4 V bytes (two copies of the 6 T 64-bit
+ * keys and of their value bytes; the positions reuse the first copy), + 4 (V + 1) if row_start_dev is NULL, and hipcub's sort and
+ * scan storage.                                                                                                                      */
+int dfusion_mesh_adjacency(const unsigned int *triangles_dev, unsigned long long n_triangles,
+                           unsigned long long n_vertices,
+                           unsigned int *row_start_dev /* nullable, n_vertices + 1 */,
+                           unsigned int *neighbours_dev, unsigned long long neighbour_capacity,
+                           unsigned char *vertex_class_dev /* nullable, n_vertices */,
+                           unsigned long long *counts_dev /* [8] */, dfStream stream);
+
+/* Taubin's lambda | mu smoothing of a mesh's vertices over that adjacency (no reference counterpart; additive, ABI 7).  Restated in
+ * tests/mesh_smooth_ref.py; every output equals it bit for bit (a NaN where it has a NaN).
+ * Inputs: V vertices of four floats (x, y, z, w), the CSR of dfusion_mesh_adjacency (row_start_dev [V + 1], neighbours_dev
+ * [n_neighbours = row_start[V]]), vertex_class_dev [V] or NULL (= every vertex with a neighbour is of class 1).
+ *   STEP       with a factor s, from a buffer P to another buffer Q, for every vertex v (a Jacobi step: no step reads what it writes).
+ *              v is MOVABLE iff its degree d > 0 and -- with DF_SMOOTH_FIX_BOUNDARY -- its class is 1.  A vertex that is not movable
+ *              is copied, all 16 bytes.  For a movable one, per axis a: acc = 0.f; for each neighbour u in the row's order
+ *              acc = acc + P[u].a (f32 adds, one after the other); mean = acc / (float)d (IEEE f32 division); delta = mean - P[v].a;
+ *              Q[v].a = P[v].a + s * delta (a multiply, then an add: two roundings, no fma).  w is copied as it is.  NaN and inf
+ *              propagate as that arithmetic propagates them.
+ *   ITERATION  a step with lambda, then -- unless mu == 0 -- a step with mu on its result.  mu == 0 is plain Laplacian smoothing,
+ *              one step an iteration.  iterations == 0 copies the input.
+ * vertices_out_dev [V] may be vertices_dev itself (in place, through the scratch).  The neighbour indices and row offsets are
+ * TRUSTED, as dfusion_gather_rows trusts its index list: every entry of a row must be < V and row_start_dev ascending within
+ * n_neighbours.
+ * DF_E_INVALID: iterations < 0, lambda or mu not finite, a flag bit other than DF_SMOOTH_FIX_BOUNDARY, V or n_neighbours > 2^32 - 1,
+ * a NULL array (vertex_class_dev apart) with a non-zero length, vertices_out_dev overlapping an input other than by being
+ * vertices_dev.  Without a device DF_E_NO_DEVICE.  No device-to-host copy, no synchronisation, no atomics.  Workspace, from the same
+ * scratch: 16 V bytes (none for a single step out of place).                                                                        */
+#define DF_SMOOTH_FIX_BOUNDARY 1u
+int dfusion_mesh_smooth(const float *vertices_dev, unsigned long long n_vertices,
+                        const unsigned int *row_start_dev /* n_vertices + 1 */,
+                        const unsigned int *neighbours_dev, unsigned long long n_neighbours,
+                        const unsigned char *vertex_class_dev /* nullable, n_vertices */,
+                        int iterations, float lambda, float mu, unsigned int flags,
+                        float *vertices_out_dev, dfStream stream);
+
 /* ---- colour volume (no reference counterpart: KinFu::operator() drops its colour image; additive, ABI 7) ----------------------
  * A colour volume belongs to a TSDF volume: the same dims, linear layout (x + y X + z X Y) and stored planes (DfSlab), 4 bytes a
  * voxel {c0, c1, c2, w}: three channels in the byte order of the input image (the kernels treat them alike) and a weight byte;
