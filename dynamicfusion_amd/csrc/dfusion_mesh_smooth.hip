@@ -4,12 +4,8 @@
 // every output is compared for equality.  The adjacency is decided by integers alone (a sort, a scan for the positions, integer
 // atomicMax and counts); a smoothing step is a function of its input buffer alone, its f32 operations in one stated order.
 //
-//   emit      one lane per triangle: six 2k-bit keys (src << k | dst), k the bits of V -- each half-edge a -> b with a != b as (a, b)
-//             with the value 0 and as (b, a) with the value 1; every other place of the six holds the all-ones key, whose src no vertex
-//             has.  Invalid and degenerate triangles counted
-//   sort      one hipcub::DeviceRadixSort::SortPairs over the 2k bits
-//   heads     a flag of 1 on the first key of every run of equal keys but the all-ones one; one hipcub exclusive sum, in place, with a
-//             spare element for the total: the position of every CSR entry
+//   emit, sort, heads   dfusion_mesh_uses.h: the directed uses of every edge as sorted 2k-bit keys (src << k | dst) with a direction
+//             byte, and the position of every run of equal keys -- the position of every CSR entry
 //   edges     one lane per sorted key: a run head writes its dst at its position; the head of a run with src < dst counts the values
 //             of its run (f zeros, b ones), classifies the edge and raises the classes of its two ends by integer atomicMax
 //   rows      one lane per v in 0 .. V: a binary search for the first key with src >= v; row_start[v] is that key's position
@@ -17,75 +13,12 @@
 //             boundary or irregular edge counted
 //   step      one lane per vertex: dfusion_mesh_smooth's hot path, run 2 x iterations times (below)
 // Every grid is capped at DF_MSM_MAX_BLOCKS workgroups (524 288 lanes) and strides over its range with 64-bit indices.
-#include <hipcub/hipcub.hpp>
-#include "dfusion_internal.h"
+#include "dfusion_mesh_uses.h"                        // emit, sort, heads and the scan: shared with dfusion_mesh_boundary_loops
 #include <math.h>
 
 #pragma clang fp contract(off)                       // p + s * delta is a multiply, then an add (the library's -ffp-contract=off, kept for this file)
 
-#define DF_MSM_MAX_BLOCKS 2048u
 #define DF_MSM_GATHER 8                              // neighbour positions in flight per lane
-
-static inline unsigned df_msm_blocks(size_t n) { const size_t b = (n + 255) / 256; return (unsigned)(b < DF_MSM_MAX_BLOCKS ? b : DF_MSM_MAX_BLOCKS); }
-
-struct DfMsmArgs {
-    const uint32_t* tris; size_t T; size_t V; size_t N;      // N = 6 T keys
-    int k;                                                   // bits of V: every index < V fits, and 2^k - 1 is no vertex
-    unsigned long long *keys_in, *keys;                      // [N] as emitted, sorted
-    uint8_t *dir_in, *dir;                                   // [N] 0: the half-edge src -> dst exists, 1: its reverse does
-    uint32_t* pos;                                           // [N + 1] head flags, then their exclusive sum (over keys_in, dead after the sort)
-    uint32_t* cls;                                           // [V] 0, raised to 2 (boundary) or 3 (irregular)
-    uint32_t* row_start;                                     // [V + 1] the caller's, or workspace
-    uint32_t* nbr; unsigned long long cap;
-    uint8_t* vclass;
-    unsigned long long* counts;
-};
-
-__device__ __forceinline__ void msm_count(unsigned long long* counts, int which, unsigned long long wave_uniform)
-{
-    if ((threadIdx.x & 63) == 0 && wave_uniform) atomicAdd(&counts[which], wave_uniform);
-}
-
-__global__ __launch_bounds__(256) void df_msm_emit_kernel(const DfMsmArgs a)
-{
-    const unsigned long long none = a.k == 32 ? ~0ull : (1ull << (2 * a.k)) - 1ull;
-    unsigned long long n_invalid = 0ull, n_degenerate = 0ull;           // wave-uniform
-    for (size_t t0 = (size_t)blockIdx.x * 256; t0 < a.T; t0 += (size_t)gridDim.x * 256) {      // (workgroup-uniform trip count)
-        const size_t t = t0 + threadIdx.x;
-        bool invalid = false, degenerate = false;
-        if (t < a.T) {
-            const uint32_t i[3] = {a.tris[3 * t], a.tris[3 * t + 1], a.tris[3 * t + 2]};
-            invalid = !((size_t)i[0] < a.V && (size_t)i[1] < a.V && (size_t)i[2] < a.V);       // tested before anything is indexed
-            degenerate = !invalid && (i[0] == i[1] || i[1] == i[2] || i[0] == i[2]);
-#pragma unroll
-            for (int e = 0; e < 3; ++e) {
-                const unsigned long long s = i[e], d = i[e == 2 ? 0 : e + 1];
-                const bool live = !invalid && s != d;
-                a.keys_in[6 * t + 2 * e] = live ? (s << a.k | d) : none;
-                a.keys_in[6 * t + 2 * e + 1] = live ? (d << a.k | s) : none;
-                a.dir_in[6 * t + 2 * e] = 0;
-                a.dir_in[6 * t + 2 * e + 1] = 1;
-            }
-        }
-        n_invalid += (unsigned long long)__popcll(__ballot(invalid));
-        n_degenerate += (unsigned long long)__popcll(__ballot(degenerate));
-    }
-    msm_count(a.counts, 5, n_invalid);
-    msm_count(a.counts, 6, n_degenerate);
-}
-
-__global__ __launch_bounds__(256) void df_msm_heads_kernel(const DfMsmArgs a)
-{
-    const unsigned long long none = a.k == 32 ? ~0ull : (1ull << (2 * a.k)) - 1ull;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i <= a.N; i += (size_t)gridDim.x * 256) {
-        uint32_t head = 0u;
-        if (i < a.N) {
-            const unsigned long long key = a.keys[i];
-            head = key != none && (i == 0 || a.keys[i - 1] != key) ? 1u : 0u;
-        }
-        a.pos[i] = head;
-    }
-}
 
 __global__ __launch_bounds__(256) void df_msm_edges_kernel(const DfMsmArgs a)
 {
@@ -159,13 +92,6 @@ __global__ void df_msm_set_kernel(unsigned long long* dst, unsigned long long va
     if (threadIdx.x == 0 && blockIdx.x == 0) *dst = value;
 }
 
-static inline bool msm_overlap(const void* p, size_t pn, const void* q, size_t qn)
-{
-    if (!p || !q || !pn || !qn) return false;
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + qn && b < a + pn;
-}
-
 extern "C" int dfusion_mesh_adjacency(const unsigned int* triangles_dev, unsigned long long n_triangles, unsigned long long n_vertices,
                                       unsigned int* row_start_dev, unsigned int* neighbours_dev, unsigned long long neighbour_capacity,
                                       unsigned char* vertex_class_dev, unsigned long long* counts_dev, dfStream stream)
@@ -190,36 +116,23 @@ extern "C" int dfusion_mesh_adjacency(const unsigned int* triangles_dev, unsigne
     DfMsmArgs a;
     memset(&a, 0, sizeof(a));
     a.tris = triangles_dev; a.T = T; a.V = V; a.N = N;
-    a.k = 1;
-    while (a.k < 32 && (V >> a.k)) ++a.k;                                 // 2^k > V
+    a.k = df_msm_key_bits(V);                                             // 2^k > V
     a.nbr = neighbours_dev; a.cap = neighbour_capacity; a.vclass = vertex_class_dev; a.counts = counts_dev;
-    size_t sort_bytes = 0, scan_bytes = 0;
-    DF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                              (const uint8_t*)nullptr, (uint8_t*)nullptr, N, 0, 2 * a.k, st));
-    DF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, N + 1, st));
-    size_t cub_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-    // workspace: [keys as emitted 48 T, then the positions 24 T + 4 over them] [sorted keys 48 T] [values 6 T] [sorted values 6 T]
-    //            [raised classes 4 V, zeroed] [row_start 4 (V + 1), unless the caller gives one] [hipcub's storage]
+    a.slot_invalid = 5; a.slot_degenerate = 6;
+    size_t cub_bytes = 0;
+    DF_TRY(df_msm_uses_cub_bytes(N, a.k, N + 1, st, &cub_bytes));
+    // workspace: [the sorted uses' 108 T (dfusion_mesh_uses.h)] [raised classes 4 V, zeroed] [row_start 4 (V + 1), unless the caller
+    //            gives one] [hipcub's storage]
     auto up = [](size_t b) { return (b + 15) / 16 * 16; };
-    const size_t o_keys_in = 0, o_keys = o_keys_in + up(N * 8), o_dir_in = o_keys + up(N * 8), o_dir = o_dir_in + up(N), o_cls = o_dir + up(N),
-                 o_rows = o_cls + up(V * 4), o_cub = (o_rows + (row_start_dev ? 0 : up((V + 1) * 4)) + 255) / 256 * 256;
+    const size_t o_cls = df_msm_uses_bytes(N), o_rows = o_cls + up(V * 4), o_cub = (o_rows + (row_start_dev ? 0 : up((V + 1) * 4)) + 255) / 256 * 256;
     DfScratchHold hold(st, o_cub + cub_bytes);                            // held until the last launch is enqueued
     if (!hold.entry) return (int)hipErrorOutOfMemory;
     char* const ws = hold.mem;
-    a.keys_in = (unsigned long long*)(ws + o_keys_in); a.keys = (unsigned long long*)(ws + o_keys);
-    a.dir_in = (uint8_t*)(ws + o_dir_in); a.dir = (uint8_t*)(ws + o_dir);
-    a.pos = (uint32_t*)(ws + o_keys_in);                                  // 4 (N + 1) <= 8 N
     a.cls = (uint32_t*)(ws + o_cls);
     a.row_start = row_start_dev ? row_start_dev : (uint32_t*)(ws + o_rows);
     DF_HIP(hipMemsetAsync(a.cls, 0, V * 4, st));
-    const dim3 gt(df_msm_blocks(T)), gn(df_msm_blocks(N + 1)), gv(df_msm_blocks(V + 1)), wg(256);
-    hipLaunchKernelGGL(df_msm_emit_kernel, gt, wg, 0, st, a);
-    DF_LAUNCH_CHECK();
-    DF_HIP(hipcub::DeviceRadixSort::SortPairs(ws + o_cub, cub_bytes, (const unsigned long long*)a.keys_in, a.keys, (const uint8_t*)a.dir_in, a.dir,
-                                              N, 0, 2 * a.k, st));
-    hipLaunchKernelGGL(df_msm_heads_kernel, gn, wg, 0, st, a);
-    DF_LAUNCH_CHECK();
-    DF_HIP(hipcub::DeviceScan::ExclusiveSum(ws + o_cub, cub_bytes, a.pos, a.pos, N + 1, st));
+    DF_TRY(df_msm_sorted_uses(a, ws, ws + o_cub, cub_bytes, st));
+    const dim3 gn(df_msm_blocks(N + 1)), gv(df_msm_blocks(V + 1)), wg(256);
     hipLaunchKernelGGL(df_msm_edges_kernel, gn, wg, 0, st, a);
     DF_LAUNCH_CHECK();
     hipLaunchKernelGGL(df_msm_rows_kernel, gv, wg, 0, st, a);

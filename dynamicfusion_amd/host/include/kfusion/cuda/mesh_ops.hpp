@@ -2,7 +2,8 @@
 // mesh and the mesh without its small pieces (no reference counterpart).  Forward to dfusion_mesh_components / dfusion_mesh_filter /
 // dfusion_gather_rows of include/dfusion.h, where the rule is stated; no kernels of their own.  simplifyMesh: the mesh simplified by
 // vertex clustering (dfusion_mesh_simplify).  meshAdjacency / smoothMesh: the vertex adjacency with the edge statistics and Taubin
-// smoothing over it (dfusion_mesh_adjacency / dfusion_mesh_smooth).  Same calls as the Python mirror
+// smoothing over it (dfusion_mesh_adjacency / dfusion_mesh_smooth).  boundaryLoops / fillHoles: the closed loops of boundary half-edges
+// and the mesh with the small ones filled (dfusion_mesh_boundary_loops / dfusion_mesh_fill_holes).  Same calls as the Python mirror
 // (dynamicfusion_amd.mesh_ops).
 #pragma once
 #include <kfusion/types.hpp>
@@ -52,5 +53,22 @@ void smoothMesh(const DeviceArray<Point>& vertices, const DeviceArray<int>& row_
 /// The same, building the adjacency of `triangles` first.
 void smoothMesh(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, int iterations, float lambda, float mu, unsigned int flags,
                 DeviceArray<Point>& out_vertices);
+
+/// The closed loops of boundary half-edges of a mesh over n_vertices vertices: vertex_next[v] = the head of a simple vertex's one
+/// outgoing boundary half-edge, vertex_loop[v] = the smallest vertex index of v's loop, vertex_rank[v] = its steps from there
+/// (0xffffffff each where there is none); loop i holds loop_vertices[loop_start[i] .. loop_start[i + 1]), from its label vertex along
+/// next, the loops in ascending label; counts (optional): the call's 8 counts -- loops, vertices on loops, boundary half-edges, other
+/// boundary vertices, simple vertices on open chains, the longest loop, invalid and degenerate triangles.  One call with capacities of
+/// V, trimmed from one read-back of the counts.
+void boundaryLoops(const DeviceArray<int>& triangles, size_t n_vertices, DeviceArray<int>& vertex_next, DeviceArray<int>& vertex_loop,
+                   DeviceArray<int>& vertex_rank, DeviceArray<int>& loop_start, DeviceArray<int>& loop_vertices,
+                   DeviceArray<unsigned long long>* counts = nullptr);
+
+/// The mesh with every boundary loop of at most max_edges edges closed by a fan around a new vertex at its centroid: the old vertices
+/// and triangles as they are, then one vertex per filled loop and its L triangles, in ascending label.  vertex_src[i] = i for an old
+/// vertex, 0xffffffff for a new one (it has no source row); counts (optional): the call's 8 counts.  Every array is sized exactly (a
+/// count-only call whose counts are read back, then one of that size).
+void fillHoles(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, unsigned int max_edges, DeviceArray<Point>& out_vertices,
+               DeviceArray<int>& out_triangles, DeviceArray<int>& vertex_src, DeviceArray<unsigned long long>* counts = nullptr);
 
 } }

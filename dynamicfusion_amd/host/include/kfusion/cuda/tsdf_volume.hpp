@@ -107,6 +107,10 @@ public:
     // and, after both, smoothed by smooth_iterations lambda | mu iterations with the boundary fixed (kfusion/cuda/mesh_ops.hpp smoothMesh); 0: the call above
     void fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& triangles, unsigned long long min_component_triangles, bool keep_largest, float simplify_cell,
                    int smooth_iterations, float smooth_lambda = 0.5f, float smooth_mu = -0.53f) const;
+    // and, after the filter and the simplification and before the smoothing, with every boundary loop of at most fill_holes_max_edges edges
+    // closed by a fan around its centroid (kfusion/cuda/mesh_ops.hpp fillHoles); 0: the call above
+    void fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& triangles, unsigned long long min_component_triangles, bool keep_largest, float simplify_cell,
+                   int smooth_iterations, float smooth_lambda, float smooth_mu, unsigned int fill_holes_max_edges) const;
     void compute_points();
     void compute_normals();
 #ifdef KFUSION_USE_OPENCV

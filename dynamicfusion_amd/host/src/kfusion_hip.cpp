@@ -342,6 +342,21 @@ void TsdfVolume::fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& trian
     smoothMesh(vertices, triangles, smooth_iterations, smooth_lambda, smooth_mu, DF_SMOOTH_FIX_BOUNDARY, vertices);
 }
 
+void TsdfVolume::fetchMesh(DeviceArray<Point>& vertices, DeviceArray<int>& triangles, unsigned long long min_component_triangles, bool keep_largest,
+                           float simplify_cell, int smooth_iterations, float smooth_lambda, float smooth_mu, unsigned int fill_holes_max_edges) const
+{
+    if (!fill_holes_max_edges) {
+        fetchMesh(vertices, triangles, min_component_triangles, keep_largest, simplify_cell, smooth_iterations, smooth_lambda, smooth_mu);
+        return;
+    }
+    DeviceArray<Point> open_vertices; DeviceArray<int> open_triangles, vertex_src;
+    fetchMesh(open_vertices, open_triangles, min_component_triangles, keep_largest, simplify_cell);
+    if (open_vertices.size() == 0) { vertices = open_vertices; triangles = open_triangles; return; }
+    fillHoles(open_vertices, open_triangles, fill_holes_max_edges, vertices, triangles, vertex_src);
+    if (smooth_iterations != 0) smoothMesh(vertices, triangles, smooth_iterations, smooth_lambda, smooth_mu, DF_SMOOTH_FIX_BOUNDARY, vertices);
+    KF_HIP(hipStreamSynchronize(nullptr));                                // the open mesh is freed on return
+}
+
 // ------------------------------------------------------------------------------------------ mesh components (include/dfusion.h dfusion_mesh_*)
 void kfusion::cuda::meshComponents(const DeviceArray<int>& triangles, size_t n_vertices, DeviceArray<int>& vertex_label, DeviceArray<int>& triangle_count,
                                    DeviceArray<unsigned long long>* counts)
@@ -449,6 +464,54 @@ void kfusion::cuda::smoothMesh(const DeviceArray<Point>& vertices, const DeviceA
     meshAdjacency(triangles, vertices.size(), row_start, neighbours, vertex_class);
     smoothMesh(vertices, row_start, neighbours, vertex_class, iterations, lambda, mu, flags, out_vertices);
     KF_HIP(hipStreamSynchronize(nullptr));                                // the adjacency is freed on return
+}
+
+void kfusion::cuda::boundaryLoops(const DeviceArray<int>& triangles, size_t n_vertices, DeviceArray<int>& vertex_next, DeviceArray<int>& vertex_loop,
+                                  DeviceArray<int>& vertex_rank, DeviceArray<int>& loop_start, DeviceArray<int>& loop_vertices,
+                                  DeviceArray<unsigned long long>* counts_out)
+{
+    const size_t nt = triangles.size() / 3, nv = n_vertices;
+    DeviceArray<unsigned long long> own;
+    DeviceArray<unsigned long long>& counts = counts_out ? *counts_out : own;
+    counts.create(8);
+    vertex_next.create(nv); vertex_loop.create(nv); vertex_rank.create(nv);
+    DeviceArray<int> all_start, all_vertices;
+    all_start.create(nv + 1);
+    all_vertices.create(nv);
+    KF_HIP(hipMemsetAsync(all_start.ptr(), 0, 4, nullptr));               // no vertex: both capacities are 0 and the call leaves it alone
+    KF_DF(dfusion_mesh_boundary_loops(nt ? (const unsigned int*)triangles.ptr() : nullptr, nt, nv, nv ? (unsigned int*)vertex_next.ptr() : nullptr,
+                                      nv ? (unsigned int*)vertex_loop.ptr() : nullptr, nv ? (unsigned int*)vertex_rank.ptr() : nullptr,
+                                      (unsigned int*)all_start.ptr(), nv, nv ? (unsigned int*)all_vertices.ptr() : nullptr, nv, counts.ptr(), nullptr));
+    unsigned long long n[8];
+    counts.download(n);
+    loop_start.create((size_t)n[0] + 1);
+    loop_vertices.create((size_t)n[1]);
+    KF_HIP(hipMemcpyAsync(loop_start.ptr(), all_start.ptr(), ((size_t)n[0] + 1) * sizeof(int), hipMemcpyDeviceToDevice, nullptr));
+    if (n[1]) KF_HIP(hipMemcpyAsync(loop_vertices.ptr(), all_vertices.ptr(), (size_t)n[1] * sizeof(int), hipMemcpyDeviceToDevice, nullptr));
+    KF_HIP(hipStreamSynchronize(nullptr));                                // the full-size arrays are freed on return
+}
+
+void kfusion::cuda::fillHoles(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, unsigned int max_edges,
+                              DeviceArray<Point>& out_vertices, DeviceArray<int>& out_triangles, DeviceArray<int>& vertex_src,
+                              DeviceArray<unsigned long long>* counts_out)
+{
+    const size_t nv = vertices.size(), nt = triangles.size() / 3;
+    DeviceArray<unsigned long long> own;
+    DeviceArray<unsigned long long>& counts = counts_out ? *counts_out : own;
+    counts.create(8);
+    auto run = [&](float* v_out, unsigned int* src, unsigned long long vcap, unsigned int* tri_out, unsigned long long tcap) {
+        KF_DF(dfusion_mesh_fill_holes(nv ? (const float*)vertices.ptr() : nullptr, nv, nt ? (const unsigned int*)triangles.ptr() : nullptr, nt, max_edges, 0u,
+                                      v_out, vcap, tri_out, tcap, src, counts.ptr(), nullptr));
+    };
+    run(nullptr, nullptr, 0, nullptr, 0);
+    unsigned long long n[8];
+    counts.download(n);
+    out_vertices.create((size_t)n[0]);
+    vertex_src.create((size_t)n[0]);
+    out_triangles.create((size_t)n[1] * 3);
+    if (n[0] || n[1])
+        run(n[0] ? (float*)out_vertices.ptr() : nullptr, n[0] ? (unsigned int*)vertex_src.ptr() : nullptr, n[0],
+            n[1] ? (unsigned int*)out_triangles.ptr() : nullptr, n[1]);
 }
 
 // ------------------------------------------------------------------------------------------ ColorVolume (include/dfusion.h dfusion_color_*)

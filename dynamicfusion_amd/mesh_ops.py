@@ -1,7 +1,8 @@
 """Operations on an indexed triangle mesh (fetchMesh's, or any) over the C-ABI: its connected components and the mesh without its small
 pieces (include/dfusion.h dfusion_mesh_components / dfusion_mesh_filter / dfusion_gather_rows, where the rule is stated), and the mesh
 simplified by vertex clustering (dfusion_mesh_simplify), its vertex adjacency with the edge statistics (dfusion_mesh_adjacency) and Taubin
-smoothing over it (dfusion_mesh_smooth).  Device tensors in, device tensors out; all compute is in libdfusion_hip.so."""
+smoothing over it (dfusion_mesh_smooth), its closed boundary loops (dfusion_mesh_boundary_loops) and the mesh with the small ones
+filled (dfusion_mesh_fill_holes).  Device tensors in, device tensors out; all compute is in libdfusion_hip.so."""
 import torch
 
 from . import capi
@@ -151,6 +152,68 @@ def mesh_topology(triangles, n_vertices):
     out = dict(zip(TOPOLOGY_NAMES, (int(c) for c in counts.tolist())))
     out["euler"] = out["used_vertices"] - out["edges"] + (nt - out["invalid_triangles"])
     return out
+
+
+LOOP_COUNT_NAMES = ("loops", "loop_vertices", "boundary_half_edges", "other_boundary_vertices", "chain_vertices", "longest_loop",
+                    "invalid_triangles", "degenerate_triangles")
+FILL_COUNT_NAMES = ("vertices", "triangles", "loops_filled", "loops_open", "triangles_added", "longest_filled", "longest_open", "chain_vertices")
+
+
+def boundary_loops(triangles, n_vertices, return_counts=False):
+    """The closed loops of boundary half-edges of an indexed mesh (include/dfusion.h dfusion_mesh_boundary_loops has the rule): triangles
+    int32 [T, 3] (uint32 bits) over n_vertices vertices -> (vertex_next int32 [V]: the head of a simple vertex's one outgoing boundary
+    half-edge, vertex_loop int32 [V]: the smallest vertex index of the vertex's loop, vertex_rank int32 [V]: its steps from there --
+    0xffffffff each where there is none --, loop_start int32 [loops + 1], loop_vertices int32 [loop_start[-1]]: the loops in ascending
+    label, each from its label vertex along next; uint32 bits all); with return_counts also counts int64 [8] (LOOP_COUNT_NAMES).  One
+    call with capacities of V, trimmed from one read-back of the counts."""
+    tp, nt = _triangles(triangles)
+    nv = int(n_vertices)
+    dev = triangles.device
+    nxt = torch.empty(nv, dtype=torch.int32, device=dev)
+    loop = torch.empty(nv, dtype=torch.int32, device=dev)
+    rank = torch.empty(nv, dtype=torch.int32, device=dev)
+    start = torch.zeros(nv + 1, dtype=torch.int32, device=dev)
+    members = torch.empty(nv, dtype=torch.int32, device=dev)
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    capi.check(capi.lib().dfusion_mesh_boundary_loops(tp, nt, nv, _flat(nxt) if nv else None, _flat(loop) if nv else None, _flat(rank) if nv else None,
+                                                      _flat(start), nv, _flat(members) if nv else None, nv, _flat(counts), _stream()),
+               "dfusion_mesh_boundary_loops")
+    n_loops, n_members = (int(c) for c in counts[:2].tolist())
+    start, members = start[:n_loops + 1], members[:n_members]
+    return (nxt, loop, rank, start, members, counts) if return_counts else (nxt, loop, rank, start, members)
+
+
+def fill_holes(vertices, triangles, max_edges, return_counts=False):
+    """The mesh with every boundary loop of at most max_edges edges closed by a fan around its centroid (include/dfusion.h
+    dfusion_mesh_fill_holes has the rule).  vertices float32 [V, 4], triangles int32 [T, 3] (uint32 bits) -> (vertices float32 [V + F, 4]:
+    the old ones as they are, then one per filled loop, triangles int32 [T + A, 3]: the old ones, then the fans, vertex_src int32
+    [V + F]: i for an old vertex, 0xffffffff for a new one, which has no source row); with return_counts also counts int64 [8]
+    (FILL_COUNT_NAMES).  One count-only call, then one of exactly that size (the counts are read back)."""
+    tp, nt = _triangles(triangles)
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 4 or not vertices.is_contiguous():
+        raise ValueError("vertices %s %s, expected contiguous float32 [V, 4]" % (vertices.dtype, tuple(vertices.shape)))
+    if vertices.device != triangles.device:
+        raise ValueError("vertices on %s, triangles on %s" % (vertices.device, triangles.device))
+    if not 0 <= int(max_edges) <= 0xffffffff:
+        raise ValueError("max_edges %r, expected 0 .. 2^32 - 1" % (max_edges,))
+    nv = int(vertices.shape[0])
+    dev = triangles.device
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    L = capi.lib()
+
+    def run(out_v, n_v, out_t, n_t, src):
+        capi.check(L.dfusion_mesh_fill_holes(_flat(vertices) if nv else None, nv, tp, nt, int(max_edges), 0, _flat(out_v) if n_v else None, n_v,
+                                             _flat(out_t) if n_t else None, n_t, _flat(src) if n_v else None, _flat(counts), _stream()),
+                   "dfusion_mesh_fill_holes")
+
+    run(None, 0, None, 0, None)
+    kv, kt = (int(c) for c in counts[:2].tolist())
+    out_v = torch.empty((kv, 4), dtype=torch.float32, device=dev)
+    out_t = torch.empty((kt, 3), dtype=torch.int32, device=dev)
+    src = torch.empty(kv, dtype=torch.int32, device=dev)
+    if kv or kt:
+        run(out_v, kv, out_t, kt, src)
+    return (out_v, out_t, src, counts) if return_counts else (out_v, out_t, src)
 
 
 def smooth_mesh(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, fix_boundary=True, adjacency=None):

@@ -386,7 +386,7 @@ class TsdfVolume:
 
     # ---- no reference counterpart: the surface as a triangle mesh (include/dfusion.h dfusion_extract_mesh)
     def fetchMesh(self, with_normals=False, min_component_triangles=0, keep_largest=False, simplify_cell=0.0, smooth_iterations=0, smooth_lambda=0.5,
-                  smooth_mu=-0.53):
+                  smooth_mu=-0.53, fill_holes_max_edges=0):
         """-> (vertices float32 [n, 4], triangles int32 [m, 3] (uint32 bits)) device tensors, in the rule's order; with_normals: also
         fetchNormals(vertices).  One count-only call, then one of exactly that size; the counts stay in last_mesh_counts_.
         min_component_triangles / keep_largest: the mesh goes through mesh_ops.remove_small_components first (the connected pieces of
@@ -394,7 +394,11 @@ class TsdfVolume:
         kept vertices only).  simplify_cell > 0: the mesh -- after the component filter -- is simplified by vertex clustering at that cell
         size (mesh_ops.simplify_mesh); the normals are fetched for the new vertices.  smooth_iterations > 0: the vertices -- after both --
         go through that many lambda | mu iterations of mesh_ops.smooth_mesh (boundary vertices fixed); the normals are fetched at the
-        smoothed positions.  At their defaults nothing but the calls above runs."""
+        smoothed positions.  fill_holes_max_edges > 0: after the component filter and the simplification and before the smoothing, every
+        boundary loop of at most that many edges is closed by a fan around its centroid (mesh_ops.fill_holes), so a closed-up rim is no
+        longer frozen by the smoothing.  A fan's centre is a new vertex without a source row: its normal is whatever fetchNormals gives at
+        its position, and a colour for it comes from ColorVolume.fetchColors at its position.  At their defaults nothing but the calls
+        above runs."""
         aff = capi.floats(aff12(self.pose_))
         counts = torch.empty(2, dtype=torch.int64, device=self.device)
         capi.check(capi.lib().dfusion_extract_mesh(self.c_volume(), self.c_slab(), aff, None, 0, None, 0, _ptr(counts), _stream()),
@@ -417,6 +421,9 @@ class TsdfVolume:
             vertices, triangles, _, _ = simplify_mesh(vertices, triangles, simplify_cell)
             if with_normals and not vertices.shape[0]:
                 return vertices, triangles, torch.empty((0, 4), dtype=torch.float32, device=self.device)
+        if fill_holes_max_edges and vertices.shape[0]:
+            from .mesh_ops import fill_holes
+            vertices, triangles, _ = fill_holes(vertices, triangles, fill_holes_max_edges)
         if smooth_iterations and vertices.shape[0]:
             from .mesh_ops import smooth_mesh
             vertices = smooth_mesh(vertices, triangles, smooth_iterations, smooth_lambda, smooth_mu)

@@ -451,6 +451,84 @@ int dfusion_mesh_smooth(const float *vertices_dev, unsigned long long n_vertices
                         int iterations, float lambda, float mu, unsigned int flags,
                         float *vertices_out_dev, dfStream stream);
 
+/* The closed loops of boundary half-edges of an indexed triangle mesh (no reference counterpart; additive, ABI 7).  DESIGN.md section
+ * 27 has the kernels; tests/mesh_holes_ref.py restates the rule in numpy and every output equals it bit for bit.
+ * Inputs: T triangles of three uint32 indices over V vertices (the positions take no part).  VALID, HALF-EDGES and the EDGE classes
+ * are dfusion_mesh_adjacency's, word for word.
+ *   BOUNDARY HALF-EDGE  a half-edge a -> b whose undirected edge is BOUNDARY (f + b == 1).  out(v) and in(v) count those that leave
+ *               and enter v.
+ *   SIMPLE      v is simple iff out(v) == 1, in(v) == 1 and no IRREGULAR edge ends at v.  Every simple vertex has adjacency class 2;
+ *               the reverse does not hold (a vertex where two sheets touch has out == in == 2).
+ *   next(v)     of a simple v: the head of its one outgoing boundary half-edge.
+ *   LOOP        a simple v is on a loop iff following next from v comes back to v having met only simple vertices.  Every simple
+ *               vertex has in == 1, so next is injective on the simple vertices: a walk either closes or ends at a vertex that is not
+ *               simple.  Simple vertices whose walk ends are on an OPEN CHAIN and belong to no loop.
+ *   LABEL       of a loop: its smallest vertex index.  rank(v) = the number of next steps from the label vertex to v; the loop's
+ *               LENGTH L = its vertex count.  L >= 3 always: next(v) != v because a half-edge has different ends, and L == 2 would be
+ *               the half-edges a -> b and b -> a, which make the edge {a, b} INTERIOR, not BOUNDARY.
+ *   Loops are numbered in ascending label.
+ *   vertex_next_dev[v] (nullable)  next(v), or 0xffffffff for a v that is not simple.
+ *   vertex_loop_dev[v]             the label of v's loop, or 0xffffffff.
+ *   vertex_rank_dev[v] (nullable)  rank(v), or 0xffffffff.
+ *   loop_start_dev [loop_capacity + 1], loop_vertices_dev [vertex_capacity]: a CSR of the loops -- loop number i holds
+ *               loop_vertices_dev[loop_start_dev[i] .. loop_start_dev[i + 1]), starting at its label vertex and following next.
+ *   counts_dev[8] (u64, WRITTEN, always the full numbers): [0] loops, [1] vertices on loops, [2] boundary half-edges (=
+ *               dfusion_mesh_adjacency's counts[2]), [3] vertices that are not simple and have out + in > 0, [4] simple vertices on
+ *               open chains, [5] the longest loop's length, [6] invalid triangles, [7] degenerate triangles.
+ * Nothing is written past a capacity; if [0] exceeds loop_capacity or [1] vertex_capacity the contents of the two CSR arrays are
+ * unspecified, the per-vertex arrays and the counts are complete all the same (dfusion_mesh_filter's contract).  Both capacities 0:
+ * per-vertex arrays and counts only (neither CSR array is touched).  T == 0 or V == 0 is valid input.  Arrays of length 0 may be NULL.
+ * DF_E_INVALID: V > 2^32 - 1, 6 T > 2^32 - 1, a capacity > 2^32 - 1, triangles_dev NULL with T > 0, vertex_loop_dev NULL with V > 0,
+ * loop_start_dev NULL unless both capacities are 0, loop_vertices_dev NULL with vertex_capacity > 0, counts_dev NULL, an output array
+ * (counts_dev included) that overlaps triangles_dev.  Without a device DF_E_NO_DEVICE.  No device-to-host copy, no synchronisation,
+ * integer atomics only (no output depends on scheduling); every launch covers its range with 64-bit indices.  Labels and ranks come
+ * from ceil(log2 V) pointer-doubling rounds between two buffers, each a launch over V.  As in dfusion_mesh_adjacency the time of the
+ * runs launch grows with the longest run of uses of ONE edge.  Workspace, from the per-(device, stream) scratch of
+ * dfusion_extract_mesh (dfusion_release_scratch): 108 T + 76 V bytes and hipcub's sort and scan storage.                              */
+int dfusion_mesh_boundary_loops(const unsigned int *triangles_dev, unsigned long long n_triangles,
+                                unsigned long long n_vertices,
+                                unsigned int *vertex_next_dev /* nullable, n_vertices */,
+                                unsigned int *vertex_loop_dev /* n_vertices */,
+                                unsigned int *vertex_rank_dev /* nullable, n_vertices */,
+                                unsigned int *loop_start_dev /* loop_capacity + 1 */,
+                                unsigned long long loop_capacity,
+                                unsigned int *loop_vertices_dev, unsigned long long vertex_capacity,
+                                unsigned long long *counts_dev /* [8] */, dfStream stream);
+
+/* The mesh with its small holes closed: every loop of dfusion_mesh_boundary_loops of at most max_edges edges gets a fan of triangles
+ * around a new vertex at its centroid (no reference counterpart; additive, ABI 7).  Restated in tests/mesh_holes_ref.py; every output
+ * equals it bit for bit (a NaN where it has a NaN).
+ * Inputs: V vertices of four floats (x, y, z, w), T triangles of three uint32 indices, max_edges, flags (none defined).
+ *   FILLED     a loop is filled iff L <= max_edges.  max_edges of 0 to 2 fills nothing (L >= 3) and the mesh is copied.
+ *   VERTICES   the V input vertices as they are (16 bytes each), then one new vertex m per filled loop, in ascending label.
+ *   TRIANGLES  the T input triangles as they are, invalid ones included, then per filled loop in ascending label L triangles:
+ *              triangle j is (v_(j+1) mod L, v_j, m), v_j the loop's vertex of rank j.  Every old boundary edge v_j -> v_(j+1) gets
+ *              its opposite half-edge, and each spoke {v_j, m} is used once each way.
+ *   POSITION   of m, per axis a: acc = 0.f; for j = 0 .. L-1 in rank order acc = acc + P[v_j].a (f32 adds, one after the other);
+ *              m.a = acc / (float)L (IEEE f32 division); w = 0.f.  NaN and inf propagate as that arithmetic propagates them.
+ *   vertex_src_dev[i] (nullable, vertex_capacity)  i for i < V, 0xffffffff for a new vertex: it has no source row.
+ *   counts_dev[8] (u64, WRITTEN, always the full numbers): [0] output vertices, [1] output triangles, [2] loops filled, [3] loops
+ *              left open, [4] triangles added, [5] the longest filled loop, [6] the longest loop left open (0 if none), [7] simple
+ *              vertices on open chains.
+ * Boundary edges fall by the sum of the filled L, irregular edges are unchanged, the Euler characteristic rises by one per filled
+ * loop, and filling the result again with the same max_edges adds nothing.  New indices are 32-bit: V + [2] must stay below 2^32 - 1.
+ * The input triangles go across as they are: an INVALID one that names an index in V .. V + [2] - 1 is a valid triangle on a new
+ * vertex in the output, and the four statements above are made for meshes without such a triangle.
+ * Nothing is written past a capacity; if a count exceeds its capacity the contents of the output arrays are unspecified
+ * (dfusion_mesh_filter's contract).  Both capacities 0: counts only.  T == 0 or V == 0 is valid input: the mesh is copied.
+ * DF_E_INVALID: a flag bit, V > 2^32 - 1, 6 T > 2^32 - 1, a capacity > 2^32 - 1, a NULL input or output array with a non-zero size
+ * or capacity, counts_dev NULL, an output array (counts_dev included) that overlaps vertices_dev or triangles_dev.  Without a device
+ * DF_E_NO_DEVICE.  No device-to-host copy, no synchronisation, integer atomics only.  The loop stage runs inside the call, through
+ * the same scratch (dfusion_mesh_boundary_loops' workspace); the old arrays go across as device-to-device copies.  ONE lane walks a
+ * filled loop for its centroid, L <= max_edges dependent loads: the time of that launch grows with max_edges.                        */
+int dfusion_mesh_fill_holes(const float *vertices_dev, unsigned long long n_vertices,
+                            const unsigned int *triangles_dev, unsigned long long n_triangles,
+                            unsigned int max_edges, unsigned int flags,
+                            float *vertices_out_dev, unsigned long long vertex_capacity,
+                            unsigned int *triangles_out_dev, unsigned long long triangle_capacity,
+                            unsigned int *vertex_src_dev /* nullable, vertex_capacity */,
+                            unsigned long long *counts_dev /* [8] */, dfStream stream);
+
 /* ---- colour volume (no reference counterpart: KinFu::operator() drops its colour image; additive, ABI 7) ----------------------
  * A colour volume belongs to a TSDF volume: the same dims, linear layout (x + y X + z X Y) and stored planes (DfSlab), 4 bytes a
  * voxel {c0, c1, c2, w}: three channels in the byte order of the input image (the kernels treat them alike) and a weight byte;
