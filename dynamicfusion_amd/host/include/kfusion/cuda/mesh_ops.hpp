@@ -3,7 +3,8 @@
 // dfusion_gather_rows of include/dfusion.h, where the rule is stated; no kernels of their own.  simplifyMesh: the mesh simplified by
 // vertex clustering (dfusion_mesh_simplify).  meshAdjacency / smoothMesh: the vertex adjacency with the edge statistics and Taubin
 // smoothing over it (dfusion_mesh_adjacency / dfusion_mesh_smooth).  boundaryLoops / fillHoles: the closed loops of boundary half-edges
-// and the mesh with the small ones filled (dfusion_mesh_boundary_loops / dfusion_mesh_fill_holes).  Same calls as the Python mirror
+// and the mesh with the small ones filled (dfusion_mesh_boundary_loops / dfusion_mesh_fill_holes).  closestPoints / meshDistance: the
+// closest point of a mesh to every query point and the distances between two meshes (dfusion_mesh_closest_points).  Same calls as the Python mirror
 // (dynamicfusion_amd.mesh_ops).
 #pragma once
 #include <kfusion/types.hpp>
@@ -70,5 +71,25 @@ void boundaryLoops(const DeviceArray<int>& triangles, size_t n_vertices, DeviceA
 /// count-only call whose counts are read back, then one of that size).
 void fillHoles(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, unsigned int max_edges, DeviceArray<Point>& out_vertices,
                DeviceArray<int>& out_triangles, DeviceArray<int>& vertex_src, DeviceArray<unsigned long long>* counts = nullptr);
+
+/// For every query point (w ignored) the nearest eligible triangle of the mesh and the closest point on it, through a BVH built inside
+/// the call: triangle[q] = its index (0xffffffff without a winner: no eligible triangle, a non-finite query, nothing within max_dist2),
+/// point[q] = (x, y, z, squared distance); bary (optional) = (u, v, w, 0); counts (optional): the call's 8 counts.  max_dist2: the
+/// largest admissible squared distance, +infinity for no limit.  Enqueued only when `counts` is given; without it the call's own counts
+/// array is freed on return, so the stream is waited for.
+void closestPoints(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, const DeviceArray<Point>& points, float max_dist2,
+                   DeviceArray<int>& triangle, DeviceArray<Point>& point, DeviceArray<Point>* bary = nullptr,
+                   DeviceArray<unsigned long long>* counts = nullptr);
+
+/// One direction of meshDistance: the samples with and without a closest point, the largest distance with the smallest sample index that
+/// attains it (from the call's counts; -1 if none), and the mean and RMS distance over the answered samples.
+struct MeshDistanceSide { unsigned long long answered, unanswered; double max; long long max_vertex; double mean, rms; };
+struct MeshDistance { MeshDistanceSide a_to_b, b_to_a; double hausdorff; };
+
+/// The distances between two meshes sampled at their vertices (every vertex of the arrays, used or not): A's against mesh B, B's against
+/// mesh A, and the larger of the two maxima.  Two closestPoints calls; their counts and squared distances are read back, and mean and
+/// RMS are double sums over them on the host, in index order.
+MeshDistance meshDistance(const DeviceArray<Point>& vertices_a, const DeviceArray<int>& triangles_a, const DeviceArray<Point>& vertices_b,
+                          const DeviceArray<int>& triangles_b);
 
 } }

@@ -6,6 +6,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
+#include <vector>
 #include <hip/hip_runtime_api.h>
 #include <kfusion/cuda/tsdf_volume.hpp>
 #include <kfusion/cuda/color_volume.hpp>
@@ -512,6 +514,55 @@ void kfusion::cuda::fillHoles(const DeviceArray<Point>& vertices, const DeviceAr
     if (n[0] || n[1])
         run(n[0] ? (float*)out_vertices.ptr() : nullptr, n[0] ? (unsigned int*)vertex_src.ptr() : nullptr, n[0],
             n[1] ? (unsigned int*)out_triangles.ptr() : nullptr, n[1]);
+}
+
+void kfusion::cuda::closestPoints(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, const DeviceArray<Point>& points, float max_dist2,
+                                  DeviceArray<int>& triangle, DeviceArray<Point>& point, DeviceArray<Point>* bary, DeviceArray<unsigned long long>* counts_out)
+{
+    const size_t nv = vertices.size(), nt = triangles.size() / 3, nq = points.size();
+    DeviceArray<unsigned long long> own;
+    DeviceArray<unsigned long long>& counts = counts_out ? *counts_out : own;
+    counts.create(8);
+    triangle.create(nq); point.create(nq);
+    if (bary) bary->create(nq);
+    KF_DF(dfusion_mesh_closest_points(nv ? (const float*)vertices.ptr() : nullptr, nv, nt ? (const unsigned int*)triangles.ptr() : nullptr, nt,
+                                      nq ? (const float*)points.ptr() : nullptr, nq, max_dist2, nq ? (unsigned int*)triangle.ptr() : nullptr,
+                                      nq ? (float*)point.ptr() : nullptr, bary && nq ? (float*)bary->ptr() : nullptr, counts.ptr(), nullptr));
+    if (!counts_out) KF_HIP(hipStreamSynchronize(nullptr));               // the counts are freed on return
+}
+
+static kfusion::cuda::MeshDistanceSide one_sided_distance(const kfusion::cuda::DeviceArray<kfusion::Point>& samples, const kfusion::cuda::DeviceArray<kfusion::Point>& vertices,
+                                                          const kfusion::cuda::DeviceArray<int>& triangles)
+{
+    using namespace kfusion;
+    cuda::DeviceArray<int> triangle; cuda::DeviceArray<Point> point; cuda::DeviceArray<unsigned long long> counts;
+    cuda::closestPoints(vertices, triangles, samples, std::numeric_limits<float>::infinity(), triangle, point, nullptr, &counts);
+    unsigned long long n[8];
+    counts.download(n);
+    std::vector<int> tri; std::vector<Point> pt;
+    triangle.download(tri); point.download(pt);
+    double sum_d = 0.0, sum_d2 = 0.0;
+    for (size_t i = 0; i < tri.size(); ++i)
+        if ((unsigned int)tri[i] != 0xffffffffu) { sum_d += std::sqrt((double)pt[i].data[3]); sum_d2 += (double)pt[i].data[3]; }
+    cuda::MeshDistanceSide s;
+    s.answered = n[0]; s.unanswered = n[1];
+    const unsigned int bits = (unsigned int)n[4];
+    float top; std::memcpy(&top, &bits, 4);
+    s.max = n[0] ? std::sqrt((double)top) : 0.0;
+    s.max_vertex = n[0] ? (long long)n[5] : -1;
+    s.mean = n[0] ? sum_d / (double)n[0] : 0.0;
+    s.rms = n[0] ? std::sqrt(sum_d2 / (double)n[0]) : 0.0;
+    return s;
+}
+
+kfusion::cuda::MeshDistance kfusion::cuda::meshDistance(const DeviceArray<Point>& vertices_a, const DeviceArray<int>& triangles_a,
+                                                        const DeviceArray<Point>& vertices_b, const DeviceArray<int>& triangles_b)
+{
+    MeshDistance d;
+    d.a_to_b = one_sided_distance(vertices_a, vertices_b, triangles_b);
+    d.b_to_a = one_sided_distance(vertices_b, vertices_a, triangles_a);
+    d.hausdorff = d.a_to_b.max > d.b_to_a.max ? d.a_to_b.max : d.b_to_a.max;
+    return d;
 }
 
 // ------------------------------------------------------------------------------------------ ColorVolume (include/dfusion.h dfusion_color_*)

@@ -2,7 +2,11 @@
 pieces (include/dfusion.h dfusion_mesh_components / dfusion_mesh_filter / dfusion_gather_rows, where the rule is stated), and the mesh
 simplified by vertex clustering (dfusion_mesh_simplify), its vertex adjacency with the edge statistics (dfusion_mesh_adjacency) and Taubin
 smoothing over it (dfusion_mesh_smooth), its closed boundary loops (dfusion_mesh_boundary_loops) and the mesh with the small ones
-filled (dfusion_mesh_fill_holes).  Device tensors in, device tensors out; all compute is in libdfusion_hip.so."""
+filled (dfusion_mesh_fill_holes), and the closest point of the mesh to every query point with the distances between two meshes
+(dfusion_mesh_closest_points).  Device tensors in, device tensors out; all compute is in libdfusion_hip.so."""
+import math
+import struct
+
 import torch
 
 from . import capi
@@ -236,3 +240,64 @@ def smooth_mesh(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, fix_bound
                                               _flat(vertex_class) if vertex_class is not None and nv else None, int(iterations), float(lam), float(mu),
                                               FIX_BOUNDARY if fix_boundary else 0, _flat(out) if nv else None, _stream()), "dfusion_mesh_smooth")
     return out
+
+
+CLOSEST_COUNT_NAMES = ("answered", "unanswered", "eligible_triangles", "skipped_triangles", "max_d2_bits", "max_query", "triangle_tests",
+                       "nodes_visited")
+
+
+def _points4(x, what):
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 4 or not x.is_contiguous():
+        raise ValueError("%s %s %s, expected contiguous float32 [N, 4]" % (what, x.dtype, tuple(x.shape)))
+    return int(x.shape[0])
+
+
+def closest_points(vertices, triangles, points, max_distance=None, return_barycentric=False, return_counts=False):
+    """For every query point the nearest eligible triangle of the mesh and the closest point on it (include/dfusion.h
+    dfusion_mesh_closest_points has the rule; a linear BVH is built inside the call).  vertices float32 [V, 4], triangles int32 [T, 3]
+    (uint32 bits), points float32 [Q, 4] (w ignored), max_distance None (no limit) or a distance whose f32 square is max_dist2 ->
+    (triangle int32 [Q] (uint32 bits; 0xffffffff without a winner), point float32 [Q, 4]: x, y, z and the squared distance); with
+    return_barycentric also bary float32 [Q, 4] (u, v, w, 0); with return_counts also counts int64 [8] (CLOSEST_COUNT_NAMES).
+    Nothing synchronises."""
+    tp, nt = _triangles(triangles)
+    nv, nq = _points4(vertices, "vertices"), _points4(points, "points")
+    if vertices.device != triangles.device or points.device != triangles.device:
+        raise ValueError("vertices on %s, triangles on %s, points on %s" % (vertices.device, triangles.device, points.device))
+    if max_distance is None:
+        max_d2 = float("inf")
+    else:
+        d = torch.tensor(float(max_distance), dtype=torch.float32)
+        max_d2 = float(d * d)                                            # the f32 product
+    dev = triangles.device
+    tri = torch.empty(nq, dtype=torch.int32, device=dev)
+    point = torch.empty((nq, 4), dtype=torch.float32, device=dev)
+    bary = torch.empty((nq, 4), dtype=torch.float32, device=dev) if return_barycentric else None
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    capi.check(capi.lib().dfusion_mesh_closest_points(_flat(vertices) if nv else None, nv, tp, nt, _flat(points) if nq else None, nq, max_d2,
+                                                      _flat(tri) if nq else None, _flat(point) if nq else None,
+                                                      _flat(bary) if return_barycentric and nq else None, _flat(counts), _stream()),
+               "dfusion_mesh_closest_points")
+    return (tri, point) + ((bary,) if return_barycentric else ()) + ((counts,) if return_counts else ())
+
+
+def _one_sided(vertices_a, vertices_b, triangles_b):
+    tri, point, counts = closest_points(vertices_b, triangles_b, vertices_a, return_counts=True)
+    d2 = torch.where(tri != -1, point[:, 3].double(), torch.zeros((), dtype=torch.float64, device=point.device))      # f64 sums on the device
+    sums = torch.stack([d2.sqrt().sum(), d2.sum()])
+    c = [int(x) for x in counts.tolist()]                                # the one read-back
+    s_d, s_d2 = (float(x) for x in sums.tolist())
+    n = c[0]
+    max_d = math.sqrt(struct.unpack("<f", struct.pack("<I", c[4]))[0]) if n else 0.0      # the f64 root of the largest f32 d2
+    return {"answered": n, "unanswered": c[1], "max": max_d, "max_vertex": c[5] if n else None,
+            "mean": s_d / n if n else 0.0, "rms": math.sqrt(s_d2 / n) if n else 0.0}
+
+
+def mesh_distance(vertices_a, triangles_a, vertices_b, triangles_b):
+    """The distances between two meshes, sampled at the given vertices: -> dict with "a_to_b" (every vertex of A against mesh B) and
+    "b_to_a", each a dict of answered / unanswered (the vertices with and without a closest point), max (the largest distance, from
+    the call's counts) with max_vertex (the smallest index that attains it), mean and rms over the answered vertices (f64 reductions of
+    the returned squared distances on the device), and "hausdorff", the larger of the two maxima.  Every vertex of the arrays is a
+    sample, used by a triangle or not.  Two closest_points calls; their counts are read back."""
+    ab = _one_sided(vertices_a, vertices_b, triangles_b)
+    ba = _one_sided(vertices_b, vertices_a, triangles_a)
+    return {"a_to_b": ab, "b_to_a": ba, "hausdorff": max(ab["max"], ba["max"])}

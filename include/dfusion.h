@@ -529,6 +529,55 @@ int dfusion_mesh_fill_holes(const float *vertices_dev, unsigned long long n_vert
                             unsigned int *vertex_src_dev /* nullable, vertex_capacity */,
                             unsigned long long *counts_dev /* [8] */, dfStream stream);
 
+/* Closest point on a triangle mesh: for every query point the nearest eligible triangle, the closest point on it, the squared distance
+ * and the barycentrics, through a linear BVH built inside the call (no reference counterpart; additive, ABI 7).  DESIGN.md section 28
+ * has the kernels, the slack of the pruning bound and the stack bound; tests/mesh_closest_ref.py restates the rule in numpy by brute
+ * force over all triangles, and triangle, point, bary and counts [0] - [5] equal it bit for bit: the tree only prunes.
+ * Inputs: V vertices of four floats (x, y, z, w; w ignored), T triangles of three uint32 indices, Q query points of four floats (w
+ * ignored), max_dist2 (f32; +inf: no limit).
+ *   ELIGIBLE   a triangle whose three indices are < V and pairwise different and whose nine coordinates are finite.  Every other one is
+ *              skipped and counted.  A geometrically degenerate triangle with three different indices stays eligible: the arithmetic
+ *              below decides what it yields.
+ *   DISTANCE   of the query p to the triangle (a, b, c): the Voronoi-region routine of Ericson, Real-Time Collision Detection 5.1.5, in
+ *              its published order of tests.  Every operation is ONE f32 operation, nothing is fused, dot(x, y) = x.x*y.x + x.y*y.y +
+ *              x.z*y.z added left to right, divisions are IEEE f32:
+ *                ab = b - a; ac = c - a; ap = p - a; d1 = dot(ab, ap); d2 = dot(ac, ap);
+ *                bp = p - b; d3 = dot(ab, bp); d4 = dot(ac, bp);  cp = p - c; d5 = dot(ab, cp); d6 = dot(ac, cp);
+ *                vc = d1*d4 - d3*d2; vb = d5*d2 - d1*d6; va = d3*d6 - d5*d4;
+ *                1 vertex A  if d1 <= 0 && d2 <= 0:                      v = 0, w = 0
+ *                2 vertex B  else if d3 >= 0 && d4 <= d3:                v = 1, w = 0
+ *                3 edge AB   else if vc <= 0 && d1 >= 0 && d3 <= 0:      v = d1 / (d1 - d3), w = 0
+ *                4 vertex C  else if d6 >= 0 && d5 <= d6:                v = 0, w = 1
+ *                5 edge AC   else if vb <= 0 && d2 >= 0 && d6 <= 0:      v = 0, w = d2 / (d2 - d6)
+ *                6 edge BC   else if va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0:  w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), v = 1 - w
+ *                7 face      else:  denom = 1 / ((va + vb) + vc); v = vb * denom; w = vc * denom
+ *              u = (1 - v) - w; point = (a + ab*v) + ac*w per axis (each product rounded, then the two adds); e = p - point;
+ *              d2 = dot(e, e).  A NaN anywhere makes the comparisons false, falls through to the face case and gives a NaN d2.
+ *   WINNER     the routine is applied to every eligible triangle t.  The candidate (d2, t) is admissible iff d2 <= max_dist2 (a NaN
+ *              never is); it beats the best so far iff its d2 is smaller, or equal with a smaller t.
+ *   NO WINNER  (no eligible triangle, a query with a non-finite x, y or z, nothing within max_dist2): triangle 0xffffffff, point x, y,
+ *              z = the bits 0x7fc00000, d2 = +inf, barycentrics 0.
+ *   triangle_dev[q]           the winner's index.
+ *   point_dev[4 q ..]         (x, y, z, d2).
+ *   bary_dev[4 q ..] (nullable)  (u, v, w, 0).
+ *   counts_dev[8] (u64, WRITTEN, always): [0] queries with a winner, [1] without, [2] eligible triangles, [3] skipped triangles, [4] the
+ *              f32 bits of the largest winning d2 (0 if [0] == 0), [5] the smallest query index that attains it (0xffffffff if none) --
+ *              both from one 64-bit integer atomic max over {bits, ~q} --, [6] triangle tests made and [7] tree nodes visited, summed
+ *              over the queries: integer sums, reproducible for one input, but a property of the tree and not of the rule.
+ * T == 0, V == 0 and Q == 0 are valid inputs; with Q == 0 the triangles are still counted.  Arrays of length 0 may be NULL.
+ * DF_E_INVALID: V, T or Q > 2^32 - 1, a NULL array (bary_dev apart) with a non-zero length, counts_dev NULL, an output array
+ * (counts_dev included) that overlaps vertices_dev, triangles_dev or queries_dev.  Without a device DF_E_NO_DEVICE.  No device-to-host
+ * copy, no synchronisation, integer atomics only (no output but [6] and [7] depends on the tree, none on scheduling); every launch
+ * covers its range with 64-bit indices.  The tree lives in the workspace and is rebuilt by every call.  Workspace, from the
+ * per-(device, stream) scratch of dfusion_extract_mesh (dfusion_release_scratch): 77 T + 48 bytes, every array rounded up to 16, and
+ * hipcub's storage for one sort of T 64-bit keys.                                                                                    */
+int dfusion_mesh_closest_points(const float *vertices_dev, unsigned long long n_vertices,
+                                const unsigned int *triangles_dev, unsigned long long n_triangles,
+                                const float *queries_dev, unsigned long long n_queries, float max_dist2,
+                                unsigned int *triangle_dev /* n_queries */, float *point_dev /* 4 n_queries */,
+                                float *bary_dev /* nullable, 4 n_queries */,
+                                unsigned long long *counts_dev /* [8] */, dfStream stream);
+
 /* ---- colour volume (no reference counterpart: KinFu::operator() drops its colour image; additive, ABI 7) ----------------------
  * A colour volume belongs to a TSDF volume: the same dims, linear layout (x + y X + z X Y) and stored planes (DfSlab), 4 bytes a
  * voxel {c0, c1, c2, w}: three channels in the byte order of the input image (the kernels treat them alike) and a weight byte;
