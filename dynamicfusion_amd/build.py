@@ -15,9 +15,9 @@ LIB_PATH = os.path.join(PKG_DIR, "libdfusion_hip.so")
 
 SOURCES = ["dfusion_volume.hip", "dfusion_warp.hip", "dfusion_warp_nodes.hip", "dfusion_warp_points.hip", "dfusion_warp_index.hip",
            "dfusion_raycast.hip", "dfusion_frontend.hip", "dfusion_solver.hip", "dfusion_selftest.hip", "dfusion_warp_extend.hip", "dfusion_mesh.hip", "dfusion_associate.hip", "dfusion_color.hip", "dfusion_render.hip",
-           "dfusion_warp_graph.hip", "dfusion_mesh_components.hip", "dfusion_mesh_simplify.hip", "dfusion_mesh_smooth.hip", "dfusion_mesh_holes.hip", "dfusion_mesh_bvh.hip"]
+           "dfusion_warp_graph.hip", "dfusion_mesh_components.hip", "dfusion_mesh_simplify.hip", "dfusion_mesh_smooth.hip", "dfusion_mesh_holes.hip", "dfusion_mesh_bvh.hip", "dfusion_mesh_rays.hip"]
 HEADERS = ["dfusion_device.h", "dfusion_internal.h", "dfusion_nanoflann.h", "dfusion_pyramid.h", "dfusion_warp_topk.h", "dfusion_warp_sweep.h",
-           "dfusion_warp_blocks.h", "dfusion_warp_pipe.h", "dfusion_plan_halves.h", "dfusion_warp_decide.h", "dfusion_mesh_cc.h", "dfusion_mesh_uses.h", os.path.join(REPO_DIR, "include", "dfusion.h")]
+           "dfusion_warp_blocks.h", "dfusion_warp_pipe.h", "dfusion_plan_halves.h", "dfusion_warp_decide.h", "dfusion_mesh_cc.h", "dfusion_mesh_uses.h", "dfusion_mesh_bvh.h", os.path.join(REPO_DIR, "include", "dfusion.h")]
 
 # -ffp-contract=off: fused multiply-adds only where the reference writes __fmaf_rn (explicit fmaf);
 # that is what makes the kernels bit-comparable with the IEEE CPU oracle.
@@ -68,6 +68,7 @@ def kernel_source_sha(kernel):
          else "dfusion_mesh_smooth.hip" if k.startswith("df_msm_")
          else "dfusion_mesh_holes.hip" if k.startswith("df_mhl_")
          else "dfusion_mesh_bvh.hip" if k.startswith("df_mbv_")
+         else "dfusion_mesh_rays.hip" if k.startswith("df_mry_")
          else "dfusion_mesh.hip" if k.startswith("df_mesh")
          else "dfusion_associate.hip" if k.startswith("df_assoc")
          else "dfusion_color.hip" if k.startswith("df_color")
@@ -106,10 +107,11 @@ HOST_SIMPLIFY_MESH = os.path.join(HOST_DIR, "simplify_mesh")
 HOST_SMOOTH_MESH = os.path.join(HOST_DIR, "smooth_mesh")
 HOST_FILL_HOLES = os.path.join(HOST_DIR, "fill_holes")
 HOST_MESH_DISTANCE = os.path.join(HOST_DIR, "mesh_distance")
+HOST_MESH_RAYS = os.path.join(HOST_DIR, "mesh_rays")
 HOST_ZSLAB_LIB = os.path.join(HOST_DIR, "libkfusion_zslab.so")       # kfusion::cuda::ZSlabComm: the RCCL side of the Z-slab sharding
 HOST_ZSLAB_APP = os.path.join(HOST_DIR, "zslab_frame")
 # the apps over libkfusion_hip.so, in build order: host/<name> from host/apps/<name>.cpp (zslab_frame also links libkfusion_zslab.so and rccl)
-HOST_APPS = [HOST_APP, HOST_KINFU_APP, HOST_WARP_TESTS, HOST_DEMO_CALLS, HOST_WARP_SOLVE, HOST_ASSOCIATE, HOST_COLOR_FRAME, HOST_RENDER_MESH, HOST_SIMPLIFY_MESH, HOST_SMOOTH_MESH, HOST_FILL_HOLES, HOST_MESH_DISTANCE, HOST_ZSLAB_APP]
+HOST_APPS = [HOST_APP, HOST_KINFU_APP, HOST_WARP_TESTS, HOST_DEMO_CALLS, HOST_WARP_SOLVE, HOST_ASSOCIATE, HOST_COLOR_FRAME, HOST_RENDER_MESH, HOST_SIMPLIFY_MESH, HOST_SMOOTH_MESH, HOST_FILL_HOLES, HOST_MESH_DISTANCE, HOST_MESH_RAYS, HOST_ZSLAB_APP]
 
 
 def build_host(force=False, verbose=False):

@@ -68,6 +68,7 @@ SYMBOLS = [
     "dfusion_warp_set_preconditioner", "dfusion_warp_preconditioner",
     "dfusion_mesh_components", "dfusion_mesh_filter", "dfusion_gather_rows", "dfusion_mesh_simplify",
     "dfusion_mesh_adjacency", "dfusion_mesh_smooth", "dfusion_mesh_boundary_loops", "dfusion_mesh_fill_holes", "dfusion_mesh_closest_points",
+    "dfusion_mesh_ray_hits",
 ]
 
 
@@ -138,6 +139,7 @@ def load(path, strict=True):
     L.dfusion_mesh_boundary_loops.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, vp, vp, vp, vp, C.c_ulonglong, vp, C.c_ulonglong, vp, vp]
     L.dfusion_mesh_fill_holes.argtypes = [vp, C.c_ulonglong, vp, C.c_ulonglong, C.c_uint, C.c_uint, vp, C.c_ulonglong, vp, C.c_ulonglong, vp, vp, vp]
     L.dfusion_mesh_closest_points.argtypes = [vp, C.c_ulonglong, vp, C.c_ulonglong, vp, C.c_ulonglong, C.c_float, vp, vp, vp, vp, vp]
+    L.dfusion_mesh_ray_hits.argtypes = [vp, C.c_ulonglong, vp, C.c_ulonglong, vp, vp, C.c_ulonglong, C.c_float, C.c_float, C.c_uint, vp, vp, vp, vp, vp]
     L.dfusion_color_clear.argtypes = [vp, DfVolume, C.POINTER(DfSlab), vp]
     L.dfusion_color_integrate.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, DfVolume, C.POINTER(DfSlab), vp, fp, fp, fp, vp, C.c_int,
                                           C.c_float, C.c_int, C.c_longlong, vp, vp, vp]

@@ -19,38 +19,17 @@
 //             (strictly, so an equal distance with a smaller index is still reached); the bound carries the slack of DESIGN section 28
 //   finish    one lane: counts [4] and [5] from the packed maximum
 // Every grid is capped at DF_MSM_MAX_BLOCKS workgroups (524 288 lanes) and strides over its range with 64-bit indices.
+// The stages bounds .. boxes are also what dfusion_mesh_ray_hits (dfusion_mesh_rays.hip) builds its tree with: df_mbv_plan and df_mbv_build
+// below run them for both; what the two files share is declared in dfusion_mesh_bvh.h.
 //
 // The stack.  A key has 62 significant bits (30 of code, 32 of index; bits 63 and 62 are zero in every eligible key).  An internal node's
 // keys share a prefix of d bits, 2 <= d <= 63 (two different keys differ somewhere), and a child's prefix is strictly longer than its
 // parent's.  So a root-to-leaf path holds at most 62 internal nodes.  The walk pushes at most one entry (the farther child) per
 // internal node on the current path and only internal nodes are ever pushed, so at most 62 entries are live: DF_MBV_STACK = 64.
-#include "dfusion_mesh_uses.h"
+#include "dfusion_mesh_bvh.h"
 #include <math.h>
 
 #pragma clang fp contract(off)                       // the routine is single f32 operations in a written order; nothing here may fuse
-
-#define DF_MBV_NONE 0xffffffffu
-#define DF_MBV_STACK 64
-#define DF_MBV_LEFT_LEAF 1u
-#define DF_MBV_RIGHT_LEAF 2u
-
-struct DfMbvArgs {
-    size_t V, T, Q;
-    const float4* P; const uint32_t* tris; const float4* q; float max_d2;
-    uint32_t* bounds;                                        // [8] keys: min x y z -, max x y z - of the eligible centroids
-    unsigned long long *keys_in, *keys;                      // [T] as emitted, sorted
-    uint32_t* split; uint8_t* flags;                         // [T] per internal node: children are split and split + 1; which of them are leaves
-    uint32_t *par_i, *par_l;                                 // [T] the parent (an internal node) of an internal node / of a sorted leaf
-    uint32_t *box_i, *box_l;                                 // [6 T] keys {min x y z, max x y z} of an internal node / of a sorted leaf
-    unsigned long long* top;                                 // the largest winning d2: bits << 32 | ~q
-    unsigned long long* counts;
-    uint32_t* out_t; float4* out_p; float4* out_b;
-};
-
-// An order-preserving map of the finite and infinite floats onto uint32 (-0 below +0), and back.
-__device__ __forceinline__ uint32_t mbv_key(float f) { const uint32_t b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : b ^ 0x80000000u; }
-__device__ __forceinline__ float mbv_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? k ^ 0x80000000u : ~k); }
-__device__ __forceinline__ bool mbv_finite(float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; }
 
 // ELIGIBLE: three indices < V (tested before anything is indexed), pairwise different, nine finite coordinates.
 __device__ __forceinline__ bool mbv_load(const DfMbvArgs& a, size_t t, float4& A, float4& B, float4& C)
@@ -64,19 +43,6 @@ __device__ __forceinline__ bool mbv_load(const DfMbvArgs& a, size_t t, float4& A
 }
 
 __device__ __forceinline__ float mbv_centroid(float a, float b, float c) { return ((a + b) + c) / 3.0f; }
-
-// counts[slot[j]] += the workgroup's sum of value[j], through LDS: one global atomic per workgroup and slot.  Every lane calls it, once.
-template <int K>
-__device__ __forceinline__ void mbv_block_add(unsigned long long* counts, const int (&slot)[K], const unsigned long long (&value)[K])
-{
-    __shared__ unsigned long long acc[K];
-    if (threadIdx.x < K) acc[threadIdx.x] = 0ull;
-    __syncthreads();
-    for (int j = 0; j < K; ++j)
-        if (value[j]) atomicAdd(&acc[j], value[j]);
-    __syncthreads();
-    if (threadIdx.x < K && acc[threadIdx.x]) atomicAdd(&counts[slot[threadIdx.x]], acc[threadIdx.x]);
-}
 
 __global__ __launch_bounds__(256) void df_mbv_bounds_kernel(const DfMbvArgs a)
 {
@@ -345,12 +311,7 @@ __global__ __launch_bounds__(256) void df_mbv_none_kernel(const DfMbvArgs a)
     if (blockIdx.x == 0 && threadIdx.x == 0) a.counts[1] = (unsigned long long)a.Q;
 }
 
-// The workspace, front to back (every array rounded up to 16 bytes): [keys as emitted 8 T] [sorted keys 8 T] [split 4 T] [flags T]
-// [parents of internal nodes 4 T, of leaves 4 T] [boxes of internal nodes 24 T, of leaves 24 T] [bounds 32] [top 16]
-// [hipcub's sort storage, 256-byte aligned]: 77 T + 48 bytes and that storage.
-struct DfMbvLayout { size_t o_keys, o_split, o_flags, o_par_i, o_par_l, o_box_i, o_box_l, o_bounds, o_top, o_cub, cub_bytes, total; };
-
-static int mbv_plan(size_t T, hipStream_t st, DfMbvLayout* l)
+int df_mbv_plan(size_t T, hipStream_t st, DfMbvLayout* l)
 {
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t o = at; at += df_msm_up16(bytes); return o; };
@@ -360,6 +321,30 @@ static int mbv_plan(size_t T, hipStream_t st, DfMbvLayout* l)
     l->cub_bytes = 0;
     DF_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, l->cub_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, T, 0, 64, st));
     l->total = l->o_cub + l->cub_bytes;
+    return DF_OK;
+}
+
+int df_mbv_build(DfMbvArgs& a, const DfMbvLayout& l, char* ws, bool tree, hipStream_t st)
+{
+    a.keys_in = (unsigned long long*)ws; a.keys = (unsigned long long*)(ws + l.o_keys);
+    a.split = (uint32_t*)(ws + l.o_split); a.flags = (uint8_t*)(ws + l.o_flags);
+    a.par_i = (uint32_t*)(ws + l.o_par_i); a.par_l = (uint32_t*)(ws + l.o_par_l);
+    a.box_i = (uint32_t*)(ws + l.o_box_i); a.box_l = (uint32_t*)(ws + l.o_box_l);
+    a.bounds = (uint32_t*)(ws + l.o_bounds); a.top = (unsigned long long*)(ws + l.o_top);
+    const dim3 wg(256), gt(df_msm_blocks(a.T));
+    DF_HIP(hipMemsetAsync(a.bounds, 0xff, 16, st));
+    DF_HIP(hipMemsetAsync(a.bounds + 4, 0, 16 + 16, st));                 // the maxima and, behind them, top
+    hipLaunchKernelGGL(df_mbv_bounds_kernel, gt, wg, 0, st, a);
+    DF_LAUNCH_CHECK();
+    if (!tree) return DF_OK;
+    hipLaunchKernelGGL(df_mbv_codes_kernel, gt, wg, 0, st, a);
+    DF_LAUNCH_CHECK();
+    size_t cub_bytes = l.cub_bytes;
+    DF_HIP(hipcub::DeviceRadixSort::SortKeys(ws + l.o_cub, cub_bytes, (const unsigned long long*)a.keys_in, a.keys, a.T, 0, 64, st));
+    hipLaunchKernelGGL(df_mbv_tree_kernel, gt, wg, 0, st, a);
+    DF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(df_mbv_boxes_kernel, gt, wg, 0, st, a);
+    DF_LAUNCH_CHECK();
     return DF_OK;
 }
 
@@ -385,7 +370,7 @@ extern "C" int dfusion_mesh_closest_points(const float* vertices_dev, unsigned l
     a.V = V; a.T = T; a.Q = Q;
     a.P = (const float4*)vertices_dev; a.tris = triangles_dev; a.q = (const float4*)queries_dev; a.max_d2 = max_dist2;
     a.counts = counts_dev; a.out_t = triangle_dev; a.out_p = (float4*)point_dev; a.out_b = (float4*)bary_dev;
-    const dim3 wg(256), gq(df_msm_blocks(Q)), gt(df_msm_blocks(T));
+    const dim3 wg(256), gq(df_msm_blocks(Q));
     if (!T) {
         if (Q) { hipLaunchKernelGGL(df_mbv_none_kernel, gq, wg, 0, st, a); DF_LAUNCH_CHECK(); }
         hipLaunchKernelGGL(df_mbv_finish_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long*)nullptr, counts_dev);
@@ -393,27 +378,11 @@ extern "C" int dfusion_mesh_closest_points(const float* vertices_dev, unsigned l
         return DF_OK;
     }
     DfMbvLayout l;
-    DF_TRY(mbv_plan(T, st, &l));
+    DF_TRY(df_mbv_plan(T, st, &l));
     DfScratchHold hold(st, l.total);                                      // held until the last launch is enqueued
     if (!hold.entry) return (int)hipErrorOutOfMemory;
-    char* const ws = hold.mem;
-    a.keys_in = (unsigned long long*)ws; a.keys = (unsigned long long*)(ws + l.o_keys);
-    a.split = (uint32_t*)(ws + l.o_split); a.flags = (uint8_t*)(ws + l.o_flags);
-    a.par_i = (uint32_t*)(ws + l.o_par_i); a.par_l = (uint32_t*)(ws + l.o_par_l);
-    a.box_i = (uint32_t*)(ws + l.o_box_i); a.box_l = (uint32_t*)(ws + l.o_box_l);
-    a.bounds = (uint32_t*)(ws + l.o_bounds); a.top = (unsigned long long*)(ws + l.o_top);
-    DF_HIP(hipMemsetAsync(a.bounds, 0xff, 16, st));
-    DF_HIP(hipMemsetAsync(a.bounds + 4, 0, 16 + 16, st));                 // the maxima and, behind them, top
-    hipLaunchKernelGGL(df_mbv_bounds_kernel, gt, wg, 0, st, a);
-    DF_LAUNCH_CHECK();
+    DF_TRY(df_mbv_build(a, l, hold.mem, Q != 0, st));
     if (Q) {
-        hipLaunchKernelGGL(df_mbv_codes_kernel, gt, wg, 0, st, a);
-        DF_LAUNCH_CHECK();
-        DF_HIP(hipcub::DeviceRadixSort::SortKeys(ws + l.o_cub, l.cub_bytes, (const unsigned long long*)a.keys_in, a.keys, T, 0, 64, st));
-        hipLaunchKernelGGL(df_mbv_tree_kernel, gt, wg, 0, st, a);
-        DF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(df_mbv_boxes_kernel, gt, wg, 0, st, a);
-        DF_LAUNCH_CHECK();
         hipLaunchKernelGGL(df_mbv_query_kernel, gq, wg, 0, st, a);
         DF_LAUNCH_CHECK();
     }

@@ -4,9 +4,11 @@
 // vertex clustering (dfusion_mesh_simplify).  meshAdjacency / smoothMesh: the vertex adjacency with the edge statistics and Taubin
 // smoothing over it (dfusion_mesh_adjacency / dfusion_mesh_smooth).  boundaryLoops / fillHoles: the closed loops of boundary half-edges
 // and the mesh with the small ones filled (dfusion_mesh_boundary_loops / dfusion_mesh_fill_holes).  closestPoints / meshDistance: the
-// closest point of a mesh to every query point and the distances between two meshes (dfusion_mesh_closest_points).  Same calls as the Python mirror
+// closest point of a mesh to every query point and the distances between two meshes (dfusion_mesh_closest_points).  rayHits /
+// visiblePoints: what every ray hits first on a mesh and which points an eye sees (dfusion_mesh_ray_hits).  Same calls as the Python mirror
 // (dynamicfusion_amd.mesh_ops).
 #pragma once
+#include <vector>
 #include <kfusion/types.hpp>
 
 namespace kfusion { namespace cuda {
@@ -91,5 +93,20 @@ struct MeshDistance { MeshDistanceSide a_to_b, b_to_a; double hausdorff; };
 /// RMS are double sums over them on the host, in index order.
 MeshDistance meshDistance(const DeviceArray<Point>& vertices_a, const DeviceArray<int>& triangles_a, const DeviceArray<Point>& vertices_b,
                           const DeviceArray<int>& triangles_b);
+
+/// For every ray origins[r] + t directions[r] (w ignored; the direction is used as given, t is in its units), t in [t_min, t_max], the
+/// first eligible triangle of the mesh that it hits, through a BVH built inside the call: triangle[r] = its index (0xffffffff without a
+/// hit), hit[r] = (x, y, z, t); bary (optional) = (1 - u - v, u, v, side); counts (optional): the call's 8 counts.  With
+/// DF_RAYS_ANY_HIT in `flags` triangle[r] is 0 where the ray hits anything, `hit` is left alone and `bary` must be null.  Enqueued only
+/// when `counts` is given; without it the call's own counts array is freed on return, so the stream is waited for.
+void rayHits(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, const DeviceArray<Point>& origins,
+             const DeviceArray<Point>& directions, float t_min, float t_max, unsigned int flags, DeviceArray<int>& triangle, DeviceArray<Point>& hit,
+             DeviceArray<Point>* bary = nullptr, DeviceArray<unsigned long long>* counts = nullptr);
+
+/// visible[i] = 1 iff the eye sees points[i]: the ray o = eye, d = p - eye (one f32 subtraction, on the host) on [0, 1 - margin] hits
+/// nothing of the mesh (one any-hit rayHits) and p is finite.  `margin`: the share of the segment in front of p that is not looked at.
+/// The points are read back and the rays uploaded: the mirror has no kernels of its own.
+void visiblePoints(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, const DeviceArray<Point>& points, const float eye[3],
+                   float margin, std::vector<unsigned char>& visible);
 
 } }

@@ -565,6 +565,47 @@ kfusion::cuda::MeshDistance kfusion::cuda::meshDistance(const DeviceArray<Point>
     return d;
 }
 
+void kfusion::cuda::rayHits(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, const DeviceArray<Point>& origins,
+                            const DeviceArray<Point>& directions, float t_min, float t_max, unsigned int flags, DeviceArray<int>& triangle,
+                            DeviceArray<Point>& hit, DeviceArray<Point>* bary, DeviceArray<unsigned long long>* counts_out)
+{
+    const size_t nv = vertices.size(), nt = triangles.size() / 3, nr = origins.size();
+    if (directions.size() != nr) kfusion::cuda::error("origins and directions differ in length", __FILE__, __LINE__, "rayHits");
+    const bool any = (flags & DF_RAYS_ANY_HIT) != 0u;
+    DeviceArray<unsigned long long> own;
+    DeviceArray<unsigned long long>& counts = counts_out ? *counts_out : own;
+    counts.create(8);
+    triangle.create(nr);
+    if (!any) hit.create(nr);
+    if (bary) bary->create(nr);
+    KF_DF(dfusion_mesh_ray_hits(nv ? (const float*)vertices.ptr() : nullptr, nv, nt ? (const unsigned int*)triangles.ptr() : nullptr, nt,
+                                nr ? (const float*)origins.ptr() : nullptr, nr ? (const float*)directions.ptr() : nullptr, nr, t_min, t_max, flags,
+                                nr ? (unsigned int*)triangle.ptr() : nullptr, !any && nr ? (float*)hit.ptr() : nullptr,
+                                bary && nr ? (float*)bary->ptr() : nullptr, counts.ptr(), nullptr));
+    if (!counts_out) KF_HIP(hipStreamSynchronize(nullptr));               // the counts are freed on return
+}
+
+void kfusion::cuda::visiblePoints(const DeviceArray<Point>& vertices, const DeviceArray<int>& triangles, const DeviceArray<Point>& points,
+                                  const float eye[3], float margin, std::vector<unsigned char>& visible)
+{
+    std::vector<Point> p;
+    points.download(p);
+    std::vector<Point> o(p.size()), d(p.size());
+    for (size_t i = 0; i < p.size(); ++i)
+        for (int k = 0; k < 4; ++k) {
+            o[i].data[k] = k < 3 ? eye[k] : 0.0f;
+            d[i].data[k] = p[i].data[k] - o[i].data[k];
+        }
+    DeviceArray<Point> od, dd, hit; DeviceArray<int> triangle;
+    if (!p.empty()) { od.upload(o.data(), o.size()); dd.upload(d.data(), d.size()); }
+    cuda::rayHits(vertices, triangles, od, dd, 0.0f, 1.0f - margin, DF_RAYS_ANY_HIT, triangle, hit);
+    std::vector<int> tri;
+    triangle.download(tri);
+    visible.resize(p.size());
+    for (size_t i = 0; i < p.size(); ++i)
+        visible[i] = (unsigned int)tri[i] == 0xffffffffu && std::isfinite(p[i].data[0]) && std::isfinite(p[i].data[1]) && std::isfinite(p[i].data[2]);
+}
+
 // ------------------------------------------------------------------------------------------ ColorVolume (include/dfusion.h dfusion_color_*)
 ColorVolume::ColorVolume(const TsdfVolume& volume) : volume_(&volume)
 {

@@ -3,7 +3,8 @@ pieces (include/dfusion.h dfusion_mesh_components / dfusion_mesh_filter / dfusio
 simplified by vertex clustering (dfusion_mesh_simplify), its vertex adjacency with the edge statistics (dfusion_mesh_adjacency) and Taubin
 smoothing over it (dfusion_mesh_smooth), its closed boundary loops (dfusion_mesh_boundary_loops) and the mesh with the small ones
 filled (dfusion_mesh_fill_holes), and the closest point of the mesh to every query point with the distances between two meshes
-(dfusion_mesh_closest_points).  Device tensors in, device tensors out; all compute is in libdfusion_hip.so."""
+(dfusion_mesh_closest_points), and what every ray hits first on the mesh with the visibility of points from an eye
+(dfusion_mesh_ray_hits).  Device tensors in, device tensors out; all compute is in libdfusion_hip.so."""
 import math
 import struct
 
@@ -301,3 +302,52 @@ def mesh_distance(vertices_a, triangles_a, vertices_b, triangles_b):
     ab = _one_sided(vertices_a, vertices_b, triangles_b)
     ba = _one_sided(vertices_b, vertices_a, triangles_a)
     return {"a_to_b": ab, "b_to_a": ba, "hausdorff": max(ab["max"], ba["max"])}
+
+
+RAYS_ANY_HIT = 1                                         # DF_RAYS_ANY_HIT
+RAY_COUNT_NAMES = ("hits", "misses", "eligible_triangles", "skipped_triangles", "invalid_rays", "reserved", "triangle_tests", "nodes_visited")
+
+
+def ray_hits(vertices, triangles, origins, directions, t_min=0.0, t_max=None, any_hit=False, return_barycentric=False, return_counts=False):
+    """For every ray o + t d, t in [t_min, t_max], the first eligible triangle of the mesh that it hits (include/dfusion.h
+    dfusion_mesh_ray_hits has the rule; a linear BVH is built inside the call).  vertices float32 [V, 4], triangles int32 [T, 3] (uint32
+    bits), origins and directions float32 [R, 4] (w ignored; d is used as given, t is in units of d), t_max None: no limit ->
+    (triangle int32 [R] (uint32 bits; 0xffffffff without a hit), hit float32 [R, 4]: x, y, z and t); with return_barycentric also bary
+    float32 [R, 4] (1 - u - v, u, v, side: +1 where the ray meets the face whose corners it sees run counter-clockwise, else -1); with
+    return_counts also counts int64 [8] (RAY_COUNT_NAMES).  any_hit: only (triangle,) -- 0 where the ray hits anything, else 0xffffffff
+    -- and the counts on request; the walk stops at the first hit.  Nothing synchronises."""
+    tp, nt = _triangles(triangles)
+    nv, nr = _points4(vertices, "vertices"), _points4(origins, "origins")
+    if _points4(directions, "directions") != nr:
+        raise ValueError("%d origins, %d directions" % (nr, int(directions.shape[0])))
+    if vertices.device != triangles.device or origins.device != triangles.device or directions.device != triangles.device:
+        raise ValueError("vertices on %s, triangles on %s, origins on %s, directions on %s" % (vertices.device, triangles.device, origins.device,
+                                                                                             directions.device))
+    if any_hit and return_barycentric:
+        raise ValueError("any_hit gives no barycentrics")
+    dev = triangles.device
+    tri = torch.empty(nr, dtype=torch.int32, device=dev)
+    hit = None if any_hit else torch.empty((nr, 4), dtype=torch.float32, device=dev)
+    bary = torch.empty((nr, 4), dtype=torch.float32, device=dev) if return_barycentric else None
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    capi.check(capi.lib().dfusion_mesh_ray_hits(_flat(vertices) if nv else None, nv, tp, nt, _flat(origins) if nr else None,
+                                                _flat(directions) if nr else None, nr, float(t_min), float("inf") if t_max is None else float(t_max),
+                                                RAYS_ANY_HIT if any_hit else 0, _flat(tri) if nr else None, _flat(hit) if hit is not None and nr else None,
+                                                _flat(bary) if return_barycentric and nr else None, _flat(counts), _stream()), "dfusion_mesh_ray_hits")
+    return (tri,) + (() if any_hit else (hit,)) + ((bary,) if return_barycentric else ()) + ((counts,) if return_counts else ())
+
+
+def visible_points(vertices, triangles, points, eye, margin=2.0 ** -10):
+    """bool [N]: which of `points` (float32 [N, 4], w ignored) the eye sees: the segment from the eye to the point p, as the ray o = eye,
+    d = p - eye (one f32 subtraction) on [0, 1 - margin] (the f32 difference), hits no triangle of the mesh (an any-hit ray_hits).
+    `margin` is the share of the segment in front of p that is not looked at -- a point of the surface itself is not hidden by its
+    own triangles --, a parameter of the query and no tolerance.  A point with a non-finite coordinate is not visible.  eye: three
+    numbers, or a tensor of three.  Nothing synchronises."""
+    n = _points4(points, "points")
+    e = torch.as_tensor(eye, dtype=torch.float32).reshape(-1)[:3].to(points.device)
+    o = torch.zeros_like(points)
+    o[:, :3] = e
+    d = points - o
+    t_max = float(torch.tensor(1.0, dtype=torch.float32) - torch.tensor(float(margin), dtype=torch.float32))      # on the host
+    tri, = ray_hits(vertices, triangles, o, d, 0.0, t_max, any_hit=True)
+    return (tri == -1) & torch.isfinite(points[:, :3]).all(1) if n else torch.zeros(0, dtype=torch.bool, device=points.device)

@@ -578,6 +578,59 @@ int dfusion_mesh_closest_points(const float *vertices_dev, unsigned long long n_
                                 float *bary_dev /* nullable, 4 n_queries */,
                                 unsigned long long *counts_dev /* [8] */, dfStream stream);
 
+/* Ray queries against a triangle mesh: for every ray the first eligible triangle it hits -- or, with DF_RAYS_ANY_HIT, whether it hits
+ * any --, the hit point with its parameter and the barycentrics, through the linear BVH of dfusion_mesh_closest_points, built inside
+ * the call (no reference counterpart; additive, ABI 7).  DESIGN.md section 29 has the kernel and the proof that the tree only prunes;
+ * tests/mesh_rays_ref.py restates the rule in numpy by brute force over all triangles, and triangle, hit, bary and counts [0] - [5]
+ * equal it bit for bit.
+ * Inputs: V vertices of four floats (w ignored), T triangles of three uint32 indices, R rays as origins o and directions d of four
+ * floats each (w ignored), t_min and t_max (f32, for every ray).  d is used as given, never normalised: t is in units of d.
+ * Every operation below is ONE f32 operation, nothing is fused, dot(x, y) = x.x*y.x + x.y*y.y + x.z*y.z added left to right, a cross
+ * product component is a*b - c*d as two products and one difference, divisions are IEEE f32.  min(a, b) and max(a, b) are fminf and
+ * fmaxf -- a NaN operand is dropped -- with the one case IEEE leaves open pinned: of two EQUAL operands (zeros of either sign included)
+ * the second is returned: max(a, b) = (b is NaN || a > b) ? a : b, min alike with <.
+ *   ELIGIBLE   a triangle as for dfusion_mesh_closest_points: three indices < V, pairwise different, nine finite coordinates.  Every
+ *              other one is skipped and counted.
+ *   VALID      a ray whose o.x, o.y, o.z, d.x, d.y, d.z are finite and whose d is not (+-0, +-0, +-0).  An invalid ray hits nothing and
+ *              is counted.
+ *   TEST       Moeller-Trumbore, two-sided, of a valid ray against the triangle (A, B, C):
+ *                e1 = B - A; e2 = C - A; p = d x e2; det = dot(e1, p); inv = 1 / det;
+ *                s = o - A; u = dot(s, p) * inv; q = s x e1; v = dot(d, q) * inv; t = dot(e2, q) * inv;
+ *              the triangle is a CANDIDATE iff det != 0 && u >= 0 && v >= 0 && u + v <= 1 && t >= t_min && t <= t_max (a NaN anywhere
+ *              fails it); side = det > 0 ? +1 : -1.
+ *   BOX        Moeller-Trumbore's t has no bounded error for a long sliver hit at a grazing angle, so the rule itself carries the
+ *              triangle's vertex box [lo, hi] (per axis the fminf / fmaxf of the three coordinates) and a tree over unions of such
+ *              boxes stays exact by monotone rounding alone.  slack = m * 2^-18 + 2^-126, m = the largest |coordinate| of all
+ *              eligible triangles and of o.  slab(lo, hi), on the box grown to [lo - slack, hi + slack]: tn = -inf, tf = +inf; per
+ *              axis k = x, y, z, with inv_k = 1 / d_k: where inv_k is +-inf (d_k is zero or so small that its reciprocal overflows) the
+ *              axis is PARALLEL -- the box fails unless lo_k - slack <= o_k <= hi_k + slack, and t is not constrained --, otherwise
+ *              a = ((lo_k - slack) - o_k) * inv_k; b = ((hi_k + slack) - o_k) * inv_k; tn = max(tn, min(a, b)); tf = min(tf, max(a, b)).
+ *              Then tn = max(tn, t_min); tf = min(tf, t_max); the box PASSES iff tn <= tf.
+ *   ACCEPTED   a candidate whose own vertex box passes; t_hit = min(max(t, tn), tf) with that box's tn and tf.
+ *   WINNER     the accepted candidate with the smallest t_hit, ties to the smaller triangle index.
+ *   NO HIT     (no accepted candidate, an invalid ray): triangle 0xffffffff, hit x, y, z = the bits 0x7fc00000 and w = +inf, bary 0.
+ *   triangle_dev[r]           the winner's index; with DF_RAYS_ANY_HIT 0 if ANY candidate is accepted (whichever), else 0xffffffff.
+ *   hit_dev[4 r ..]           (o.x + d.x * t_hit, o.y + d.y * t_hit, o.z + d.z * t_hit, t_hit): one product and one sum per axis.
+ *   bary_dev[4 r ..] (nullable)  ((1 - u) - v, u, v, side).
+ *   counts_dev[8] (u64, WRITTEN, always): [0] rays with a hit, [1] without (invalid ones included), [2] eligible triangles, [3] skipped
+ *              triangles, [4] invalid rays, [5] 0, [6] triangle tests made and [7] tree nodes visited, summed over the rays: integer
+ *              sums, reproducible for one input, but a property of the tree and not of the rule.
+ * With DF_RAYS_ANY_HIT the walk stops at a ray's first accepted candidate and hit_dev and bary_dev must be NULL.
+ * T == 0, V == 0 and R == 0 are valid inputs; with R == 0 the triangles are still counted.  Arrays of length 0 may be NULL.
+ * DF_E_INVALID: V, T or R > 2^32 - 1, a flag bit other than DF_RAYS_ANY_HIT, a NULL array (bary_dev apart; hit_dev too with
+ * DF_RAYS_ANY_HIT) with a non-zero length, hit_dev or bary_dev given with DF_RAYS_ANY_HIT, counts_dev NULL, an output array (counts_dev
+ * included) that overlaps vertices_dev, triangles_dev, origins_dev or directions_dev.  Without a device DF_E_NO_DEVICE.  No
+ * device-to-host copy, no synchronisation, integer atomics only; every launch covers its range with 64-bit indices.  The tree lives in
+ * the workspace and is rebuilt by every call.  Workspace: that of dfusion_mesh_closest_points for T triangles.                          */
+#define DF_RAYS_ANY_HIT 1u
+int dfusion_mesh_ray_hits(const float *vertices_dev, unsigned long long n_vertices,
+                          const unsigned int *triangles_dev, unsigned long long n_triangles,
+                          const float *origins_dev, const float *directions_dev, unsigned long long n_rays,
+                          float t_min, float t_max, unsigned int flags,
+                          unsigned int *triangle_dev /* n_rays */, float *hit_dev /* 4 n_rays; NULL with DF_RAYS_ANY_HIT */,
+                          float *bary_dev /* nullable, 4 n_rays */,
+                          unsigned long long *counts_dev /* [8] */, dfStream stream);
+
 /* ---- colour volume (no reference counterpart: KinFu::operator() drops its colour image; additive, ABI 7) ----------------------
  * A colour volume belongs to a TSDF volume: the same dims, linear layout (x + y X + z X Y) and stored planes (DfSlab), 4 bytes a
  * voxel {c0, c1, c2, w}: three channels in the byte order of the input image (the kernels treat them alike) and a weight byte;
