@@ -17,7 +17,7 @@ SOURCES = ["dfusion_volume.hip", "dfusion_warp.hip", "dfusion_warp_nodes.hip", "
            "dfusion_raycast.hip", "dfusion_frontend.hip", "dfusion_solver.hip", "dfusion_selftest.hip", "dfusion_warp_extend.hip", "dfusion_mesh.hip", "dfusion_associate.hip", "dfusion_color.hip", "dfusion_render.hip",
            "dfusion_warp_graph.hip", "dfusion_mesh_components.hip", "dfusion_mesh_simplify.hip", "dfusion_mesh_smooth.hip", "dfusion_mesh_holes.hip", "dfusion_mesh_bvh.hip", "dfusion_mesh_rays.hip"]
 HEADERS = ["dfusion_device.h", "dfusion_internal.h", "dfusion_nanoflann.h", "dfusion_pyramid.h", "dfusion_warp_topk.h", "dfusion_warp_sweep.h",
-           "dfusion_warp_blocks.h", "dfusion_warp_pipe.h", "dfusion_plan_halves.h", "dfusion_warp_decide.h", "dfusion_mesh_cc.h", "dfusion_mesh_uses.h", "dfusion_mesh_bvh.h", os.path.join(REPO_DIR, "include", "dfusion.h")]
+           "dfusion_warp_blocks.h", "dfusion_warp_pipe.h", "dfusion_plan_halves.h", "dfusion_warp_decide.h", "dfusion_mesh_cc.h", "dfusion_mesh_kit.h", "dfusion_mesh_uses.h", "dfusion_mesh_bvh.h", os.path.join(REPO_DIR, "include", "dfusion.h")]
 
 # -ffp-contract=off: fused multiply-adds only where the reference writes __fmaf_rn (explicit fmaf);
 # that is what makes the kernels bit-comparable with the IEEE CPU oracle.

@@ -1,10 +1,10 @@
 // dfusion_mesh_bvh.h -- what the two users of the linear BVH over an indexed triangle mesh share: dfusion_mesh_closest_points
 // (dfusion_mesh_bvh.hip) and dfusion_mesh_ray_hits (dfusion_mesh_rays.hip).  The build stages -- bounds, codes, sort, tree, boxes; DESIGN
 // section 28 -- exist ONCE, as kernels of dfusion_mesh_bvh.hip behind df_mbv_build; this header holds the argument block, the workspace
-// layout, the order-preserving float keys the boxes are stored as, and the counting helper.  The tree lives in the caller's workspace and
-// is rebuilt by every call: nothing here outlives the call that built it.
+// layout and the order-preserving float keys the boxes are stored as; grids, the overlap test and the counting are the mesh kit's
+// (dfusion_mesh_kit.h).  The tree lives in the caller's workspace and is rebuilt by every call: nothing here outlives the call that built it.
 #pragma once
-#include "dfusion_mesh_uses.h"
+#include "dfusion_mesh_kit.h"
 
 #define DF_MBV_NONE 0xffffffffu
 #define DF_MBV_STACK 64                              // (dfusion_mesh_bvh.hip derives it: at most 62 internal nodes on a root-to-leaf path)
@@ -28,19 +28,6 @@ struct DfMbvArgs {
 __device__ __forceinline__ uint32_t mbv_key(float f) { const uint32_t b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : b ^ 0x80000000u; }
 __device__ __forceinline__ float mbv_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? k ^ 0x80000000u : ~k); }
 __device__ __forceinline__ bool mbv_finite(float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; }
-
-// counts[slot[j]] += the workgroup's sum of value[j], through LDS: one global atomic per workgroup and slot.  Every lane calls it, once.
-template <int K>
-__device__ __forceinline__ void mbv_block_add(unsigned long long* counts, const int (&slot)[K], const unsigned long long (&value)[K])
-{
-    __shared__ unsigned long long acc[K];
-    if (threadIdx.x < K) acc[threadIdx.x] = 0ull;
-    __syncthreads();
-    for (int j = 0; j < K; ++j)
-        if (value[j]) atomicAdd(&acc[j], value[j]);
-    __syncthreads();
-    if (threadIdx.x < K && acc[threadIdx.x]) atomicAdd(&counts[slot[threadIdx.x]], acc[threadIdx.x]);
-}
 
 // The workspace, front to back (every array rounded up to 16 bytes): [keys as emitted 8 T] [sorted keys 8 T] [split 4 T] [flags T]
 // [parents of internal nodes 4 T, of leaves 4 T] [boxes of internal nodes 24 T, of leaves 24 T] [bounds 32] [top 16]

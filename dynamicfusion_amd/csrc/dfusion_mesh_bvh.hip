@@ -18,7 +18,7 @@
 //   query     one lane per query: an iterative walk from the root, nearer child first, a subtree pruned iff its lower bound is > best
 //             (strictly, so an equal distance with a smaller index is still reached); the bound carries the slack of DESIGN section 28
 //   finish    one lane: counts [4] and [5] from the packed maximum
-// Every grid is capped at DF_MSM_MAX_BLOCKS workgroups (524 288 lanes) and strides over its range with 64-bit indices.
+// Every grid is capped at DF_MESH_MAX_BLOCKS workgroups (524 288 lanes) and strides over its range with 64-bit indices.
 // The stages bounds .. boxes are also what dfusion_mesh_ray_hits (dfusion_mesh_rays.hip) builds its tree with: df_mbv_plan and df_mbv_build
 // below run them for both; what the two files share is declared in dfusion_mesh_bvh.h.
 //
@@ -26,18 +26,19 @@
 // keys share a prefix of d bits, 2 <= d <= 63 (two different keys differ somewhere), and a child's prefix is strictly longer than its
 // parent's.  So a root-to-leaf path holds at most 62 internal nodes.  The walk pushes at most one entry (the farther child) per
 // internal node on the current path and only internal nodes are ever pushed, so at most 62 entries are live: DF_MBV_STACK = 64.
+#include <hipcub/hipcub.hpp>                          // the sort of the codes
 #include "dfusion_mesh_bvh.h"
 #include <math.h>
 
 #pragma clang fp contract(off)                       // the routine is single f32 operations in a written order; nothing here may fuse
 
-// ELIGIBLE: three indices < V (tested before anything is indexed), pairwise different, nine finite coordinates.
-__device__ __forceinline__ bool mbv_load(const DfMbvArgs& a, size_t t, float4& A, float4& B, float4& C)
+// ELIGIBLE: three indices < V (df_mesh_load tests them before anything is indexed), pairwise different, nine finite coordinates.
+__device__ __forceinline__ bool mbv_eligible(const DfMbvArgs& a, size_t t, float4& A, float4& B, float4& C)
 {
-    const uint32_t i0 = a.tris[3 * t], i1 = a.tris[3 * t + 1], i2 = a.tris[3 * t + 2];
-    if (!((size_t)i0 < a.V && (size_t)i1 < a.V && (size_t)i2 < a.V)) return false;
-    if (i0 == i1 || i1 == i2 || i0 == i2) return false;
-    A = a.P[i0]; B = a.P[i1]; C = a.P[i2];
+    uint32_t i[3];
+    if (!df_mesh_load(a.tris, t, a.T, (uint32_t)a.V, i)) return false;   // (V < 2^32)
+    if (i[0] == i[1] || i[1] == i[2] || i[0] == i[2]) return false;
+    A = a.P[i[0]]; B = a.P[i[1]]; C = a.P[i[2]];
     return mbv_finite(A.x) && mbv_finite(A.y) && mbv_finite(A.z) && mbv_finite(B.x) && mbv_finite(B.y) && mbv_finite(B.z) &&
            mbv_finite(C.x) && mbv_finite(C.y) && mbv_finite(C.z);
 }
@@ -50,22 +51,20 @@ __global__ __launch_bounds__(256) void df_mbv_bounds_kernel(const DfMbvArgs a)
     uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < a.T; t += (size_t)gridDim.x * 256) {
         float4 A, B, C;
-        if (mbv_load(a, t, A, B, C)) {
+        if (mbv_eligible(a, t, A, B, C)) {
             ++n_el;
             const uint32_t k[3] = {mbv_key(mbv_centroid(A.x, B.x, C.x)), mbv_key(mbv_centroid(A.y, B.y, C.y)), mbv_key(mbv_centroid(A.z, B.z, C.z))};
             for (int j = 0; j < 3; ++j) { lo[j] = k[j] < lo[j] ? k[j] : lo[j]; hi[j] = k[j] > hi[j] ? k[j] : hi[j]; }
         } else ++n_skip;
     }
     for (int j = 0; j < 3; ++j) {                                        // the wave's box by shuffles, one atomic per wave and word
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint32_t l = (uint32_t)__shfl_xor((int)lo[j], off, 64), h = (uint32_t)__shfl_xor((int)hi[j], off, 64);
-            lo[j] = l < lo[j] ? l : lo[j]; hi[j] = h > hi[j] ? h : hi[j];
-        }
+        lo[j] = ~df_mesh_wave_max(~lo[j]);                               // (a minimum is the complement of the complements' maximum)
+        hi[j] = df_mesh_wave_max(hi[j]);
         if ((threadIdx.x & 63) == 0 && lo[j] <= hi[j]) { atomicMin(&a.bounds[j], lo[j]); atomicMax(&a.bounds[4 + j], hi[j]); }
     }
     const int slot[2] = {2, 3};
     const unsigned long long n[2] = {n_el, n_skip};
-    mbv_block_add(a.counts, slot, n);
+    df_mesh_block_add(a.counts, slot, n);
 }
 
 // 10 bits -> every third bit of 30.
@@ -89,7 +88,7 @@ __global__ __launch_bounds__(256) void df_mbv_codes_kernel(const DfMbvArgs a)
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < a.T; t += (size_t)gridDim.x * 256) {
         float4 A, B, C;
         unsigned long long key = ~0ull;
-        if (mbv_load(a, t, A, B, C)) {
+        if (mbv_eligible(a, t, A, B, C)) {
             const uint32_t code = mbv_spread(mbv_cell(mbv_centroid(A.x, B.x, C.x), lx, hx)) << 2 | mbv_spread(mbv_cell(mbv_centroid(A.y, B.y, C.y), ly, hy)) << 1 |
                                   mbv_spread(mbv_cell(mbv_centroid(A.z, B.z, C.z), lz, hz));
             key = (unsigned long long)code << 32 | (unsigned long long)t;
@@ -286,7 +285,7 @@ __global__ __launch_bounds__(256) void df_mbv_query_kernel(const DfMbvArgs a)
     if (top) atomicMax(&wg_top, top);
     const int slot[4] = {0, 1, 6, 7};
     const unsigned long long n[4] = {n_hit, n_miss, n_tests, n_nodes};
-    mbv_block_add(a.counts, slot, n);                                    // (synchronises: wg_top is complete behind it)
+    df_mesh_block_add(a.counts, slot, n);                                // (synchronises: wg_top is complete behind it)
     if (threadIdx.x == 0 && wg_top) atomicMax(a.top, wg_top);
 }
 
@@ -313,14 +312,13 @@ __global__ __launch_bounds__(256) void df_mbv_none_kernel(const DfMbvArgs a)
 
 int df_mbv_plan(size_t T, hipStream_t st, DfMbvLayout* l)
 {
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += df_msm_up16(bytes); return o; };
-    take(T * 8); l->o_keys = take(T * 8); l->o_split = take(T * 4); l->o_flags = take(T); l->o_par_i = take(T * 4); l->o_par_l = take(T * 4);
-    l->o_box_i = take(T * 24); l->o_box_l = take(T * 24); l->o_bounds = take(32); l->o_top = take(16);
-    l->o_cub = (at + 255) / 256 * 256;
     l->cub_bytes = 0;
     DF_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, l->cub_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, T, 0, 64, st));
-    l->total = l->o_cub + l->cub_bytes;
+    DfMeshCarve c; c.take(T * 8);                                         // (the keys as emitted, at the front)
+    l->o_keys = c.take(T * 8); l->o_split = c.take(T * 4); l->o_flags = c.take(T); l->o_par_i = c.take(T * 4); l->o_par_l = c.take(T * 4);
+    l->o_box_i = c.take(T * 24); l->o_box_l = c.take(T * 24); l->o_bounds = c.take(32); l->o_top = c.take(16);
+    l->o_cub = c.take(l->cub_bytes, 256);
+    l->total = c.total();
     return DF_OK;
 }
 
@@ -331,7 +329,7 @@ int df_mbv_build(DfMbvArgs& a, const DfMbvLayout& l, char* ws, bool tree, hipStr
     a.par_i = (uint32_t*)(ws + l.o_par_i); a.par_l = (uint32_t*)(ws + l.o_par_l);
     a.box_i = (uint32_t*)(ws + l.o_box_i); a.box_l = (uint32_t*)(ws + l.o_box_l);
     a.bounds = (uint32_t*)(ws + l.o_bounds); a.top = (unsigned long long*)(ws + l.o_top);
-    const dim3 wg(256), gt(df_msm_blocks(a.T));
+    const dim3 wg(256), gt(df_mesh_blocks(a.T));
     DF_HIP(hipMemsetAsync(a.bounds, 0xff, 16, st));
     DF_HIP(hipMemsetAsync(a.bounds + 4, 0, 16 + 16, st));                 // the maxima and, behind them, top
     hipLaunchKernelGGL(df_mbv_bounds_kernel, gt, wg, 0, st, a);
@@ -359,7 +357,7 @@ extern "C" int dfusion_mesh_closest_points(const float* vertices_dev, unsigned l
     const size_t V = (size_t)n_vertices, T = (size_t)n_triangles, Q = (size_t)n_queries;
     const struct { const void* p; size_t n; } outs[4] = {{triangle_dev, Q * 4}, {point_dev, Q * 16}, {bary_dev, Q * 16}, {counts_dev, 64}};
     for (const auto& o : outs)
-        if (msm_overlap(vertices_dev, V * 16, o.p, o.n) || msm_overlap(triangles_dev, T * 12, o.p, o.n) || msm_overlap(queries_dev, Q * 16, o.p, o.n))
+        if (df_mesh_overlap(vertices_dev, V * 16, o.p, o.n) || df_mesh_overlap(triangles_dev, T * 12, o.p, o.n) || df_mesh_overlap(queries_dev, Q * 16, o.p, o.n))
             return DF_E_INVALID;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return DF_E_NO_DEVICE;
@@ -370,7 +368,7 @@ extern "C" int dfusion_mesh_closest_points(const float* vertices_dev, unsigned l
     a.V = V; a.T = T; a.Q = Q;
     a.P = (const float4*)vertices_dev; a.tris = triangles_dev; a.q = (const float4*)queries_dev; a.max_d2 = max_dist2;
     a.counts = counts_dev; a.out_t = triangle_dev; a.out_p = (float4*)point_dev; a.out_b = (float4*)bary_dev;
-    const dim3 wg(256), gq(df_msm_blocks(Q));
+    const dim3 wg(256), gq(df_mesh_blocks(Q));
     if (!T) {
         if (Q) { hipLaunchKernelGGL(df_mbv_none_kernel, gq, wg, 0, st, a); DF_LAUNCH_CHECK(); }
         hipLaunchKernelGGL(df_mbv_finish_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long*)nullptr, counts_dev);

@@ -12,17 +12,17 @@
 //                totals    the four counts by integer adds and an integer maximum
 //   filter       best      with keep_largest: max over r of (triangle_count[r] << 32 | ~r): most triangles, then the smaller label
 //                keep      a flag per kept triangle, a flag per vertex a kept triangle uses (plain stores of 1)
-//                scan      two hipcub exclusive sums, in place, one spare element each for the total
+//                scan      df_mesh_scan_pair: two hipcub exclusive sums, in place, one spare element each for the total
 //                compact   triangles rewritten through the scanned vertex offsets; vertex_src / vertex_map
 // Every grid is capped and strides over its range with 64-bit indices, so a launch covers any T and V the ABI admits.
+// Grids, loads, sums and the scan tail are the mesh kit's (dfusion_mesh_kit.h); its host launchers are defined at the end of this file.
 #include <hipcub/hipcub.hpp>
-#include "dfusion_internal.h"
+#include "dfusion_mesh_kit.h"
 #include "dfusion_mesh_cc.h"
 
+// Deliberately not the kit's 2048: nobody has measured this file's kernels with fewer workgroups.  (The two reductions cap theirs at 1024.)
 #define DF_MCC_MAX_BLOCKS (256u * 32u)
 #define DF_MCC_NONE 0xffffffffu
-
-static inline unsigned df_mcc_blocks(size_t n) { const size_t b = (n + 255) / 256; return (unsigned)(b < DF_MCC_MAX_BLOCKS ? b : DF_MCC_MAX_BLOCKS); }
 
 // parent[] in device memory.  A plain load may be served from a CU's L1 and see a stale root; these go to the L2, where the
 // compare-and-swap is decided.
@@ -32,13 +32,6 @@ struct DfCcDeviceMem {
     __device__ __forceinline__ void store(uint32_t i, uint32_t v) const { __hip_atomic_store(p + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     __device__ __forceinline__ uint32_t cas(uint32_t i, uint32_t expect, uint32_t v) const { return atomicCAS(p + i, expect, v); }
 };
-
-__device__ __forceinline__ bool mcc_load(const uint32_t* tris, size_t t, size_t T, uint32_t V, uint32_t (&i)[3])
-{
-    if (t >= T) { i[0] = i[1] = i[2] = 0u; return false; }
-    i[0] = tris[3 * t]; i[1] = tris[3 * t + 1]; i[2] = tris[3 * t + 2];
-    return i[0] < V && i[1] < V && i[2] < V;                                // tested before anything is indexed
-}
 
 __global__ __launch_bounds__(256) void df_mcc_init_kernel(uint32_t* parent, size_t V, uint32_t* tcount, uint8_t* used)
 {
@@ -54,7 +47,7 @@ __global__ __launch_bounds__(256) void df_mcc_union_kernel(const uint32_t* tris,
     DfCcDeviceMem m{parent};
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < T; t += (size_t)gridDim.x * 256) {
         uint32_t i[3];
-        if (!mcc_load(tris, t, T, V, i)) continue;
+        if (!df_mesh_load(tris, t, T, V, i)) continue;
         if (i[0] != i[1]) df_cc_union(m, i[0], i[1]);                       // (edges (i0, i1) and (i1, i2) connect all three)
         if (i[1] != i[2]) df_cc_union(m, i[1], i[2]);
     }
@@ -69,13 +62,6 @@ __global__ __launch_bounds__(256) void df_mcc_flatten_kernel(uint32_t* parent, s
         m.store((uint32_t)v, df_cc_root(m, (uint32_t)v));
 }
 
-__device__ __forceinline__ unsigned long long mcc_wave_max(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const unsigned long long o = __shfl_xor(v, d, 64); v = o > v ? o : v; }
-    return v;
-}
-
 __global__ __launch_bounds__(256) void df_mcc_count_kernel(const uint32_t* tris, size_t T, uint32_t V, const uint32_t* label, uint32_t* tcount,
                                                            uint8_t* used, unsigned long long* counts)
 {
@@ -84,7 +70,7 @@ __global__ __launch_bounds__(256) void df_mcc_count_kernel(const uint32_t* tris,
     for (size_t t0 = (size_t)blockIdx.x * 256; t0 < T; t0 += (size_t)gridDim.x * 256) {   // (workgroup-uniform trip count)
         const size_t t = t0 + threadIdx.x;
         uint32_t i[3];
-        const bool valid = mcc_load(tris, t, T, V, i);
+        const bool valid = df_mesh_load(tris, t, T, V, i);
         n_invalid += (unsigned long long)__popcll(__ballot(t < T && !valid));
         uint32_t r = 0u;
         if (valid) { r = label[i[0]]; used[i[0]] = 1; used[i[1]] = 1; used[i[2]] = 1; }
@@ -98,12 +84,11 @@ __global__ __launch_bounds__(256) void df_mcc_count_kernel(const uint32_t* tris,
             todo &= ~same;
         }
     }
-    if (counts && lane == 0 && n_invalid) atomicAdd(&counts[2], n_invalid);
+    if (counts) df_mesh_wave_add(counts, 2, n_invalid);
 }
 
 __global__ __launch_bounds__(256) void df_mcc_totals_kernel(const uint32_t* tcount, const uint8_t* used, size_t V, unsigned long long* counts)
 {
-    const int lane = threadIdx.x & 63;
     unsigned long long n_comp = 0ull, n_unused = 0ull, largest = 0ull;      // the first two wave-uniform
     for (size_t v0 = (size_t)blockIdx.x * 256; v0 < V; v0 += (size_t)gridDim.x * 256) {
         const size_t v = v0 + threadIdx.x;
@@ -112,17 +97,10 @@ __global__ __launch_bounds__(256) void df_mcc_totals_kernel(const uint32_t* tcou
         n_unused += (unsigned long long)__popcll(__ballot(v < V && used[v] == 0));
         largest = c > largest ? c : largest;
     }
-    largest = mcc_wave_max(largest);
-    if (lane == 0) {
-        if (n_comp) atomicAdd(&counts[0], n_comp);
-        if (n_unused) atomicAdd(&counts[1], n_unused);
-        if (largest) atomicMax(&counts[3], largest);
-    }
-}
-
-__global__ void df_mcc_set_kernel(unsigned long long* dst, unsigned long long value)
-{
-    if (threadIdx.x == 0 && blockIdx.x == 0) *dst = value;
+    largest = df_mesh_wave_max(largest);
+    df_mesh_wave_add(counts, 0, n_comp);
+    df_mesh_wave_add(counts, 1, n_unused);
+    if ((threadIdx.x & 63) == 0 && largest) atomicMax(&counts[3], largest);
 }
 
 extern "C" int dfusion_mesh_components(const unsigned int* triangles_dev, unsigned long long n_triangles, unsigned long long n_vertices,
@@ -137,32 +115,32 @@ extern "C" int dfusion_mesh_components(const unsigned int* triangles_dev, unsign
     const size_t T = (size_t)n_triangles, V = (size_t)n_vertices;
     if (counts_dev) DF_HIP(hipMemsetAsync(counts_dev, 0, 32, st));
     if (!V) {                                                                                   // every triangle is invalid
-        if (counts_dev && T) { hipLaunchKernelGGL(df_mcc_set_kernel, dim3(1), dim3(64), 0, st, counts_dev + 2, n_triangles); DF_LAUNCH_CHECK(); }
+        if (counts_dev && T) DF_TRY(df_mesh_set_counts(counts_dev, 2, n_triangles, 2, n_triangles, st));
         return DF_OK;
     }
     const bool counting = triangle_count_dev || counts_dev;
     // workspace: [used flags: V bytes | triangle counts: 4 V bytes, when the caller keeps none]
-    const size_t o_cnt = (V + 15) / 16 * 16;
+    const size_t o_cnt = df_mesh_up16(V);
     DfScratchHold hold(st, counting ? o_cnt + (triangle_count_dev ? 0 : V * 4) : 16);           // held until the last launch is enqueued
     if (!hold.entry) return (int)hipErrorOutOfMemory;
     uint8_t* used = counting ? (uint8_t*)hold.mem : nullptr;
     uint32_t* tcount = triangle_count_dev ? triangle_count_dev : counting ? (uint32_t*)(hold.mem + o_cnt) : nullptr;
-    hipLaunchKernelGGL(df_mcc_init_kernel, dim3(df_mcc_blocks(V)), dim3(256), 0, st, vertex_label_dev, V, tcount, used);
+    hipLaunchKernelGGL(df_mcc_init_kernel, dim3(df_mesh_blocks(V, DF_MCC_MAX_BLOCKS)), dim3(256), 0, st, vertex_label_dev, V, tcount, used);
     DF_LAUNCH_CHECK();
     if (T) {
-        hipLaunchKernelGGL(df_mcc_union_kernel, dim3(df_mcc_blocks(T)), dim3(256), 0, st, triangles_dev, T, (uint32_t)V, vertex_label_dev);
+        hipLaunchKernelGGL(df_mcc_union_kernel, dim3(df_mesh_blocks(T, DF_MCC_MAX_BLOCKS)), dim3(256), 0, st, triangles_dev, T, (uint32_t)V, vertex_label_dev);
         DF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(df_mcc_flatten_kernel, dim3(df_mcc_blocks(V)), dim3(256), 0, st, vertex_label_dev, V);
+        hipLaunchKernelGGL(df_mcc_flatten_kernel, dim3(df_mesh_blocks(V, DF_MCC_MAX_BLOCKS)), dim3(256), 0, st, vertex_label_dev, V);
         DF_LAUNCH_CHECK();
     }
     if (!counting) return DF_OK;
     if (T) {
-        hipLaunchKernelGGL(df_mcc_count_kernel, dim3(df_mcc_blocks(T)), dim3(256), 0, st, triangles_dev, T, (uint32_t)V,
+        hipLaunchKernelGGL(df_mcc_count_kernel, dim3(df_mesh_blocks(T, DF_MCC_MAX_BLOCKS)), dim3(256), 0, st, triangles_dev, T, (uint32_t)V,
                            (const uint32_t*)vertex_label_dev, tcount, used, counts_dev);
         DF_LAUNCH_CHECK();
     }
     if (counts_dev) {
-        hipLaunchKernelGGL(df_mcc_totals_kernel, dim3(df_mcc_blocks(V) < 1024u ? df_mcc_blocks(V) : 1024u), dim3(256), 0, st,
+        hipLaunchKernelGGL(df_mcc_totals_kernel, dim3(df_mesh_blocks(V, 1024u)), dim3(256), 0, st,
                            (const uint32_t*)tcount, (const uint8_t*)used, V, counts_dev);
         DF_LAUNCH_CHECK();
     }
@@ -188,7 +166,7 @@ __global__ __launch_bounds__(256) void df_mcc_best_kernel(const uint32_t* tcount
         const unsigned long long k = ((unsigned long long)tcount[v] << 32) | (unsigned long long)(DF_MCC_NONE - (uint32_t)v);
         key = k > key ? k : key;
     }
-    key = mcc_wave_max(key);
+    key = df_mesh_wave_max(key);
     if ((threadIdx.x & 63) == 0 && key) atomicMax(best, key);
 }
 
@@ -197,17 +175,12 @@ __global__ __launch_bounds__(256) void df_mcc_keep_kernel(const DfMccFilterArgs 
     const uint32_t only = a.keep_largest ? DF_MCC_NONE - (uint32_t)(*a.best & 0xffffffffull) : 0u;
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < a.T; t += (size_t)gridDim.x * 256) {
         uint32_t i[3];
-        if (!mcc_load(a.tris, t, a.T, a.V, i)) continue;
+        if (!df_mesh_load(a.tris, t, a.T, a.V, i)) continue;
         const uint32_t r = a.label[i[0]];
         if (r >= a.V || (unsigned long long)a.tcount[r] < a.min_triangles || (a.keep_largest && r != only)) continue;
         a.tscan[t] = 1u;
         a.vscan[i[0]] = 1u; a.vscan[i[1]] = 1u; a.vscan[i[2]] = 1u;
     }
-}
-
-__global__ void df_mcc_filter_totals_kernel(const uint32_t* tscan, const uint32_t* vscan, size_t T, size_t V, unsigned long long* counts)
-{
-    if (threadIdx.x == 0 && blockIdx.x == 0) { counts[0] = vscan[V]; counts[1] = tscan[T]; }
 }
 
 __global__ __launch_bounds__(256) void df_mcc_compact_triangles_kernel(const DfMccFilterArgs a)
@@ -256,33 +229,29 @@ extern "C" int dfusion_mesh_filter(const unsigned int* triangles_dev, unsigned l
     }
     // workspace (zeroed): [best | triangle flags / offsets [T + 1] | vertex flags / offsets [V + 1]], then hipcub's temporary storage
     const size_t V = (size_t)a.V;
-    size_t scan_t = 0, scan_v = 0;
-    DF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_t, (uint32_t*)nullptr, (uint32_t*)nullptr, a.T + 1, st));
-    DF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_v, (uint32_t*)nullptr, (uint32_t*)nullptr, V + 1, st));
-    size_t scan_bytes = scan_t > scan_v ? scan_t : scan_v;
-    const size_t o_t = 16, o_v = o_t + (a.T + 1) * 4, zero_bytes = o_v + (V + 1) * 4, o_scan = (zero_bytes + 255) / 256 * 256;
-    DfScratchHold hold(st, o_scan + scan_bytes);                                         // held until the last launch is enqueued
+    size_t scan_bytes = 0;
+    DF_TRY(df_mesh_scan_bytes((a.T > V ? a.T : V) + 1, st, &scan_bytes));
+    DfMeshCarve c; c.take(16);                                                           // (best, at the front)
+    const size_t o_t = c.take((a.T + 1) * 4, 4), o_v = c.take((V + 1) * 4, 4), zero_bytes = c.total(), o_scan = c.take(scan_bytes, 256);
+    DfScratchHold hold(st, c.total());                                                   // held until the last launch is enqueued
     if (!hold.entry) return (int)hipErrorOutOfMemory;
     char* const ws = hold.mem;
     a.best = (unsigned long long*)ws; a.tscan = (uint32_t*)(ws + o_t); a.vscan = (uint32_t*)(ws + o_v);
     DF_HIP(hipMemsetAsync(ws, 0, zero_bytes, st));
     if (a.keep_largest) {
-        hipLaunchKernelGGL(df_mcc_best_kernel, dim3(df_mcc_blocks(V) < 1024u ? df_mcc_blocks(V) : 1024u), dim3(256), 0, st, a.tcount, V, a.best);
+        hipLaunchKernelGGL(df_mcc_best_kernel, dim3(df_mesh_blocks(V, 1024u)), dim3(256), 0, st, a.tcount, V, a.best);
         DF_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(df_mcc_keep_kernel, dim3(df_mcc_blocks(a.T)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(df_mcc_keep_kernel, dim3(df_mesh_blocks(a.T, DF_MCC_MAX_BLOCKS)), dim3(256), 0, st, a);
     DF_LAUNCH_CHECK();
-    DF_HIP(hipcub::DeviceScan::ExclusiveSum(ws + o_scan, scan_bytes, a.tscan, a.tscan, a.T + 1, st));
-    DF_HIP(hipcub::DeviceScan::ExclusiveSum(ws + o_scan, scan_bytes, a.vscan, a.vscan, V + 1, st));
-    hipLaunchKernelGGL(df_mcc_filter_totals_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)a.tscan, (const uint32_t*)a.vscan, a.T, V, counts_dev);
-    DF_LAUNCH_CHECK();
+    DF_TRY(df_mesh_scan_pair(ws + o_scan, scan_bytes, a.tscan, a.T + 1, a.vscan, V + 1, counts_dev, st));
     if (!emit) return DF_OK;
     if (a.tcap) {
-        hipLaunchKernelGGL(df_mcc_compact_triangles_kernel, dim3(df_mcc_blocks(a.T)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(df_mcc_compact_triangles_kernel, dim3(df_mesh_blocks(a.T, DF_MCC_MAX_BLOCKS)), dim3(256), 0, st, a);
         DF_LAUNCH_CHECK();
     }
     if (a.vcap || a.vmap) {
-        hipLaunchKernelGGL(df_mcc_compact_vertices_kernel, dim3(df_mcc_blocks(V)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(df_mcc_compact_vertices_kernel, dim3(df_mesh_blocks(V, DF_MCC_MAX_BLOCKS)), dim3(256), 0, st, a);
         DF_LAUNCH_CHECK();
     }
     return DF_OK;
@@ -309,10 +278,44 @@ extern "C" int dfusion_gather_rows(const void* src_dev, unsigned int row_bytes, 
     if (!n) return DF_OK;
     hipStream_t st = (hipStream_t)stream;
     const size_t words = (size_t)n * (row_bytes / 4u);
-    const dim3 grid(df_mcc_blocks(words));
+    const dim3 grid(df_mesh_blocks(words, DF_MCC_MAX_BLOCKS));
     if (row_bytes == 4u) hipLaunchKernelGGL(df_mcc_gather_kernel<1>, grid, dim3(256), 0, st, (const uint32_t*)src_dev, index_dev, words, (uint32_t*)dst_dev);
     else if (row_bytes == 12u) hipLaunchKernelGGL(df_mcc_gather_kernel<3>, grid, dim3(256), 0, st, (const uint32_t*)src_dev, index_dev, words, (uint32_t*)dst_dev);
     else hipLaunchKernelGGL(df_mcc_gather_kernel<4>, grid, dim3(256), 0, st, (const uint32_t*)src_dev, index_dev, words, (uint32_t*)dst_dev);
+    DF_LAUNCH_CHECK();
+    return DF_OK;
+}
+
+// ---- the mesh kit's host launchers (dfusion_mesh_kit.h), for every mesh file
+__global__ void df_mcc_set_counts_kernel(unsigned long long* counts, int i0, unsigned long long v0, int i1, unsigned long long v1)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) { counts[i0] = v0; counts[i1] = v1; }
+}
+
+__global__ void df_mcc_scan_totals_kernel(const uint32_t* a, size_t na, const uint32_t* b, size_t nb, unsigned long long* counts)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) { counts[0] = b[nb - 1]; counts[1] = a[na - 1]; }
+}
+
+int df_mesh_set_counts(unsigned long long* counts, int i0, unsigned long long v0, int i1, unsigned long long v1, hipStream_t st)
+{
+    hipLaunchKernelGGL(df_mcc_set_counts_kernel, dim3(1), dim3(64), 0, st, counts, i0, v0, i1, v1);
+    DF_LAUNCH_CHECK();
+    return DF_OK;
+}
+
+int df_mesh_scan_bytes(size_t items_max, hipStream_t st, size_t* bytes)
+{
+    DF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, items_max, st));
+    return DF_OK;
+}
+
+int df_mesh_scan_pair(char* cub, size_t cub_bytes, uint32_t* a, size_t na, uint32_t* b, size_t nb, unsigned long long* counts, hipStream_t st)
+{
+    DF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, a, a, na, st));
+    DF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, b, b, nb, st));
+    if (!counts) return DF_OK;
+    hipLaunchKernelGGL(df_mcc_scan_totals_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)a, na, (const uint32_t*)b, nb, counts);
     DF_LAUNCH_CHECK();
     return DF_OK;
 }

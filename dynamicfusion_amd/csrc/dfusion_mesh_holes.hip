@@ -6,7 +6,7 @@
 // sum in rank order and one division.
 //
 //   uses      dfusion_mesh_uses.h: emit, sort, heads and their scan -- shared with dfusion_mesh_adjacency
-//   runs      one lane per sorted key: the head of a run counts its run (f zeros, b ones).  f == 1, b == 0: a boundary half-edge
+//   runs      one lane per sorted key: the head of a run judges its run (msm_run: f zeros, b ones).  f == 1, b == 0: a boundary half-edge
 //             src -> dst: out[src] and in[dst] are incremented, cand[src] = dst.  Neither that nor f == 1, b == 1 nor f == 0, b == 1:
 //             an irregular edge, a flag raised on both ends by integer atomicMax
 //   classify  one lane per vertex: SIMPLE iff out == 1, in == 1 and no flag; next[v]; the first record of the doubling pass
@@ -16,11 +16,11 @@
 //             jump always (DEAD spreads back from the end of an open chain)
 //   label     one lane per vertex: on a loop iff the jump is alive; label = the window's smallest index, D = its offset,
 //             L = D(next(label)) + 1, rank = (L - D) % L; a flag and L at every label vertex
-//   scans     two hipcub exclusive sums: the loops' numbers and their starts
+//   scans     df_mesh_scan_pair: two hipcub exclusive sums, the loops' numbers and their starts
 //   scatter   one lane per vertex: loop_vertices[start + rank] = v; the label vertex writes loop_start
 //   select, fill   dfusion_mesh_fill_holes (below)
-// Every grid is capped at DF_MSM_MAX_BLOCKS workgroups (524 288 lanes) and strides over its range with 64-bit indices.  Counts are
-// summed per wave from ballots, then per workgroup through LDS: one atomic per workgroup and slot.
+// Every grid is capped at DF_MESH_MAX_BLOCKS workgroups (524 288 lanes) and strides over its range with 64-bit indices.  Counts are summed
+// per wave from ballots, then per workgroup through LDS (df_mesh_block_add, lane 0 speaking for its wave): one atomic per workgroup and slot.
 #include "dfusion_mesh_uses.h"
 #include <math.h>
 
@@ -47,38 +47,8 @@ struct DfMhlArgs {
     unsigned long long* fill_counts;
 };
 
-// counts[slot[j]] += the sum over the workgroup's waves of wave_uniform[j]: one atomic per workgroup and slot.  Every lane of the
-// workgroup must call it (it synchronises), once per kernel.
-template <int K>
-__device__ __forceinline__ void mhl_block_add(unsigned long long* counts, const int (&slot)[K], const unsigned long long (&wave_uniform)[K])
-{
-    __shared__ unsigned long long part[K][4];
-    if ((threadIdx.x & 63) == 0)
-        for (int j = 0; j < K; ++j) part[j][threadIdx.x >> 6] = wave_uniform[j];
-    __syncthreads();
-    if (threadIdx.x < K) {
-        const unsigned long long s = part[threadIdx.x][0] + part[threadIdx.x][1] + part[threadIdx.x][2] + part[threadIdx.x][3];
-        if (s) atomicAdd(&counts[slot[threadIdx.x]], s);
-    }
-}
-
-// counts[slot[j]] = max(itself, every lane's value[j]): the wave's maximum by shuffles, the workgroup's through LDS.
-template <int K>
-__device__ __forceinline__ void mhl_block_max(unsigned long long* counts, const int (&slot)[K], const uint32_t (&value)[K])
-{
-    __shared__ uint32_t top[K][4];
-    for (int j = 0; j < K; ++j) {
-        uint32_t m = value[j];
-        for (int off = 32; off > 0; off >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)m, off, 64); m = o > m ? o : m; }
-        if ((threadIdx.x & 63) == 0) top[j][threadIdx.x >> 6] = m;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        uint32_t m = top[threadIdx.x][0];
-        for (int w = 1; w < 4; ++w) m = top[threadIdx.x][w] > m ? top[threadIdx.x][w] : m;
-        if (m) atomicMax(&counts[slot[threadIdx.x]], (unsigned long long)m);
-    }
-}
+// (a wave-uniform count as df_mesh_block_add takes it: from lane 0 of the wave, 0 from the others)
+__device__ __forceinline__ unsigned long long mhl_once(unsigned long long wave_uniform) { return (threadIdx.x & 63) == 0 ? wave_uniform : 0ull; }
 
 __global__ __launch_bounds__(256) void df_mhl_runs_kernel(const DfMhlArgs a)
 {
@@ -90,16 +60,15 @@ __global__ __launch_bounds__(256) void df_mhl_runs_kernel(const DfMhlArgs a)
         if (i < a.N && a.pos[i + 1] != a.pos[i]) {                       // a run head (src, dst); src != dst, both < V
             const unsigned long long key = a.keys[i];
             const uint32_t src = (uint32_t)(key >> a.k), dst = (uint32_t)(key & lo_mask);
-            unsigned long long f = 0ull, b = 0ull;                       // half-edges src -> dst, dst -> src
-            for (size_t j = i; j < a.N && a.keys[j] == key; ++j) { if (a.dir[j]) ++b; else ++f; }
-            if (f + b == 1ull) {
-                if (f) {                                                 // the edge's one use runs src -> dst
+            const DfMsmRun run = msm_run(a.keys, a.dir, a.N, i);
+            if (run.boundary()) {
+                if (run.f) {                                             // the edge's one use runs src -> dst
                     boundary = true;
                     atomicAdd(&a.out[src], 1u);
                     atomicAdd(&a.in[dst], 1u);
                     a.cand[src] = dst;                                   // several writers only where out > 1: never read then
                 }
-            } else if (!(f == 1ull && b == 1ull)) {
+            } else if (run.irregular()) {
                 atomicMax(&a.irr[src], 1u);
                 atomicMax(&a.irr[dst], 1u);
             }
@@ -107,8 +76,8 @@ __global__ __launch_bounds__(256) void df_mhl_runs_kernel(const DfMhlArgs a)
         n_boundary += (unsigned long long)__popcll(__ballot(boundary));
     }
     const int slot[1] = {2};
-    const unsigned long long n[1] = {n_boundary};
-    mhl_block_add(a.counts, slot, n);
+    const unsigned long long n[1] = {mhl_once(n_boundary)};
+    df_mesh_block_add(a.counts, slot, n);
 }
 
 __device__ __forceinline__ bool mhl_simple(const DfMhlArgs& a, size_t v) { return a.out[v] == 1u && a.in[v] == 1u && a.irr[v] == 0u; }
@@ -135,8 +104,8 @@ __global__ __launch_bounds__(256) void df_mhl_classify_kernel(const DfMhlArgs a)
         n_other += (unsigned long long)__popcll(__ballot(other));
     }
     const int slot[1] = {3};
-    const unsigned long long n[1] = {n_other};
-    mhl_block_add(a.counts, slot, n);
+    const unsigned long long n[1] = {mhl_once(n_other)};
+    df_mesh_block_add(a.counts, slot, n);
 }
 
 // Round r: the window of 2^r vertices from v takes in the window of 2^r behind it.  Reads `from` only, writes `to` only.
@@ -184,11 +153,11 @@ __global__ __launch_bounds__(256) void df_mhl_label_kernel(const DfMhlArgs a, co
         n_chain += (unsigned long long)__popcll(__ballot(chain));
     }
     const int slot[3] = {0, 1, 4};
-    const unsigned long long n[3] = {n_loops, n_on, n_chain};
-    mhl_block_add(a.counts, slot, n);
+    const unsigned long long n[3] = {mhl_once(n_loops), mhl_once(n_on), mhl_once(n_chain)};
+    df_mesh_block_add(a.counts, slot, n);
     const int mslot[1] = {5};
     const uint32_t m[1] = {longest};
-    mhl_block_max(a.counts, mslot, m);
+    df_mesh_block_max(a.counts, mslot, m);
 }
 
 // After the scans: flag[l] is the number of the loop labelled l, len[l] its start; flag[V] and len[V] are the totals.
@@ -208,11 +177,6 @@ __global__ __launch_bounds__(256) void df_mhl_scatter_kernel(const DfMhlArgs a)
     }
 }
 
-__global__ void df_mhl_set_kernel(unsigned long long* counts, int i0, unsigned long long v0, int i1, unsigned long long v1)
-{
-    if (threadIdx.x == 0 && blockIdx.x == 0) { counts[i0] = v0; counts[i1] = v1; }
-}
-
 // What the loop stage needs of the scratch behind the sorted uses, front to back (all 16-byte aligned):
 // [out, in, irr 12 V, zeroed] [cand 4 V] [next, lab, rnk 4 V each] [flag, len, sel, toff 4 (V + 1) each] [two record buffers 16 V each]
 // [eight counts] [hipcub's storage, 256-byte aligned]
@@ -220,14 +184,13 @@ struct DfMhlLayout { size_t o_cnt3, o_cand, o_next, o_lab, o_rnk, o_flag, o_len,
 
 static int mhl_plan(size_t V, size_t N, int k, hipStream_t st, DfMhlLayout* l)
 {
-    size_t at = df_msm_uses_bytes(N);
-    auto take = [&](size_t bytes) { const size_t o = at; at += df_msm_up16(bytes); return o; };
-    l->o_cnt3 = take(V * 12); l->o_cand = take(V * 4); l->o_next = take(V * 4); l->o_lab = take(V * 4); l->o_rnk = take(V * 4);
-    l->o_flag = take((V + 1) * 4); l->o_len = take((V + 1) * 4); l->o_sel = take((V + 1) * 4); l->o_toff = take((V + 1) * 4);
-    l->o_rec_a = take(V * 16); l->o_rec_b = take(V * 16); l->o_counts = take(64);
-    l->o_cub = (at + 255) / 256 * 256;
     DF_TRY(df_msm_uses_cub_bytes(N, k, (N > V ? N : V) + 1, st, &l->cub_bytes));
-    l->total = l->o_cub + l->cub_bytes;
+    DfMeshCarve c; c.take(df_msm_uses_bytes(N));
+    l->o_cnt3 = c.take(V * 12); l->o_cand = c.take(V * 4); l->o_next = c.take(V * 4); l->o_lab = c.take(V * 4); l->o_rnk = c.take(V * 4);
+    l->o_flag = c.take((V + 1) * 4); l->o_len = c.take((V + 1) * 4); l->o_sel = c.take((V + 1) * 4); l->o_toff = c.take((V + 1) * 4);
+    l->o_rec_a = c.take(V * 16); l->o_rec_b = c.take(V * 16); l->o_counts = c.take(64);
+    l->o_cub = c.take(l->cub_bytes, 256);
+    l->total = c.total();
     return DF_OK;
 }
 
@@ -249,7 +212,7 @@ static int mhl_loops(DfMhlArgs& a, const uint32_t* tris, char* ws, const DfMhlLa
     a.flag = (uint32_t*)(ws + l.o_flag); a.len = (uint32_t*)(ws + l.o_len); a.sel = (uint32_t*)(ws + l.o_sel); a.toff = (uint32_t*)(ws + l.o_toff);
     a.rec_a = (uint4*)(ws + l.o_rec_a); a.rec_b = (uint4*)(ws + l.o_rec_b);
     DF_HIP(hipMemsetAsync(a.out, 0, V * 12, st));
-    const dim3 gn(df_msm_blocks(a.N)), gv(df_msm_blocks(V + 1)), wg(256);
+    const dim3 gn(df_mesh_blocks(a.N)), gv(df_mesh_blocks(V + 1)), wg(256);
     hipLaunchKernelGGL(df_mhl_runs_kernel, gn, wg, 0, st, a);
     DF_LAUNCH_CHECK();
     hipLaunchKernelGGL(df_mhl_classify_kernel, gv, wg, 0, st, a);
@@ -284,7 +247,7 @@ extern "C" int dfusion_mesh_boundary_loops(const unsigned int* triangles_dev, un
                                                          {csr ? loop_start_dev : nullptr, ((size_t)loop_capacity + 1) * 4},
                                                          {loop_vertices_dev, (size_t)vertex_capacity * 4}, {counts_dev, 64}};
     for (const auto& o : outs)
-        if (msm_overlap(triangles_dev, T * 12, o.p, o.n)) return DF_E_INVALID;
+        if (df_mesh_overlap(triangles_dev, T * 12, o.p, o.n)) return DF_E_INVALID;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return DF_E_NO_DEVICE;
     hipStream_t st = (hipStream_t)stream;
@@ -296,7 +259,7 @@ extern "C" int dfusion_mesh_boundary_loops(const unsigned int* triangles_dev, un
             if (vertex_rank_dev) DF_HIP(hipMemsetAsync(vertex_rank_dev, 0xff, V * 4, st));
         }
         if (csr) DF_HIP(hipMemsetAsync(loop_start_dev, 0, 4, st));
-        if (!V && T) { hipLaunchKernelGGL(df_mhl_set_kernel, dim3(1), dim3(64), 0, st, counts_dev, 6, n_triangles, 7, 0ull); DF_LAUNCH_CHECK(); }
+        if (!V && T) DF_TRY(df_mesh_set_counts(counts_dev, 6, n_triangles, 7, 0ull, st));
         return DF_OK;
     }
     DfMhlArgs a;
@@ -310,10 +273,8 @@ extern "C" int dfusion_mesh_boundary_loops(const unsigned int* triangles_dev, un
     if (!hold.entry) return (int)hipErrorOutOfMemory;
     DF_TRY(mhl_loops(a, triangles_dev, hold.mem, l, st));
     if (!csr) return DF_OK;
-    char* const cub = hold.mem + l.o_cub;
-    DF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, l.cub_bytes, a.flag, a.flag, V + 1, st));
-    DF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, l.cub_bytes, a.len, a.len, V + 1, st));
-    hipLaunchKernelGGL(df_mhl_scatter_kernel, dim3(df_msm_blocks(V + 1)), dim3(256), 0, st, a);
+    DF_TRY(df_mesh_scan_pair(hold.mem + l.o_cub, l.cub_bytes, a.flag, V + 1, a.len, V + 1, nullptr, st));
+    hipLaunchKernelGGL(df_mhl_scatter_kernel, dim3(df_mesh_blocks(V + 1)), dim3(256), 0, st, a);
     DF_LAUNCH_CHECK();
     return DF_OK;
 }
@@ -343,11 +304,11 @@ __global__ __launch_bounds__(256) void df_mhl_select_kernel(const DfMhlArgs a)
         n_open += (unsigned long long)__popcll(__ballot(open));
     }
     const int slot[1] = {3};
-    const unsigned long long n[1] = {n_open};
-    mhl_block_add(a.fill_counts, slot, n);
+    const unsigned long long n[1] = {mhl_once(n_open)};
+    df_mesh_block_add(a.fill_counts, slot, n);
     const int mslot[2] = {5, 6};
     const uint32_t m[2] = {top_filled, top_open};
-    mhl_block_max(a.fill_counts, mslot, m);
+    df_mesh_block_max(a.fill_counts, mslot, m);
 }
 
 __global__ __launch_bounds__(256) void df_mhl_fill_kernel(const DfMhlArgs a)
@@ -400,7 +361,7 @@ extern "C" int dfusion_mesh_fill_holes(const float* vertices_dev, unsigned long 
     const struct { const void* p; size_t n; } outs[4] = {{vertices_out_dev, (size_t)vertex_capacity * 16}, {triangles_out_dev, (size_t)triangle_capacity * 12},
                                                          {vertex_src_dev, (size_t)vertex_capacity * 4}, {counts_dev, 64}};
     for (const auto& o : outs)
-        if (msm_overlap(vertices_dev, V * 16, o.p, o.n) || msm_overlap(triangles_dev, T * 12, o.p, o.n)) return DF_E_INVALID;
+        if (df_mesh_overlap(vertices_dev, V * 16, o.p, o.n) || df_mesh_overlap(triangles_dev, T * 12, o.p, o.n)) return DF_E_INVALID;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return DF_E_NO_DEVICE;
     hipStream_t st = (hipStream_t)stream;
@@ -420,16 +381,17 @@ extern "C" int dfusion_mesh_fill_holes(const float* vertices_dev, unsigned long 
     a.out_vcap = vertex_capacity; a.out_tcap = triangle_capacity;
     a.fill_counts = counts_dev;
     if (!V || !T) {                                                       // nothing to fill: the mesh is copied
-        hipLaunchKernelGGL(df_mhl_set_kernel, dim3(1), dim3(64), 0, st, counts_dev, 0, n_vertices, 1, n_triangles);
-        DF_LAUNCH_CHECK();
+        DF_TRY(df_mesh_set_counts(counts_dev, 0, n_vertices, 1, n_triangles, st));
         if (a.vsrc && V) {                                                // vertex_src = 0 .. V - 1: the fill kernel over no loop
-            DfScratchHold hold(st, df_msm_up16(V * 4) + df_msm_up16((V + 1) * 4) * 2 + 64);
+            DfMeshCarve c;                                                // [lab: no loop] [sel, toff, the loop stage's counts: zeroed]
+            const size_t o_lab = c.take(V * 4), o_sel = c.take((V + 1) * 4), o_toff = c.take((V + 1) * 4), o_counts = c.take(64);
+            DfScratchHold hold(st, c.total());
             if (!hold.entry) return (int)hipErrorOutOfMemory;
-            a.lab = (uint32_t*)hold.mem; a.sel = a.lab + (df_msm_up16(V * 4) / 4); a.toff = a.sel + (df_msm_up16((V + 1) * 4) / 4);
-            a.counts = (unsigned long long*)(a.toff + (df_msm_up16((V + 1) * 4) / 4));
+            a.lab = (uint32_t*)(hold.mem + o_lab); a.sel = (uint32_t*)(hold.mem + o_sel); a.toff = (uint32_t*)(hold.mem + o_toff);
+            a.counts = (unsigned long long*)(hold.mem + o_counts);
             DF_HIP(hipMemsetAsync(a.lab, 0xff, V * 4, st));
-            DF_HIP(hipMemsetAsync(a.sel, 0, (size_t)((char*)a.counts - (char*)a.sel) + 64, st));
-            hipLaunchKernelGGL(df_mhl_fill_kernel, dim3(df_msm_blocks(V + 1)), dim3(256), 0, st, a);
+            DF_HIP(hipMemsetAsync(a.sel, 0, c.total() - o_sel, st));
+            hipLaunchKernelGGL(df_mhl_fill_kernel, dim3(df_mesh_blocks(V + 1)), dim3(256), 0, st, a);
             DF_LAUNCH_CHECK();
         }
         return DF_OK;
@@ -441,12 +403,10 @@ extern "C" int dfusion_mesh_fill_holes(const float* vertices_dev, unsigned long 
     a.counts = (unsigned long long*)(hold.mem + l.o_counts);
     DF_HIP(hipMemsetAsync(a.counts, 0, 64, st));
     DF_TRY(mhl_loops(a, triangles_dev, hold.mem, l, st));
-    const dim3 gv(df_msm_blocks(V + 1)), wg(256);
+    const dim3 gv(df_mesh_blocks(V + 1)), wg(256);
     hipLaunchKernelGGL(df_mhl_select_kernel, gv, wg, 0, st, a);
     DF_LAUNCH_CHECK();
-    char* const cub = hold.mem + l.o_cub;
-    DF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, l.cub_bytes, a.sel, a.sel, V + 1, st));
-    DF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, l.cub_bytes, a.toff, a.toff, V + 1, st));
+    DF_TRY(df_mesh_scan_pair(hold.mem + l.o_cub, l.cub_bytes, a.sel, V + 1, a.toff, V + 1, nullptr, st));
     hipLaunchKernelGGL(df_mhl_fill_kernel, gv, wg, 0, st, a);
     DF_LAUNCH_CHECK();
     return DF_OK;

@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void df_mry_walk_kernel(const DfMryArgs g)
     }
     const int slot[5] = {0, 1, 4, 6, 7};
     const unsigned long long n[5] = {n_hit, n_miss, n_invalid, n_tests, n_nodes};
-    mbv_block_add(a.counts, slot, n);
+    df_mesh_block_add(a.counts, slot, n);
 }
 
 extern "C" int dfusion_mesh_ray_hits(const float* vertices_dev, unsigned long long n_vertices, const unsigned int* triangles_dev,
@@ -182,8 +182,8 @@ extern "C" int dfusion_mesh_ray_hits(const float* vertices_dev, unsigned long lo
     const size_t V = (size_t)n_vertices, T = (size_t)n_triangles, R = (size_t)n_rays;
     const struct { const void* p; size_t n; } outs[4] = {{triangle_dev, R * 4}, {hit_dev, R * 16}, {bary_dev, R * 16}, {counts_dev, 64}};
     for (const auto& o : outs)
-        if (msm_overlap(vertices_dev, V * 16, o.p, o.n) || msm_overlap(triangles_dev, T * 12, o.p, o.n) || msm_overlap(origins_dev, R * 16, o.p, o.n) ||
-            msm_overlap(directions_dev, R * 16, o.p, o.n))
+        if (df_mesh_overlap(vertices_dev, V * 16, o.p, o.n) || df_mesh_overlap(triangles_dev, T * 12, o.p, o.n) || df_mesh_overlap(origins_dev, R * 16, o.p, o.n) ||
+            df_mesh_overlap(directions_dev, R * 16, o.p, o.n))
             return DF_E_INVALID;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return DF_E_NO_DEVICE;
@@ -195,7 +195,7 @@ extern "C" int dfusion_mesh_ray_hits(const float* vertices_dev, unsigned long lo
     g.m.P = (const float4*)vertices_dev; g.m.tris = triangles_dev;
     g.m.counts = counts_dev; g.m.out_t = triangle_dev; g.m.out_p = (float4*)hit_dev; g.m.out_b = (float4*)bary_dev;
     g.o = (const float4*)origins_dev; g.d = (const float4*)directions_dev; g.t_min = t_min; g.t_max = t_max; g.any = any ? 1u : 0u;
-    const dim3 wg(256), gr(df_msm_blocks(R));
+    const dim3 wg(256), gr(df_mesh_blocks(R));
     if (!T) {                                                            // counts [2] stays 0: the walk indexes nothing of the tree
         if (R) { hipLaunchKernelGGL(df_mry_walk_kernel, gr, wg, 0, st, g); DF_LAUNCH_CHECK(); }
         return DF_OK;

@@ -17,20 +17,17 @@
 //             triangle index of either parity
 //   decide    fin (|P| == |N|), the lowest index of the larger side (kept) or duplicate; a kept triangle flags itself and, at their
 //             src, its three clusters
-//   scan      two hipcub exclusive sums, in place, one spare element each for the total
+//   scan      df_mesh_scan_pair: two hipcub exclusive sums, in place, one spare element each for the total (the tail dfusion_mesh_filter has)
 //   compact   triangles through cluster and the scanned offsets; one lane per vertex index: a used src writes vertex_src and its
 //             position, every vertex its vertex_map -- the flags sit at the src indices, so the scan puts the clusters in src order
-// Every grid is capped at DF_MSP_MAX_BLOCKS workgroups (524 288 lanes) and strides over its range with 64-bit indices.
-#include <hipcub/hipcub.hpp>
-#include "dfusion_internal.h"
+// Every grid is capped at DF_MESH_MAX_BLOCKS workgroups (524 288 lanes) and strides over its range with 64-bit indices.  The grid, the
+// triangle load, the counting, the overlap test, the workspace carve and the scan tail are the mesh kit's (dfusion_mesh_kit.h).
+#include "dfusion_mesh_kit.h"
 #include <math.h>
 
-#define DF_MSP_MAX_BLOCKS 2048u
 #define DF_MSP_NONE 0xffffffffu
 #define DF_MSP_CELL_LIM 1073741824.f                 // 2^30
 #define DF_MSP_FLAGS (DF_SIMPLIFY_KEEP_FIRST | DF_SIMPLIFY_KEEP_DUPLICATES)
-
-static inline unsigned df_msp_blocks(size_t n) { const size_t b = (n + 255) / 256; return (unsigned)(b < DF_MSP_MAX_BLOCKS ? b : DF_MSP_MAX_BLOCKS); }
 
 struct DfMspArgs {
     const float* vtx; uint32_t V;
@@ -72,18 +69,6 @@ __device__ __forceinline__ bool msp_clusterable(const float* __restrict__ vtx, u
     return ok;
 }
 
-__device__ __forceinline__ bool msp_load(const uint32_t* __restrict__ tris, size_t t, size_t T, uint32_t V, uint32_t (&i)[3])
-{
-    if (t >= T) { i[0] = i[1] = i[2] = 0u; return false; }
-    i[0] = tris[3 * t]; i[1] = tris[3 * t + 1]; i[2] = tris[3 * t + 2];
-    return i[0] < V && i[1] < V && i[2] < V;                             // tested before anything is indexed
-}
-
-__device__ __forceinline__ void msp_count(unsigned long long* counts, int which, unsigned long long wave_uniform)
-{
-    if ((threadIdx.x & 63) == 0 && wave_uniform) atomicAdd(&counts[which], wave_uniform);
-}
-
 __device__ __forceinline__ uint32_t msp_hash(uint32_t a, uint32_t b, uint32_t c, uint32_t slots)
 {
     uint32_t h = a * 73856093u ^ b * 19349663u ^ c * 83492791u;
@@ -98,7 +83,7 @@ __global__ __launch_bounds__(256) void df_msp_mark_kernel(const DfMspArgs a)
     for (size_t t0 = (size_t)blockIdx.x * 256; t0 < a.T; t0 += (size_t)gridDim.x * 256) {      // (workgroup-uniform trip count)
         const size_t t = t0 + threadIdx.x;
         uint32_t i[3];
-        const bool inb = msp_load(a.tris, t, a.T, a.V, i);
+        const bool inb = df_mesh_load(a.tris, t, a.T, a.V, i);
         bool ok[3] = {false, false, false};
         if (inb) {
 #pragma unroll
@@ -115,7 +100,7 @@ __global__ __launch_bounds__(256) void df_msp_mark_kernel(const DfMspArgs a)
         }
         n_invalid += (unsigned long long)__popcll(__ballot(t < a.T && !valid));
     }
-    msp_count(a.counts, 2, n_invalid);
+    df_mesh_wave_add(a.counts, 2, n_invalid);
 }
 
 __global__ __launch_bounds__(256) void df_msp_claim_kernel(const DfMspArgs a)
@@ -160,8 +145,8 @@ __global__ __launch_bounds__(256) void df_msp_sums_kernel(const DfMspArgs a)
         n_clusters += (unsigned long long)__popcll(__ballot(m == 1 && s == (uint32_t)v));
         n_bad += (unsigned long long)__popcll(__ballot(m == 2));
     }
-    msp_count(a.counts, 6, n_clusters);
-    msp_count(a.counts, 7, n_bad);
+    df_mesh_wave_add(a.counts, 6, n_clusters);
+    df_mesh_wave_add(a.counts, 7, n_bad);
 }
 
 // the clusters of a triangle; false unless it is valid and the three differ (collapsed: valid, and two are the same)
@@ -169,7 +154,7 @@ __device__ __forceinline__ bool msp_triple(const DfMspArgs& a, size_t t, uint32_
 {
     uint32_t i[3];
     collapsed = false;
-    if (!msp_load(a.tris, t, a.T, a.V, i)) return false;
+    if (!df_mesh_load(a.tris, t, a.T, a.V, i)) return false;
     c[0] = a.cluster[i[0]]; c[1] = a.cluster[i[1]]; c[2] = a.cluster[i[2]];
     if (c[0] == DF_MSP_NONE || c[1] == DF_MSP_NONE || c[2] == DF_MSP_NONE) return false;      // a valid triangle's vertices are members, and
     collapsed = c[0] == c[1] || c[1] == c[2] || c[0] == c[2];                                   // three members make a valid triangle
@@ -223,7 +208,7 @@ __global__ __launch_bounds__(256) void df_msp_classify_kernel(const DfMspArgs a)
         }
         a.tscan[t] = h;
     }
-    msp_count(a.counts, 3, n_collapsed);
+    df_mesh_wave_add(a.counts, 3, n_collapsed);
 }
 
 __global__ __launch_bounds__(256) void df_msp_decide_kernel(const DfMspArgs a)
@@ -249,18 +234,8 @@ __global__ __launch_bounds__(256) void df_msp_decide_kernel(const DfMspArgs a)
         n_fin += (unsigned long long)__popcll(__ballot(fin));
         n_dup += (unsigned long long)__popcll(__ballot(dup));
     }
-    msp_count(a.counts, 4, n_fin);
-    msp_count(a.counts, 5, n_dup);
-}
-
-__global__ void df_msp_totals_kernel(const uint32_t* tscan, const uint32_t* vscan, size_t T, size_t V, unsigned long long* counts)
-{
-    if (threadIdx.x == 0 && blockIdx.x == 0) { counts[0] = vscan[V]; counts[1] = tscan[T]; }
-}
-
-__global__ void df_msp_set_kernel(unsigned long long* dst, unsigned long long value)
-{
-    if (threadIdx.x == 0 && blockIdx.x == 0) *dst = value;
+    df_mesh_wave_add(a.counts, 4, n_fin);
+    df_mesh_wave_add(a.counts, 5, n_dup);
 }
 
 __global__ __launch_bounds__(256) void df_msp_compact_triangles_kernel(const DfMspArgs a)
@@ -303,13 +278,6 @@ __global__ __launch_bounds__(256) void df_msp_compact_vertices_kernel(const DfMs
     }
 }
 
-static inline bool msp_overlap(const void* p, size_t pn, const void* q, size_t qn)
-{
-    if (!p || !q || !pn || !qn) return false;
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + qn && b < a + pn;
-}
-
 extern "C" int dfusion_mesh_simplify(const float* vertices_dev, unsigned long long n_vertices, const unsigned int* triangles_dev,
                                      unsigned long long n_triangles, float cell, unsigned int flags, float* vertices_out_dev,
                                      unsigned long long vertex_capacity, unsigned int* triangles_out_dev, unsigned long long triangle_capacity,
@@ -325,14 +293,14 @@ extern "C" int dfusion_mesh_simplify(const float* vertices_dev, unsigned long lo
                    {vertex_src_dev, (size_t)vertex_capacity * 4}, {vertex_map_dev, V * 4}, {counts_dev, 64}};
     for (const auto& i : ins)
         for (const auto& o : outs)
-            if (msp_overlap(i.p, i.n, o.p, o.n)) return DF_E_INVALID;
+            if (df_mesh_overlap(i.p, i.n, o.p, o.n)) return DF_E_INVALID;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return DF_E_NO_DEVICE;
     hipStream_t st = (hipStream_t)stream;
     const bool emit = triangle_capacity != 0 || vertex_capacity != 0;
     DF_HIP(hipMemsetAsync(counts_dev, 0, 64, st));
     if (!V || !T) {                                                       // no vertex: every triangle is invalid; no triangle: no member
-        if (!V && T) { hipLaunchKernelGGL(df_msp_set_kernel, dim3(1), dim3(64), 0, st, counts_dev + 2, n_triangles); DF_LAUNCH_CHECK(); }
+        if (!V && T) DF_TRY(df_mesh_set_counts(counts_dev, 2, n_triangles, 2, n_triangles, st));
         return DF_OK;                                                     // (nothing is kept: the exact capacities are 0 and 0, counts only)
     }
     DfMspArgs a;
@@ -345,19 +313,16 @@ extern "C" int dfusion_mesh_simplify(const float* vertices_dev, unsigned long lo
     // than its entries
     a.vslots = (uint32_t)(2 * V + 1 < 0xffffffffull ? 2 * V + 1 : 0xffffffffull);
     a.tslots = grouping ? (uint32_t)(2 * T + 1 < 0xffffffffull ? 2 * T + 1 : 0xffffffffull) : 0u;
-    size_t scan_t = 0, scan_v = 0;
-    DF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_t, (uint32_t*)nullptr, (uint32_t*)nullptr, T + 1, st));
-    DF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_v, (uint32_t*)nullptr, (uint32_t*)nullptr, V + 1, st));
-    size_t scan_bytes = scan_t > scan_v ? scan_t : scan_v;
+    size_t scan_bytes = 0;
+    DF_TRY(df_mesh_scan_bytes((T > V ? T : V) + 1, st, &scan_bytes));
     // workspace: [zeroed: sums 24 V | n 4 V | vertex flags 4 (V + 1) | triangle flags 4 (T + 1) | cell owners | group owners | balances
-    //             | marks V] [set to 0xff: cell minima | group minima, 2 a slot] [cluster 4 V] [hipcub's storage]
-    auto up = [](size_t b) { return (b + 15) / 16 * 16; };
-    const size_t o_sum = 0, o_n = o_sum + up(V * 24), o_vscan = o_n + up(V * 4), o_tscan = o_vscan + up((V + 1) * 4),
-                 o_vowner = o_tscan + up((T + 1) * 4), o_towner = o_vowner + up((size_t)a.vslots * 4), o_tbal = o_towner + up((size_t)a.tslots * 4),
-                 o_mark = o_tbal + up((size_t)a.tslots * 4), zero_end = o_mark + up(V),
-                 o_vmin = zero_end, o_tmin = o_vmin + up((size_t)a.vslots * 4), ff_end = o_tmin + up((size_t)a.tslots * 8),
-                 o_cluster = ff_end, o_scan = (o_cluster + up(V * 4) + 255) / 256 * 256;
-    DfScratchHold hold(st, o_scan + scan_bytes);                          // held until the last launch is enqueued
+    //             | marks V] [set to 0xff: cell minima | group minima, 2 a slot] [cluster 4 V] [hipcub's storage]; one memset a bracket
+    DfMeshCarve c;
+    const size_t o_sum = c.take(V * 24), o_n = c.take(V * 4), o_vscan = c.take((V + 1) * 4), o_tscan = c.take((T + 1) * 4),
+                 o_vowner = c.take((size_t)a.vslots * 4), o_towner = c.take((size_t)a.tslots * 4), o_tbal = c.take((size_t)a.tslots * 4),
+                 o_mark = c.take(V), o_vmin = c.take((size_t)a.vslots * 4), o_tmin = c.take((size_t)a.tslots * 8), o_cluster = c.take(V * 4),
+                 o_scan = c.take(scan_bytes, 256), zero_end = o_vmin, ff_end = o_cluster;
+    DfScratchHold hold(st, c.total());                                    // held until the last launch is enqueued
     if (!hold.entry) return (int)hipErrorOutOfMemory;
     char* const ws = hold.mem;
     a.sum = (unsigned long long*)(ws + o_sum); a.n = (uint32_t*)(ws + o_n); a.vscan = (uint32_t*)(ws + o_vscan); a.tscan = (uint32_t*)(ws + o_tscan);
@@ -365,7 +330,7 @@ extern "C" int dfusion_mesh_simplify(const float* vertices_dev, unsigned long lo
     a.vmin = (uint32_t*)(ws + o_vmin); a.tmin = (uint32_t*)(ws + o_tmin); a.cluster = (uint32_t*)(ws + o_cluster);
     DF_HIP(hipMemsetAsync(ws, 0, zero_end, st));
     DF_HIP(hipMemsetAsync(ws + zero_end, 0xff, ff_end - zero_end, st));
-    const dim3 gt(df_msp_blocks(T)), gv(df_msp_blocks(V)), wg(256);
+    const dim3 gt(df_mesh_blocks(T)), gv(df_mesh_blocks(V)), wg(256);
     hipLaunchKernelGGL(df_msp_mark_kernel, gt, wg, 0, st, a);
     DF_LAUNCH_CHECK();
     hipLaunchKernelGGL(df_msp_claim_kernel, gv, wg, 0, st, a);
@@ -378,10 +343,7 @@ extern "C" int dfusion_mesh_simplify(const float* vertices_dev, unsigned long lo
         hipLaunchKernelGGL(df_msp_decide_kernel, gt, wg, 0, st, a);
         DF_LAUNCH_CHECK();
     }
-    DF_HIP(hipcub::DeviceScan::ExclusiveSum(ws + o_scan, scan_bytes, a.tscan, a.tscan, T + 1, st));
-    DF_HIP(hipcub::DeviceScan::ExclusiveSum(ws + o_scan, scan_bytes, a.vscan, a.vscan, V + 1, st));
-    hipLaunchKernelGGL(df_msp_totals_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)a.tscan, (const uint32_t*)a.vscan, T, V, counts_dev);
-    DF_LAUNCH_CHECK();
+    DF_TRY(df_mesh_scan_pair(ws + o_scan, scan_bytes, a.tscan, T + 1, a.vscan, V + 1, counts_dev, st));
     if (!emit) return DF_OK;
     if (a.tcap) {
         hipLaunchKernelGGL(df_msp_compact_triangles_kernel, gt, wg, 0, st, a);

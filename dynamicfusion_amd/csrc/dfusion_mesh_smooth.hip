@@ -6,13 +6,13 @@
 //
 //   emit, sort, heads   dfusion_mesh_uses.h: the directed uses of every edge as sorted 2k-bit keys (src << k | dst) with a direction
 //             byte, and the position of every run of equal keys -- the position of every CSR entry
-//   edges     one lane per sorted key: a run head writes its dst at its position; the head of a run with src < dst counts the values
-//             of its run (f zeros, b ones), classifies the edge and raises the classes of its two ends by integer atomicMax
+//   edges     one lane per sorted key: a run head writes its dst at its position; the head of a run with src < dst judges its run
+//             (msm_run of dfusion_mesh_uses.h), classifies the edge and raises the classes of its two ends by integer atomicMax
 //   rows      one lane per v in 0 .. V: a binary search for the first key with src >= v; row_start[v] is that key's position
 //   classes   one lane per vertex: its class byte from its degree and the raised word; the vertices with a neighbour and those on a
 //             boundary or irregular edge counted
 //   step      one lane per vertex: dfusion_mesh_smooth's hot path, run 2 x iterations times (below)
-// Every grid is capped at DF_MSM_MAX_BLOCKS workgroups (524 288 lanes) and strides over its range with 64-bit indices.
+// Every grid is capped at DF_MESH_MAX_BLOCKS workgroups (524 288 lanes) and strides over its range with 64-bit indices (dfusion_mesh_kit.h).
 #include "dfusion_mesh_uses.h"                        // emit, sort, heads and the scan: shared with dfusion_mesh_boundary_loops
 #include <math.h>
 
@@ -20,7 +20,13 @@
 
 #define DF_MSM_GATHER 8                              // neighbour positions in flight per lane
 
-__global__ __launch_bounds__(256) void df_msm_edges_kernel(const DfMsmArgs a)
+struct DfMsmAdjArgs : DfMsmArgs {                            // the sorted uses, and what only the adjacency has
+    uint32_t* cls;                                           // [V] 0, raised to 2 (boundary) or 3 (irregular)
+    uint32_t* row_start;                                     // [V + 1] the caller's, or workspace
+    uint32_t* nbr; unsigned long long cap; uint8_t* vclass;
+};
+
+__global__ __launch_bounds__(256) void df_msm_edges_kernel(const DfMsmAdjArgs a)
 {
     const unsigned long long lo_mask = a.k == 32 ? 0xffffffffull : (1ull << a.k) - 1ull;
     unsigned long long n_edges = 0ull, n_boundary = 0ull, n_irregular = 0ull;                  // wave-uniform
@@ -34,11 +40,10 @@ __global__ __launch_bounds__(256) void df_msm_edges_kernel(const DfMsmArgs a)
                 const uint32_t src = (uint32_t)(key >> a.k), dst = (uint32_t)(key & lo_mask);
                 if ((unsigned long long)p < a.cap) a.nbr[p] = dst;
                 if (src < dst) {                                        // the edge {src < dst} is judged once, here
-                    unsigned long long f = 0ull, b = 0ull;              // half-edges src -> dst, dst -> src
-                    for (size_t j = i; j < a.N && a.keys[j] == key; ++j) { if (a.dir[j]) ++b; else ++f; }
+                    const DfMsmRun run = msm_run(a.keys, a.dir, a.N, i);
                     edge = true;
-                    boundary = f + b == 1ull;
-                    irregular = !boundary && !(f == 1ull && b == 1ull);
+                    boundary = run.boundary();
+                    irregular = run.irregular();
                     if (boundary || irregular) {
                         const uint32_t c = irregular ? 3u : 2u;
                         atomicMax(&a.cls[src], c);
@@ -51,12 +56,12 @@ __global__ __launch_bounds__(256) void df_msm_edges_kernel(const DfMsmArgs a)
         n_boundary += (unsigned long long)__popcll(__ballot(boundary));
         n_irregular += (unsigned long long)__popcll(__ballot(irregular));
     }
-    msm_count(a.counts, 1, n_edges);
-    msm_count(a.counts, 2, n_boundary);
-    msm_count(a.counts, 3, n_irregular);
+    df_mesh_wave_add(a.counts, 1, n_edges);
+    df_mesh_wave_add(a.counts, 2, n_boundary);
+    df_mesh_wave_add(a.counts, 3, n_irregular);
 }
 
-__global__ __launch_bounds__(256) void df_msm_rows_kernel(const DfMsmArgs a)
+__global__ __launch_bounds__(256) void df_msm_rows_kernel(const DfMsmAdjArgs a)
 {
     for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v <= a.V; v += (size_t)gridDim.x * 256) {
         size_t lo = 0, hi = a.N;                                        // the first key whose src is >= v (the all-ones key's is 2^k - 1 >= V)
@@ -69,7 +74,7 @@ __global__ __launch_bounds__(256) void df_msm_rows_kernel(const DfMsmArgs a)
     }
 }
 
-__global__ __launch_bounds__(256) void df_msm_classes_kernel(const DfMsmArgs a)
+__global__ __launch_bounds__(256) void df_msm_classes_kernel(const DfMsmAdjArgs a)
 {
     unsigned long long n_used = 0ull, n_open = 0ull;                    // wave-uniform
     for (size_t v0 = (size_t)blockIdx.x * 256; v0 < a.V; v0 += (size_t)gridDim.x * 256) {
@@ -83,13 +88,8 @@ __global__ __launch_bounds__(256) void df_msm_classes_kernel(const DfMsmArgs a)
         n_used += (unsigned long long)__popcll(__ballot(c != 0u));
         n_open += (unsigned long long)__popcll(__ballot(c >= 2u));
     }
-    msm_count(a.counts, 4, n_used);
-    msm_count(a.counts, 7, n_open);
-}
-
-__global__ void df_msm_set_kernel(unsigned long long* dst, unsigned long long value)
-{
-    if (threadIdx.x == 0 && blockIdx.x == 0) *dst = value;
+    df_mesh_wave_add(a.counts, 4, n_used);
+    df_mesh_wave_add(a.counts, 7, n_open);
 }
 
 extern "C" int dfusion_mesh_adjacency(const unsigned int* triangles_dev, unsigned long long n_triangles, unsigned long long n_vertices,
@@ -102,7 +102,7 @@ extern "C" int dfusion_mesh_adjacency(const unsigned int* triangles_dev, unsigne
     const struct { const void* p; size_t n; } outs[4] = {{row_start_dev, (V + 1) * 4}, {neighbours_dev, (size_t)neighbour_capacity * 4},
                                                          {vertex_class_dev, V}, {counts_dev, 64}};
     for (const auto& o : outs)
-        if (msm_overlap(triangles_dev, T * 12, o.p, o.n)) return DF_E_INVALID;
+        if (df_mesh_overlap(triangles_dev, T * 12, o.p, o.n)) return DF_E_INVALID;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return DF_E_NO_DEVICE;
     hipStream_t st = (hipStream_t)stream;
@@ -110,10 +110,10 @@ extern "C" int dfusion_mesh_adjacency(const unsigned int* triangles_dev, unsigne
     if (!V || !T) {                                                       // no vertex: every triangle is invalid; no triangle: no neighbour
         if (row_start_dev) DF_HIP(hipMemsetAsync(row_start_dev, 0, (V + 1) * 4, st));
         if (vertex_class_dev && V) DF_HIP(hipMemsetAsync(vertex_class_dev, 0, V, st));
-        if (!V && T) { hipLaunchKernelGGL(df_msm_set_kernel, dim3(1), dim3(64), 0, st, counts_dev + 5, n_triangles); DF_LAUNCH_CHECK(); }
+        if (!V && T) DF_TRY(df_mesh_set_counts(counts_dev, 5, n_triangles, 5, n_triangles, st));
         return DF_OK;
     }
-    DfMsmArgs a;
+    DfMsmAdjArgs a;
     memset(&a, 0, sizeof(a));
     a.tris = triangles_dev; a.T = T; a.V = V; a.N = N;
     a.k = df_msm_key_bits(V);                                             // 2^k > V
@@ -123,16 +123,16 @@ extern "C" int dfusion_mesh_adjacency(const unsigned int* triangles_dev, unsigne
     DF_TRY(df_msm_uses_cub_bytes(N, a.k, N + 1, st, &cub_bytes));
     // workspace: [the sorted uses' 108 T (dfusion_mesh_uses.h)] [raised classes 4 V, zeroed] [row_start 4 (V + 1), unless the caller
     //            gives one] [hipcub's storage]
-    auto up = [](size_t b) { return (b + 15) / 16 * 16; };
-    const size_t o_cls = df_msm_uses_bytes(N), o_rows = o_cls + up(V * 4), o_cub = (o_rows + (row_start_dev ? 0 : up((V + 1) * 4)) + 255) / 256 * 256;
-    DfScratchHold hold(st, o_cub + cub_bytes);                            // held until the last launch is enqueued
+    DfMeshCarve c; c.take(df_msm_uses_bytes(N));
+    const size_t o_cls = c.take(V * 4), o_rows = row_start_dev ? 0 : c.take((V + 1) * 4), o_cub = c.take(cub_bytes, 256);
+    DfScratchHold hold(st, c.total());                                    // held until the last launch is enqueued
     if (!hold.entry) return (int)hipErrorOutOfMemory;
     char* const ws = hold.mem;
     a.cls = (uint32_t*)(ws + o_cls);
     a.row_start = row_start_dev ? row_start_dev : (uint32_t*)(ws + o_rows);
     DF_HIP(hipMemsetAsync(a.cls, 0, V * 4, st));
     DF_TRY(df_msm_sorted_uses(a, ws, ws + o_cub, cub_bytes, st));
-    const dim3 gn(df_msm_blocks(N + 1)), gv(df_msm_blocks(V + 1)), wg(256);
+    const dim3 gn(df_mesh_blocks(N + 1)), gv(df_mesh_blocks(V + 1)), wg(256);
     hipLaunchKernelGGL(df_msm_edges_kernel, gn, wg, 0, st, a);
     DF_LAUNCH_CHECK();
     hipLaunchKernelGGL(df_msm_rows_kernel, gv, wg, 0, st, a);
@@ -199,7 +199,7 @@ extern "C" int dfusion_mesh_smooth(const float* vertices_dev, unsigned long long
     const struct { const void* p; size_t n; } ins[4] = {{in_place ? nullptr : vertices_dev, V * 16}, {row_start_dev, (V + 1) * 4},
                                                         {neighbours_dev, (size_t)n_neighbours * 4}, {vertex_class_dev, V}};
     for (const auto& i : ins)
-        if (msm_overlap(i.p, i.n, vertices_out_dev, V * 16)) return DF_E_INVALID;
+        if (df_mesh_overlap(i.p, i.n, vertices_out_dev, V * 16)) return DF_E_INVALID;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return DF_E_NO_DEVICE;
     if (!V) return DF_OK;
@@ -216,7 +216,7 @@ extern "C" int dfusion_mesh_smooth(const float* vertices_dev, unsigned long long
     if (!hold.entry) return (int)hipErrorOutOfMemory;
     float4* const scratch = (float4*)hold.mem;
     float4* const out = (float4*)vertices_out_dev;
-    const dim3 grid(df_msm_blocks(V)), wg(256);
+    const dim3 grid(df_mesh_blocks(V)), wg(256);
     const float4* src = (const float4*)vertices_dev;
     float4* dst = nullptr;
     for (size_t k = 0; k < steps; ++k) {

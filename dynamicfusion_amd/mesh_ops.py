@@ -23,6 +23,29 @@ def _triangles(triangles):
     return (_flat(triangles) if nt else None), nt
 
 
+def _points4(x, what, letter="N"):
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 4 or not x.is_contiguous():
+        raise ValueError("%s %s %s, expected contiguous float32 [%s, 4]" % (what, x.dtype, tuple(x.shape), letter))
+    return int(x.shape[0])
+
+
+def _mesh_vertices(vertices, triangles):
+    """The checks of an operation that takes the vertices with the triangles -> V."""
+    nv = _points4(vertices, "vertices", "V")
+    if vertices.device != triangles.device:
+        raise ValueError("vertices on %s, triangles on %s" % (vertices.device, triangles.device))
+    return nv
+
+
+def _count_then_exact(run, counts):
+    """One count-only call, the read-back of counts[0] = output vertices and counts[1] = output triangles, then -- unless both are 0 --
+    one call of exactly that size.  run(n_vertices, n_triangles) allocates outputs of these capacities, makes the call and returns
+    them.  -> the outputs of the last call."""
+    outs = run(0, 0)
+    kv, kt = (int(c) for c in counts[:2].tolist())
+    return run(kv, kt) if kv or kt else outs
+
+
 def mesh_components(triangles, n_vertices, return_counts=False):
     """triangles int32 [T, 3] (uint32 bits) over n_vertices vertices -> (vertex_label int32 [V]: the smallest vertex index of every
     vertex's component, triangle_count int32 [V]: the valid triangles of the component labelled r, 0 where r is no label), both uint32
@@ -71,17 +94,15 @@ def remove_small_components(vertices, triangles, min_triangles=0, keep_largest=F
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     L = capi.lib()
 
-    def run(tri_out, n_tri, src, n_src):
+    def run(kv, kt):
+        tri_out = torch.empty((kt, 3), dtype=torch.int32, device=dev)
+        src = torch.empty(kv, dtype=torch.int32, device=dev)
         capi.check(L.dfusion_mesh_filter(tp, nt, nv, _flat(label) if nv else None, _flat(count) if nv else None, int(min_triangles),
-                                         1 if keep_largest else 0, _flat(tri_out) if n_tri else None, n_tri,
-                                         _flat(src) if n_src else None, n_src, None, _flat(counts), _stream()), "dfusion_mesh_filter")
+                                         1 if keep_largest else 0, _flat(tri_out) if kt else None, kt,
+                                         _flat(src) if kv else None, kv, None, _flat(counts), _stream()), "dfusion_mesh_filter")
+        return tri_out, src
 
-    run(None, 0, None, 0)
-    kv, kt = (int(c) for c in counts.tolist())
-    tri_out = torch.empty((kt, 3), dtype=torch.int32, device=dev)
-    src = torch.empty(kv, dtype=torch.int32, device=dev)
-    if kv or kt:
-        run(tri_out, kt, src, kv)
+    tri_out, src = _count_then_exact(run, counts)
     return gather_rows(vertices, src), tri_out, tuple(gather_rows(a, src) for a in attributes), src
 
 
@@ -98,29 +119,23 @@ def simplify_mesh(vertices, triangles, cell, keep_first=False, keep_duplicates=F
     with return_counts also counts int64 [8]: output vertices, output triangles, invalid, collapsed, fin and duplicate triangles,
     clusters, unclusterable vertices.  One count-only call, then one of exactly that size (the counts are read back)."""
     tp, nt = _triangles(triangles)
-    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 4 or not vertices.is_contiguous():
-        raise ValueError("vertices %s %s, expected contiguous float32 [V, 4]" % (vertices.dtype, tuple(vertices.shape)))
-    if vertices.device != triangles.device:
-        raise ValueError("vertices on %s, triangles on %s" % (vertices.device, triangles.device))
-    nv = int(vertices.shape[0])
+    nv = _mesh_vertices(vertices, triangles)
     dev = triangles.device
     flags = (KEEP_FIRST if keep_first else 0) | (KEEP_DUPLICATES if keep_duplicates else 0)
     counts = torch.empty(8, dtype=torch.int64, device=dev)
+    vmap = torch.full((nv,), -1, dtype=torch.int32, device=dev)             # nothing kept: every entry stays 0xffffffff
     L = capi.lib()
 
-    def run(out_v, n_v, out_t, n_t, src, vmap):
-        capi.check(L.dfusion_mesh_simplify(_flat(vertices) if nv else None, nv, tp, nt, float(cell), flags, _flat(out_v) if n_v else None, n_v,
-                                           _flat(out_t) if n_t else None, n_t, _flat(src) if n_v else None, _flat(vmap) if vmap is not None and nv else None,
+    def run(kv, kt):
+        out_v = torch.empty((kv, 4), dtype=torch.float32, device=dev)
+        out_t = torch.empty((kt, 3), dtype=torch.int32, device=dev)
+        src = torch.empty(kv, dtype=torch.int32, device=dev)
+        capi.check(L.dfusion_mesh_simplify(_flat(vertices) if nv else None, nv, tp, nt, float(cell), flags, _flat(out_v) if kv else None, kv,
+                                           _flat(out_t) if kt else None, kt, _flat(src) if kv else None, _flat(vmap) if (kv or kt) and nv else None,
                                            _flat(counts), _stream()), "dfusion_mesh_simplify")
+        return out_v, out_t, src
 
-    run(None, 0, None, 0, None, None)
-    kv, kt = (int(c) for c in counts[:2].tolist())
-    out_v = torch.empty((kv, 4), dtype=torch.float32, device=dev)
-    out_t = torch.empty((kt, 3), dtype=torch.int32, device=dev)
-    src = torch.empty(kv, dtype=torch.int32, device=dev)
-    vmap = torch.full((nv,), -1, dtype=torch.int32, device=dev)             # nothing kept: every entry stays 0xffffffff
-    if kv or kt:
-        run(out_v, kv, out_t, kt, src, vmap)
+    out_v, out_t, src = _count_then_exact(run, counts)
     return (out_v, out_t, src, vmap, counts) if return_counts else (out_v, out_t, src, vmap)
 
 
@@ -195,29 +210,23 @@ def fill_holes(vertices, triangles, max_edges, return_counts=False):
     [V + F]: i for an old vertex, 0xffffffff for a new one, which has no source row); with return_counts also counts int64 [8]
     (FILL_COUNT_NAMES).  One count-only call, then one of exactly that size (the counts are read back)."""
     tp, nt = _triangles(triangles)
-    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 4 or not vertices.is_contiguous():
-        raise ValueError("vertices %s %s, expected contiguous float32 [V, 4]" % (vertices.dtype, tuple(vertices.shape)))
-    if vertices.device != triangles.device:
-        raise ValueError("vertices on %s, triangles on %s" % (vertices.device, triangles.device))
+    nv = _mesh_vertices(vertices, triangles)
     if not 0 <= int(max_edges) <= 0xffffffff:
         raise ValueError("max_edges %r, expected 0 .. 2^32 - 1" % (max_edges,))
-    nv = int(vertices.shape[0])
     dev = triangles.device
     counts = torch.empty(8, dtype=torch.int64, device=dev)
     L = capi.lib()
 
-    def run(out_v, n_v, out_t, n_t, src):
-        capi.check(L.dfusion_mesh_fill_holes(_flat(vertices) if nv else None, nv, tp, nt, int(max_edges), 0, _flat(out_v) if n_v else None, n_v,
-                                             _flat(out_t) if n_t else None, n_t, _flat(src) if n_v else None, _flat(counts), _stream()),
+    def run(kv, kt):
+        out_v = torch.empty((kv, 4), dtype=torch.float32, device=dev)
+        out_t = torch.empty((kt, 3), dtype=torch.int32, device=dev)
+        src = torch.empty(kv, dtype=torch.int32, device=dev)
+        capi.check(L.dfusion_mesh_fill_holes(_flat(vertices) if nv else None, nv, tp, nt, int(max_edges), 0, _flat(out_v) if kv else None, kv,
+                                             _flat(out_t) if kt else None, kt, _flat(src) if kv else None, _flat(counts), _stream()),
                    "dfusion_mesh_fill_holes")
+        return out_v, out_t, src
 
-    run(None, 0, None, 0, None)
-    kv, kt = (int(c) for c in counts[:2].tolist())
-    out_v = torch.empty((kv, 4), dtype=torch.float32, device=dev)
-    out_t = torch.empty((kt, 3), dtype=torch.int32, device=dev)
-    src = torch.empty(kv, dtype=torch.int32, device=dev)
-    if kv or kt:
-        run(out_v, kv, out_t, kt, src)
+    out_v, out_t, src = _count_then_exact(run, counts)
     return (out_v, out_t, src, counts) if return_counts else (out_v, out_t, src)
 
 
@@ -227,11 +236,7 @@ def smooth_mesh(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, fix_bound
     result; with fix_boundary only the vertices of class 1 move.  vertices float32 [V, 4], triangles int32 [T, 3] (uint32 bits) -> new
     vertices float32 [V, 4]; the triangles stay as they are.  adjacency: mesh_adjacency's (row_start, neighbours, vertex_class) of
     this mesh, built here when None.  Nothing synchronises when an adjacency is given."""
-    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 4 or not vertices.is_contiguous():
-        raise ValueError("vertices %s %s, expected contiguous float32 [V, 4]" % (vertices.dtype, tuple(vertices.shape)))
-    if vertices.device != triangles.device:
-        raise ValueError("vertices on %s, triangles on %s" % (vertices.device, triangles.device))
-    nv = int(vertices.shape[0])
+    nv = _mesh_vertices(vertices, triangles)
     row_start, neighbours, vertex_class = mesh_adjacency(triangles, nv) if adjacency is None else adjacency[:3]
     if int(row_start.shape[0]) != nv + 1 or (vertex_class is not None and int(vertex_class.shape[0]) != nv):
         raise ValueError("adjacency of %d vertices for %d vertices" % (int(row_start.shape[0]) - 1, nv))
@@ -245,12 +250,6 @@ def smooth_mesh(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, fix_bound
 
 CLOSEST_COUNT_NAMES = ("answered", "unanswered", "eligible_triangles", "skipped_triangles", "max_d2_bits", "max_query", "triangle_tests",
                        "nodes_visited")
-
-
-def _points4(x, what):
-    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 4 or not x.is_contiguous():
-        raise ValueError("%s %s %s, expected contiguous float32 [N, 4]" % (what, x.dtype, tuple(x.shape)))
-    return int(x.shape[0])
 
 
 def closest_points(vertices, triangles, points, max_distance=None, return_barycentric=False, return_counts=False):

@@ -11,6 +11,7 @@ import torch
 import mesh_closest_ref as M
 import mesh_ref as R
 from dynamicfusion_amd import capi, closest_points, mesh_distance, mesh_ops, simplify_mesh
+from mesh_gpu import ptr, stream, u32
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -18,20 +19,8 @@ INVALID = 100001
 GUARD = 4                                            # guard rows behind every output
 G32 = -7                                             # what they hold
 NONE = M.NONE
-GRID_CAP = 2048 * 256                                # DF_MSM_MAX_BLOCKS workgroups of 256 lanes: past it a lane takes a second element
+GRID_CAP = 2048 * 256                                # DF_MESH_MAX_BLOCKS workgroups of 256 lanes: past it a lane takes a second element
 INF = float("inf")
-
-
-def ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 def raw(v, t, q, max_d2=INF, with_bary=True):

@@ -9,24 +9,13 @@ import torch
 import mesh_components_ref as M
 import mesh_ref as R
 from dynamicfusion_amd import Intr, capi, frontend, mesh_components, mesh_ops, remove_small_components, synth
+from mesh_gpu import dev_tri, ptr, same_bits, u32
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 INVALID = 100001
 GUARD = 4                                            # guard rows behind every output
 G32 = -7                                             # what they hold (0xfffffff9)
-
-
-def ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def dev_tri(tri):
-    return torch.from_numpy(np.ascontiguousarray(tri, np.uint32).view(np.int32).reshape(-1, 3)).cuda()
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 def raw_components(tri, V, with_count=True, with_counts=True, tri_dev=None):
@@ -306,10 +295,6 @@ def fused_scene():
     wf.init(sc.pos, sigma=sc.sigma, transforms=sc.dqs[2])
     ref = R.extract_mesh(S.vols[2], S.cfg.dims, sc.vs, synth.aff12(sc.pose))
     return S, vol, cv, wf, intr, ref
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
 
 
 def test_fetch_mesh_and_render_live_model_on_a_fused_scene():

@@ -11,6 +11,7 @@ import mesh_holes_ref as H
 import mesh_ref as R
 import mesh_smooth_ref as S
 from dynamicfusion_amd import boundary_loops, capi, fill_holes, mesh_ops
+from mesh_gpu import ptr, same_bits, same_or_both_nan, stream, u32
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -18,20 +19,8 @@ INVALID = 100001
 GUARD = 4                                            # guard rows behind every output
 G32 = -7                                             # what they hold
 NONE = H.NONE
-GRID_CAP = 2048 * 256                                # DF_MSM_MAX_BLOCKS workgroups of 256 lanes: past it a lane takes a second element
+GRID_CAP = 2048 * 256                                # DF_MESH_MAX_BLOCKS workgroups of 256 lanes: past it a lane takes a second element
 ALL = 0xffffffff
-
-
-def ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 class Mesh:
@@ -103,13 +92,6 @@ def raw_fill(m, max_edges, vcap, tcap, with_src=True, flags=0):
     assert (out_v[vcap:] == G32).all() and (out_t[tcap:] == G32).all() and (src[vcap:] == G32).all() and (counts[8:] == 123).all()
     assert with_src or (src == G32).all()
     return u32(out_v[:vcap]), u32(out_t[:tcap]), u32(src[:vcap]), counts[:8].cpu().numpy().astype(np.uint64)
-
-
-def same_or_both_nan(got_u32, want_f32):
-    """Bit-equal, except that wherever the restatement has a NaN the GPU has a NaN (payloads differ between x86 and the GPU)."""
-    got = got_u32.view(F32)
-    nan = np.isnan(want_f32)
-    return np.array_equal(np.isnan(got), nan) and np.array_equal(got_u32[~nan], want_f32.view(np.uint32)[~nan])
 
 
 def check_fill(m, max_edges, nan_ok=False):
@@ -420,10 +402,6 @@ def test_mirror_functions_equal_the_restatement():
     assert fill_holes(m.vd[:0], m.td[:0], 9)[0].shape == (0, 4)
     gv, gt, src = fill_holes(m.vd, m.td[:0], 9)                                           # no triangle: the vertices are copied
     assert np.array_equal(u32(gv), m.v.view(np.uint32)) and gt.shape == (0, 3) and u32(src).tolist() == list(range(m.V))
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
 
 
 def test_fetch_mesh_with_fill_holes_max_edges_on_a_fused_scene():

@@ -12,6 +12,7 @@ import mesh_closest_ref as M
 import mesh_rays_ref as Y
 import mesh_ref as R
 from dynamicfusion_amd import capi, mesh_ops, ray_hits, visible_points
+from mesh_gpu import ptr, stream, u32
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -20,20 +21,8 @@ GUARD = 4                                            # guard rows behind every o
 G32 = -7                                             # what they hold
 NONE = Y.NONE
 ANY = 1                                              # DF_RAYS_ANY_HIT
-GRID_CAP = 2048 * 256                                # DF_MSM_MAX_BLOCKS workgroups of 256 lanes: past it a lane takes a second element
+GRID_CAP = 2048 * 256                                # DF_MESH_MAX_BLOCKS workgroups of 256 lanes: past it a lane takes a second element
 INF = float("inf")
-
-
-def ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 def raw(v, t, o, d, t_min=0.0, t_max=INF, flags=0, with_bary=True):

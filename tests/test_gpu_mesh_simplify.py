@@ -8,6 +8,7 @@ import torch
 
 import mesh_simplify_ref as S
 from dynamicfusion_amd import capi, mesh_ops, simplify_mesh
+from mesh_gpu import dev_tri, dev_vtx, ptr, same_bits, stream, u32
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -16,27 +17,7 @@ GUARD = 4                                            # guard rows behind every o
 G32 = -7                                             # what they hold (0xfffffff9)
 KF, KD = S.KEEP_FIRST, S.KEEP_DUPLICATES
 ALL_FLAGS = (0, KF, KD, KF | KD)
-GRID_CAP = 2048 * 256                                # DF_MSP_MAX_BLOCKS workgroups of 256 lanes: past it a lane takes a second element
-
-
-def ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def dev_tri(tri):
-    return torch.from_numpy(np.ascontiguousarray(tri, np.uint32).view(np.int32).reshape(-1, 3)).cuda()
-
-
-def dev_vtx(v):
-    return torch.from_numpy(np.ascontiguousarray(v, F32).reshape(-1, 4)).cuda()
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32)
+GRID_CAP = 2048 * 256                                # DF_MESH_MAX_BLOCKS workgroups of 256 lanes: past it a lane takes a second element
 
 
 class Mesh:
@@ -289,10 +270,6 @@ def test_mirror_function_equals_the_restatement():
     assert e[0].shape == (0, 4) and e[1].shape == (0, 3) and e[2].shape == (0,) and (u32(e[3]) == S.NONE).all() and e[3].shape == (len(mesh.vertices),)
     e = simplify_mesh(vd[:0], td[:0], cell, return_counts=True)
     assert e[3].shape == (0,) and e[4].tolist() == [0] * 8
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
 
 
 def test_fetch_mesh_with_a_simplify_cell_on_a_fused_scene():

@@ -10,6 +10,7 @@ import torch
 import mesh_ref as R
 import mesh_smooth_ref as S
 from dynamicfusion_amd import capi, mesh_adjacency, mesh_ops, mesh_topology, smooth_mesh
+from mesh_gpu import ptr, same_bits, same_or_both_nan, stream, u32
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -17,20 +18,8 @@ INVALID = 100001
 GUARD = 4                                            # guard rows behind every output
 G32, G8 = -7, 0xa5                                   # what they hold
 FIX = S.FIX_BOUNDARY
-GRID_CAP = 2048 * 256                                # DF_MSM_MAX_BLOCKS workgroups of 256 lanes: past it a lane takes a second element
+GRID_CAP = 2048 * 256                                # DF_MESH_MAX_BLOCKS workgroups of 256 lanes: past it a lane takes a second element
 ITERATIONS = (0, 1, 2, 5)
-
-
-def ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 class Mesh:
@@ -92,13 +81,6 @@ def raw_smooth(m, iterations, lam=0.5, mu=-0.53, flags=FIX, with_class=True, in_
     torch.cuda.synchronize()
     assert (out[m.V:] == G32).all()
     return u32(out[:m.V])
-
-
-def same_or_both_nan(got_u32, want_f32):
-    """Bit-equal, except that wherever the restatement has a NaN the GPU has a NaN (payloads differ between x86 and the GPU)."""
-    got = got_u32.view(F32)
-    nan = np.isnan(want_f32)
-    return np.array_equal(np.isnan(got), nan) and np.array_equal(got_u32[~nan], want_f32.view(np.uint32)[~nan])
 
 
 def check_smooth(m, iterations=ITERATIONS, lam=0.5, mu=-0.53, flags=FIX, with_class=True, in_place=False):
@@ -366,10 +348,6 @@ def test_mirror_functions_equal_the_restatement():
     assert u32(e[0]).tolist() == [0] * 6 and e[1].shape == (0,) and e[2].tolist() == [0] * 5 and e[3].tolist() == [0] * 8
     assert smooth_mesh(m.vd[:0], m.td[:0]).shape == (0, 4)
     assert np.array_equal(u32(smooth_mesh(m.vd, m.td[:0])), m.v.view(np.uint32))                                     # no triangle: nothing moves
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
 
 
 def test_fetch_mesh_with_smooth_iterations_on_a_fused_scene():
